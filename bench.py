@@ -6,8 +6,12 @@ completed surfaces pasted into 16 KITTI-shaped ray-cast scenes (~17k pts each), 
 VoxelBackBone8x (sparse 3-D conv) + HeightCompression forward, loss, backward, SGD step.  Inputs are resident in
 HBM before the timed region.  Scenes shard data-parallel (weak scaling); gradients are all-reduced over RCCL.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]     the headline line only
+  python bench.py --full [--no-kernel-rooflines] [--no-cpu-baseline] [--no-side-modes] ...     + roofline blocks, CPU baseline, side modes
   python bench.py --config {stageA,second,pvrcnn,centerpoint} [--gpus N] [--steps K] [--warmup W]     side modes (bench_configs.py)
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, 28 MB at the default size; dump_outputs): the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the process is only a launcher: it starts N rank processes (one GPU each,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before anything touches the GPU and exits with their status -- the role of
@@ -115,10 +119,62 @@ def allreduce_grads(params, world):
     torch._foreach_copy_(grads, views)
 
 
-def run_step(model, opt, params, inputs, world):
+DUMP_SAMPLE = 1 << 22                 # values of the dense BEV tensor kept by --dump-outputs (of 144 M at the default size)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def keep_outputs(keep, bd_in, bd_out):
+    """--dump-outputs: the voxelised input of the trained side and a sample of the dense BEV tensor it produced (577 MB whole) -- DUMP_SAMPLE
+    values at seeded positions, gathered on the device in logical (B, C, H, W) order whatever its memory format.  Runs in the last warm-up
+    step too: the positions are drawn there (kept under "_sample_index") and the first launches of these kernels stay out of the timed steps."""
+    sf = bd_out["spatial_features"].detach()
+    idx = keep.get("_sample_index")
+    if idx is None:
+        gen = torch.Generator(device=sf.device)
+        gen.manual_seed(0)
+        idx = keep["_sample_index"] = torch.randint(sf.numel(), (min(DUMP_SAMPLE, sf.numel()),), generator=gen, device=sf.device).sort().values
+    keep["spatial_features_sample"] = torch.take(sf, idx)
+    keep["voxel_features"] = bd_in["voxel_features"].detach()
+    keep["voxel_coords"] = bd_in["voxel_coords"]
+
+
+def dump_outputs(out_dir, model, loss, keep):
+    """--dump-outputs DIR: what the last timed step hands its caller, as DIR/<name>.npy in float32 -- the loss, the trained parameters after
+    the optimiser step and their gradients, the floating-point buffers (BatchNorm running statistics), and keep_outputs' arrays (voxel
+    coordinates as float32: exact, they are below 2^24).  Above 64 MB in all, a seeded sample of the voxel rows.  Written after the timed
+    region, before anything else runs a step."""
+    arrays = {"loss": loss}
+    arrays.update((k, v) for k, v in keep.items() if not k.startswith("_"))
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            arrays[f"param.{name}"] = p
+            if p.grad is not None:
+                arrays[f"grad.{name}"] = p.grad
+    for name, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays[f"buffer.{name}"] = b
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        # larger batches (--scenes-per-gpu): a seeded sample of the voxel rows, the same rows of features and coordinates, fits the limit
+        vf, vc = host["voxel_features"], host["voxel_coords"]
+        room = DUMP_LIMIT_BYTES - (total - vf.nbytes - vc.nbytes)
+        rows = int(room // (vf.itemsize * vf.shape[1] + vc.itemsize * vc.shape[1])) if room > 0 else 0
+        if rows < 1:
+            raise RuntimeError(f"--dump-outputs: {total / 2**20:.1f} MB of outputs, above the {DUMP_LIMIT_BYTES >> 20} MB limit")
+        sel = np.sort(np.random.default_rng(0).choice(len(vf), rows, replace=False))
+        host["voxel_features"], host["voxel_coords"] = vf[sel], vc[sel]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_step(model, opt, params, inputs, world, keep=None):
     points, objects, scene = inputs
     opt.zero_grad(set_to_none=True)
     bd = model(points, objects, scene, SCENES_PER_GPU)
+    if keep is not None:
+        keep_outputs(keep, bd, bd)
     loss = loss_fn(bd)
     loss.backward()
     allreduce_grads(params, world)
@@ -229,10 +285,12 @@ class Prefetch:
             _lib.flush_checks()                # the last front_a's parked check (its batch is never trained on)
 
 
-def _compute_gen(model, opt, params, bd, world, out):
+def _compute_gen(model, opt, params, bd, world, out, keep=None):
     """The trained side of one batch as a generator: yields between pieces so that the caller can enqueue them one at a time."""
     opt.zero_grad(set_to_none=True)
     res = yield from model.compute_stages(bd)
+    if keep is not None:
+        keep_outputs(keep, bd, res)
     loss = loss_fn(res)
     yield
     loss.backward()
@@ -242,7 +300,7 @@ def _compute_gen(model, opt, params, bd, world, out):
     out.append(loss)
 
 
-def run_step_prefetched(model, opt, params, pre, world, interleave=True):
+def run_step_prefetched(model, opt, params, pre, world, interleave=True, keep=None):
     """One step = compute(N) on the main stream + front(N + 1) on the side stream, enqueued by ONE host thread, whose time is what the step is
     made of (round 4: ~1.6 ms to enqueue the trained side, ~1.9 ms for the input side, against 3.8 ms of main-stream GPU time).  The input side has
     ONE blocking device -> host read (voxel count + the strided levels' site counts).  Order: forward + loss of batch N right away (the main
@@ -262,7 +320,7 @@ def run_step_prefetched(model, opt, params, pre, world, interleave=True):
         pre.__dict__["_backpressure_s"] = pre.__dict__.get("_backpressure_s", 0.0) + (time.perf_counter() - t_w)      # host time blocked here: > 0 = the GPU is the slower side
     bd = pre.take()
     out = []
-    gen = _compute_gen(model, opt, params, bd, world, out)
+    gen = _compute_gen(model, opt, params, bd, world, out, keep)
     main = torch.cuda.current_stream()
 
     def rest():
@@ -552,11 +610,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)     # 0.8 s timed: 20-step runs of this 4 ms step scattered by +-5 % on one box
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure what it does not need: the per-kernel event timing "
+                    "(roofline blocks), the CPU baseline and the brief runs of the other BASELINE configs (side modes); without it the run "
+                    "sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32, "
+                    "at most 64 MB; dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--scenes-per-gpu", type=int, default=None, help="override the 16 scenes per GPU (tests)")
     ap.add_argument("--objects-per-gpu", type=int, default=None, help="override the 64 objects per GPU (tests)")
-    ap.add_argument("--no-side-modes", action="store_true", help="skip the brief runs of the other BASELINE configs after the headline")
-    ap.add_argument("--no-kernel-rooflines", action="store_true", help="skip the per-kernel event timing after the timed region (tests)")
+    ap.add_argument("--no-side-modes", action="store_true", help="with --full: skip the brief runs of the other BASELINE configs after the headline")
+    ap.add_argument("--no-kernel-rooflines", action="store_true", help="with --full: skip the per-kernel event timing after the timed region (tests)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only control flow of the multi-rank path (gloo), no kernels")
     ap.add_argument("--no-prefetch", action="store_true", help="run the input side (stage A, voxelise, rulebooks) in line on the main stream")
     ap.add_argument("--no-interleave", action="store_true", help="enqueue the WHOLE trained side before the input side instead of its backward half inside the input side's read (A/B)")
@@ -570,6 +633,10 @@ def main():
     ap.add_argument("--config", default="main", choices=("main", "stageA", "second", "pvrcnn", "centerpoint"),
                     help="main (default): the headline step; the others are side modes over the other BASELINE configs (bench_configs.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config != "main" or args.roofline_only or args.dry_run):
+        ap.error("--dump-outputs applies to the headline step only (not with --config, --roofline-only or --dry-run)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -635,9 +702,13 @@ def main():
         main_ctx = torch.cuda.stream(main_stream)
     main_ctx.__enter__()
     pre = None if args.no_prefetch else Prefetch(model, inputs, threaded=args.prefetch_thread)
-    step = (lambda: run_step(model, opt, params, inputs, world)) if pre is None else (lambda: run_step_prefetched(model, opt, params, pre, world, not args.no_interleave))
-    for _ in range(args.warmup):
-        step()
+    step = ((lambda keep=None: run_step(model, opt, params, inputs, world, keep)) if pre is None else
+            (lambda keep=None: run_step_prefetched(model, opt, params, pre, world, not args.no_interleave, keep)))
+    keep = {} if args.dump_outputs else None     # filled by the last warm-up step (first launches), then by the last timed step
+    for i in range(args.warmup):
+        step(keep if i == args.warmup - 1 else None)
+    if keep:
+        keep = {"_sample_index": keep["_sample_index"]}      # the warm-up's arrays are not outputs: only the drawn positions stay
     if pre is not None:
         pre.wait_issued()              # the front of the first timed batch: enqueued and (next line) finished before the clock starts
     if world > 1:
@@ -650,8 +721,8 @@ def main():
         pre.__dict__["_backpressure_s"] = 0.0
     t0 = time.perf_counter()
     stamps = []                        # host clock after every step's enqueue (a pipelined step ends in a blocking read: stamps follow the steps): one
-    for _ in range(args.steps):        # perf_counter call per step, reported as the slowest / median step interval so that a transient shows in the line
-        step()
+    for i in range(args.steps):        # perf_counter call per step, reported as the slowest / median step interval so that a transient shows in the line
+        loss = step(keep if i == args.steps - 1 else None)
         stamps.append(time.perf_counter())
     if pre is not None:
         pre.wait_issued()              # K steps = K computes + K fronts: the last front issued belongs to the timed region
@@ -699,15 +770,17 @@ def main():
                                  "host_blocked_on_gpu_ms": None if backpressure_ms is None else round(backpressure_ms, 3)},
             "ranks": ident, "backend": (backend if world > 1 else None),
         }
-        if not args.no_kernel_rooflines:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, loss, keep)     # before the --full blocks below run steps of their own
+        if args.full and not args.no_kernel_rooflines:
             # rank 0 only, so NO collective inside: the measured steps run with world = 1 (the exchange step is skipped)
             kernel_rooflines(out, model, opt, params, inputs)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pts_np, objs_np, scene_np)
-        if not args.no_side_modes and world == 1:
+        if args.full and not args.no_side_modes and world == 1:
             # the other BASELINE configs, a few steps each, AFTER the headline was measured (its numbers above are final): same protocol as
-            # `--config X`, so that the driver's one command sees them too
-            del model, opt, params, inputs, points, objects, scene, pre, step
+            # `--config X`, so that `--full` sees them too
+            del model, opt, params, inputs, points, objects, scene, pre, step, loss, keep
             out["side_modes"] = side_modes_brief(device)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -53,7 +53,12 @@ size_t sv_index_scratch_bytes(int64_t ncells);
  *   columns after batch_idx are averaged.  Outputs are ordered by ascending key (same as torch.unique):
  *   voxel_coords (cap,4) int32 [b,z,y,x], voxel_features (cap,num_features), point_to_voxel (P) int32
  *   (row of the voxel each point fell in, -1 if out of range; may be NULL), *num_voxels (device int32).
- *   index_ws: sv_index_persistent_bytes(batch*X*Y*Z); scratch: sv_voxelize_dynamic_scratch_bytes().
+ *   index_ws: sv_index_persistent_bytes(batch*X*Y*Z); scratch: sv_voxelize_dynamic_scratch_bytes() (it includes a
+ *   capacity x 4 x 8 B fixed-point accumulator).
+ *   Means: with num_features <= 4, finite values with |v| < 2^15 (of a voxel's first 2^16 points) are summed as 64-bit
+ *   fixed point (v x 2^32, exact for |v| >= 2^-9, off by <= 2^-33 below) -- order independent, so bit-reproducible
+ *   run to run; NaN, +-inf, larger values and further points are summed in fp32 (NaN propagates).  The mean is
+ *   (fixed sum + fp32 sum) / count in fp64, rounded once to fp32.  num_features > 4: fp32 sums in arrival order.
  * ---------------------------------------------------------------------------------------------- */
 size_t sv_voxelize_dynamic_scratch_bytes(int64_t num_points, int64_t ncells, int64_t capacity);
 int sv_voxelize_dynamic(const float* points, int64_t num_points, int point_stride, int num_features,

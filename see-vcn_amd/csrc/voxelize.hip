@@ -2,8 +2,16 @@
 //
 // No sort: points set bits in the persistent coordinate index (dense bitmap in HBM), a scan over the
 // per-chunk counts gives every occupied cell its position in ascending key order (= torch.unique order
-// of dynamic_mean_vfe.py:62), points then accumulate into their voxel row with fp32 atomics and the last
-// pass divides by the count and returns the touched index words to zero.
+// of dynamic_mean_vfe.py:62), points then accumulate into their voxel row and the last pass divides by the count
+// and returns the touched index words to zero.
+//
+// Sums (up to VOX_FIXED_MAX_FEATURES features): a finite value with |v| < 2^15 from one of the first 2^16 points to
+// arrive in its voxel is added as 64-bit fixed point, llrint(v * 2^32), with an integer atomic -- integer sums do not
+// depend on the order the points arrive in, so such voxels come out bit for bit the same every run (fp32 atomics round
+// in arrival order).  The conversion is exact for |v| >= 2^-9 and off by at most 2^-33 below; |term| < 2^47 and at most
+// 2^16 terms keep |sum| < 2^63.  Every other value (NaN, +-inf, |v| >= 2^15, points past the 2^16th) goes to an fp32
+// atomic sum as before, so it propagates or is summed in arrival order.  The finalize pass divides (fixed sum * 2^-32 +
+// fp32 sum) by the count in fp64 and rounds once to fp32.  More features: fp32 atomic sums only.
 #include "common.h"
 
 struct VoxGeom {
@@ -14,6 +22,10 @@ struct VoxGeom {
 };
 
 constexpr int VOX_THREADS = 256;
+constexpr int VOX_FIXED_MAX_FEATURES = 4;        // features summed in fixed point (scratch holds capacity x 4 x 8 B)
+constexpr float VOX_FIXED_SCALE = 4294967296.0f; // 2^32
+constexpr float VOX_FIXED_MAX_ABS = 32768.0f;     // 2^15: |v * 2^32| < 2^47
+constexpr int32_t VOX_FIXED_MAX_POINTS = 65536;   // 2^16 terms of < 2^47: |sum| < 2^63
 
 __device__ __forceinline__ int64_t vox_key(const float* __restrict__ p, const VoxGeom& g) {
   // floor((xyz - min) / voxel) exactly as torch does it in fp32 (dynamic_mean_vfe.py:53): IEEE sub, IEEE div
@@ -30,10 +42,12 @@ __device__ __forceinline__ int64_t vox_key(const float* __restrict__ p, const Vo
 
 __global__ __launch_bounds__(VOX_THREADS) void k_vox_mark(const float* __restrict__ points, int64_t n, int stride,
                                                           VoxGeom g, SvIndexView ix, int64_t* __restrict__ keys, int32_t* __restrict__ cnt,
-                                                          int64_t capacity, float* __restrict__ feats, int64_t feat_words) {
-  // the accumulators of k_vox_accum (two launches later) start from zero: cleared here instead of by two memsets
+                                                          int64_t capacity, float* __restrict__ feats, int64_t feat_words,
+                                                          uint32_t* __restrict__ acc, int64_t acc_words) {
+  // the accumulators of k_vox_accum (two launches later) start from zero: cleared here instead of by memsets
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < capacity; i += (int64_t)gridDim.x * blockDim.x) cnt[i] = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < feat_words; i += (int64_t)gridDim.x * blockDim.x) feats[i] = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < acc_words; i += (int64_t)gridDim.x * blockDim.x) acc[i] = 0u;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float p[4];
     if (stride == 4) {
@@ -54,6 +68,7 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_accum(const float* __restri
                                                            int nfeat, VoxGeom g, SvIndexView ix,
                                                            const int64_t* __restrict__ keys, int64_t capacity,
                                                            int32_t* __restrict__ coords, float* __restrict__ feats,
+                                                           unsigned long long* __restrict__ acc,
                                                            int32_t* __restrict__ cnt, int32_t* __restrict__ p2v) {
   const int nf = C > 0 ? C : nfeat;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -63,10 +78,23 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_accum(const float* __restri
       row = sv_index_rank_slow(ix, key, nullptr);
       if (row < capacity) {
         const float* r = points + i * stride + 1;
+        const int32_t arrival = atomicAdd(cnt + row, 1);           // this point's place among its voxel's points
         float* dst = feats + (int64_t)row * nf;
+        if (acc) {
+          unsigned long long* fix = acc + (int64_t)row * nf;
 #pragma unroll
-        for (int c = 0; c < nf; ++c) atomicAdd(dst + c, r[c]);
-        if (atomicAdd(cnt + row, 1) == 0) {
+          for (int c = 0; c < nf; ++c) {
+            const float v = r[c];
+            if (arrival < VOX_FIXED_MAX_POINTS && fabsf(v) < VOX_FIXED_MAX_ABS)   // false for NaN
+              atomicAdd(fix + c, (unsigned long long)__float2ll_rn(v * VOX_FIXED_SCALE));
+            else
+              atomicAdd(dst + c, v);
+          }
+        } else {
+#pragma unroll
+          for (int c = 0; c < nf; ++c) atomicAdd(dst + c, r[c]);
+        }
+        if (arrival == 0) {
           // decode (dynamic_mean_vfe.py:67-71) and reorder to [b, z, y, x]
           const int z = (int)(key % g.grid[2]);
           const int64_t t = key / g.grid[2];
@@ -87,6 +115,7 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_accum(const float* __restri
 __global__ __launch_bounds__(VOX_THREADS) void k_vox_finalize(int64_t n, SvIndexView ix,
                                                               const int64_t* __restrict__ keys, int nfeat,
                                                               int64_t capacity, float* __restrict__ feats,
+                                                              const unsigned long long* __restrict__ acc,
                                                               const int32_t* __restrict__ cnt,
                                                               int32_t* __restrict__ num_voxels) {
   int64_t nv = *num_voxels;
@@ -96,7 +125,13 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_finalize(int64_t n, SvIndex
     if (i < nv) {
       const float c = (float)cnt[i];  // >= 1 by construction
       float* dst = feats + i * nfeat;
-      for (int k = 0; k < nfeat; ++k) dst[k] = __fdiv_rn(dst[k], c);
+      if (acc) {
+        const unsigned long long* src = acc + i * nfeat;
+        for (int k = 0; k < nfeat; ++k)
+          dst[k] = __double2float_rn(((double)(long long)src[k] * (1.0 / 4294967296.0) + (double)dst[k]) / (double)c);
+      } else {
+        for (int k = 0; k < nfeat; ++k) dst[k] = __fdiv_rn(dst[k], c);
+      }
     }
     if (i < n) {
       const int64_t key = keys[i];
@@ -113,7 +148,8 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_finalize(int64_t n, SvIndex
 static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 extern "C" size_t sv_voxelize_dynamic_scratch_bytes(int64_t num_points, int64_t ncells, int64_t capacity) {
-  return align256((size_t)num_points * 8) + align256((size_t)capacity * 4) + align256(sv_index_scan_tmp_bytes(ncells));
+  return align256((size_t)num_points * 8) + align256((size_t)capacity * 4) + align256((size_t)capacity * VOX_FIXED_MAX_FEATURES * 8) +
+         align256(sv_index_scan_tmp_bytes(ncells));
 }
 
 extern "C" int sv_voxelize_dynamic(const float* points, int64_t num_points, int point_stride, int num_features,
@@ -144,12 +180,15 @@ extern "C" int sv_voxelize_dynamic(const float* points, int64_t num_points, int 
   s += align256((size_t)num_points * 8);
   int32_t* cnt = reinterpret_cast<int32_t*>(s);
   s += align256((size_t)capacity * 4);
+  unsigned long long* acc = num_features <= VOX_FIXED_MAX_FEATURES ? reinterpret_cast<unsigned long long*>(s) : nullptr;
+  s += align256((size_t)capacity * VOX_FIXED_MAX_FEATURES * 8);
   void* scan_tmp = s;
+  const int64_t acc_words = acc ? capacity * num_features * 2 : 0;
 
   const int grid = sv_grid_1d(num_points, VOX_THREADS);
   if (num_points > 0) {
     hipLaunchKernelGGL(k_vox_mark, dim3(grid), dim3(VOX_THREADS), 0, st, points, num_points, point_stride, g, ix, keys, cnt, capacity, voxel_features,
-                       capacity * num_features);
+                       capacity * num_features, reinterpret_cast<uint32_t*>(acc), acc_words);
   } else {
     SV_HIP(hipMemsetAsync(cnt, 0, (size_t)capacity * 4, st));
     SV_HIP(hipMemsetAsync(voxel_features, 0, (size_t)capacity * num_features * 4, st));
@@ -159,17 +198,17 @@ extern "C" int sv_voxelize_dynamic(const float* points, int64_t num_points, int 
   if (num_points > 0) {
     if (num_features == 3)
       hipLaunchKernelGGL(k_vox_accum<3>, dim3(grid), dim3(VOX_THREADS), 0, st, points, num_points, point_stride,
-                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, cnt, point_to_voxel);
+                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, acc, cnt, point_to_voxel);
     else if (num_features == 4)
       hipLaunchKernelGGL(k_vox_accum<4>, dim3(grid), dim3(VOX_THREADS), 0, st, points, num_points, point_stride,
-                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, cnt, point_to_voxel);
+                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, acc, cnt, point_to_voxel);
     else
       hipLaunchKernelGGL(k_vox_accum<0>, dim3(grid), dim3(VOX_THREADS), 0, st, points, num_points, point_stride,
-                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, cnt, point_to_voxel);
+                         num_features, g, ix, keys, capacity, voxel_coords, voxel_features, acc, cnt, point_to_voxel);
   }
   const int64_t work = num_points > capacity ? num_points : capacity;
   hipLaunchKernelGGL(k_vox_finalize, dim3(sv_grid_1d(work, VOX_THREADS)), dim3(VOX_THREADS), 0, st, num_points, ix,
-                     keys, num_features, capacity, voxel_features, cnt, num_voxels);
+                     keys, num_features, capacity, voxel_features, acc, cnt, num_voxels);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

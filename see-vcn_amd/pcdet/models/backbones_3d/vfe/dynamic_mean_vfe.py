@@ -9,7 +9,7 @@ class DynamicMeanVFE(VFETemplate):
 
     Same constructor keywords and batch_dict keys; the torch.unique + torch_scatter pipeline is replaced by
     sv_voxelize_dynamic (bitmap rank index in HBM, no sort).  voxel_coords come out bit-identical and in
-    the same (ascending key) order; voxel_features are sum/count in fp32.
+    the same (ascending key) order; voxel_features are sum/count (order-independent fixed-point sums up to 4 features, include/seevcn_hip.h).
     """
 
     def __init__(self, model_cfg, num_point_features, voxel_size, grid_size, point_cloud_range, **kwargs):

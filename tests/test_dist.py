@@ -123,7 +123,7 @@ def test_bench_rank_under_an_external_launcher_world2_gloo():
 def test_bench_main_two_ranks_end_to_end_on_one_gpu():
     """bench.py's whole N = 2 path (launcher, per-rank inputs, steps with the exchange, timing protocol, rank-0-only kernel timing,
     barrier, teardown) with both ranks on cuda:0 over gloo.  Round 1's main() hung here: rank 0 entered a collective alone."""
-    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--scenes-per-gpu", "2", "--objects-per-gpu", "8", "--no-cpu-baseline"],
+    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--scenes-per-gpu", "2", "--objects-per-gpu", "8", "--full", "--no-cpu-baseline"],
                      {"SEEVCN_BENCH_SHARE_GPU": "1", "SEEVCN_BENCH_BACKEND": "gloo"}, timeout=900)
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["roofline"]["achieved"] > 0
     assert out["config"]["scenes_per_gpu"] == 2

@@ -111,7 +111,43 @@ def test_hip_full_size_properties(cuda, hip_lib):
     perm = np.random.default_rng(1).permutation(len(pts))
     f2, c2, _ = _run_hip(pts[perm], pc_range, vs, grid, 16, cuda)
     assert np.array_equal(c2.cpu().numpy(), c)
-    np.testing.assert_allclose(f2.cpu().numpy(), f, rtol=1e-5, atol=1e-5)
+    np.testing.assert_array_equal(f2.cpu().numpy(), f)        # fixed-point sums: the same bits whatever order the points come in
+
+
+@pytest.mark.gpu
+def test_hip_feature_sums_order_independent_and_exact(cuda, hip_lib):
+    """Up to 4 features the per-voxel sums are fixed point: every permutation of the points gives the same bits; in-range means are the
+    fp64 mean rounded to fp32 (within one ulp, 2^-32 absolute for tiny values); negative, tiny and large (|v| < 2^15) values; a value of
+    2^15 or more and a NaN take the fp32 side sum (the NaN propagates to its voxel's mean only)."""
+    rng_, vs, grid = [0, 0, 0, 1, 1, 1], [0.5, 0.5, 0.5], [2, 2, 2]
+    r = np.random.default_rng(3)
+    n = 4000
+    xyz = r.uniform(0.0, 0.999, (n, 3)).astype(np.float32)
+    extra = (r.normal(size=n) * 3000).astype(np.float32)                       # negative and large, inside +-2^15
+    extra[::7] = (r.normal(size=len(extra[::7])) * 1e-7).astype(np.float32)      # tiny: below 2^-9
+    pts = np.concatenate([np.zeros((n, 1), np.float32), xyz, extra[:, None]], axis=1)
+    special = np.array([[0, 0.1, 0.1, 0.1, 1.0e6],                               # >= 2^15: fp32 side sum
+                        [0, 0.9, 0.9, 0.9, np.nan]], np.float32)                  # NaN: propagates
+    pts = np.concatenate([pts, special])
+    f, c, _ = _run_hip(pts, rng_, vs, grid, 1, cuda)
+    f, c = f.cpu().numpy(), c.cpu().numpy()
+    for seed in range(3):
+        perm = np.random.default_rng(10 + seed).permutation(len(pts))
+        f2, c2, _ = _run_hip(pts[perm], rng_, vs, grid, 1, cuda)
+        assert np.array_equal(c2.cpu().numpy(), c)
+        np.testing.assert_array_equal(f2.cpu().numpy(), f)
+    idx = np.floor(pts[:, 1:4] / 0.5).astype(np.int64)
+    key = (idx[:, 0] * 2 + idx[:, 1]) * 2 + idx[:, 2]
+    ckey = (c[:, 3].astype(np.int64) * 2 + c[:, 2]) * 2 + c[:, 1]
+    nan_key = key[-1]
+    for row, k in enumerate(ckey):
+        want = pts[key == k, 1:].astype(np.float64).mean(0)
+        got = f[row]
+        if k == nan_key:
+            assert np.isnan(got[3]) and np.isfinite(got[:3]).all()
+            want, got = want[:3], got[:3]
+        ref = want.astype(np.float32)
+        assert (np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(ref)).astype(np.float64) + 2.0 ** -32).all(), (row, got, want)
 
 
 @pytest.mark.gpu

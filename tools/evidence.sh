@@ -1,11 +1,14 @@
 #!/bin/bash
-# usage (on the GPU box, from the repo root): tools/evidence.sh <tag>      e.g. r02_a
-# One call that leaves everything profiles/ holds for a round under gpurun_out/: the default bench line, the rocprofv3 kernel stats of the
+# usage (on the GPU box, from the repo root): OUT=<folder> tools/evidence.sh <tag>      e.g. r02_a
+# One call that leaves everything profiles/ holds for a round: the `bench.py --full` line (in $OUT), and in the fixed results folder the
+# gate log and the tools called below write to, the rocprofv3 kernel stats of the
 # same command (whole process + steady steps), the PMC traffic passes, the side-mode bench lines with their steady kernel tables, and the
 # micro-benchmarks (per-layer sparse conv, FPS), the host-time split, the blocking-read traces and the launch sites of the PV-RCNN step.
 # FIRST the gate: the driver's own command (`pytest -m gpu -x -q`) at this tree, log kept as gpurun_out/<round>_gputest.log (copy it to profiles/);
 # a red gate stops the call -- numbers of a tree whose parity is not green are not evidence.  GATE=0 skips it (A/B reruns on a box that already ran it).
 TAG=$1
+# OUT: the folder the --full bench line goes to (the gate log and the tools called below keep their own fixed results folder)
+OUT=${OUT:?set OUT to the folder that collects the results}
 cd $GRAFT_REPO_ROOT
 if [ "${GATE:-1}" != "0" ]; then
   timeout 1500 python3 -m pytest tests -x -q -m gpu -p no:cacheprovider > gpurun_out/${TAG%%_*}_gputest.log 2>&1
@@ -16,8 +19,8 @@ if [ "${GATE:-1}" != "0" ]; then
   # them and reads 3x slow for its whole timed loop (seen twice in round 5: 11.4 and 12.6 ms/step with every kernel at its normal duration)
   sleep 30
 fi
-timeout 900 python3 bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-tail -c 600 gpurun_out/${TAG}_bench.json
+timeout 900 python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+tail -c 600 "$OUT/${TAG}_bench.json"
 TOP=8 tools/profile.sh ${TAG}_main 20 2>&1 | head -10
 tools/roofline_pass.sh ${TAG} 2>&1 | tail -8
 tools/traffic.sh ${TAG} 2>&1 | tail -6
