@@ -592,6 +592,15 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
  *   SV_OP_BN_FINALIZE   sv_batchnorm_finalize_forward: p = gamma, beta, running_mean, running_var, scratch, coef, save_mean, save_invstd,
  *                       num_batches_tracked, x (0: partials in scratch); n = rows; i = channels, n_partials; f = momentum, eps
  *   SV_OP_BN_APPLY      sv_batchnorm_apply: p = x, coef, y; n = rows; i = channels, relu
+ *   SV_OP_BN_STATS_LOCAL       sv_batchnorm_stats_local: p = x (0: partials in scratch), scratch, sums; n = rows; i = channels, n_partials
+ *   SV_OP_BN_FINALIZE_GLOBAL   sv_batchnorm_finalize_global: p = gathered, gamma, beta, running_mean, running_var, coef, save_mean, save_invstd,
+ *                       num_batches_tracked, total_rows; i = channels, world; f = momentum, eps
+ *   SV_OP_BN_BWD_SUMS_LOCAL    sv_batchnorm_backward_sums_local: p = x, dy, gamma, beta, save_mean, save_invstd, scratch, dgamma, dbeta, sums; n = rows;
+ *                       i = channels, relu, n_partials (0: the reduce pass over x, dy runs first)
+ *   SV_OP_BN_BWD_APPLY_GLOBAL  sv_batchnorm_backward_apply_global: p = x, dy, gamma, beta, save_mean, save_invstd, scratch, gathered, total_rows, dx;
+ *                       n = rows; i = channels, relu, world
+ *                       (SyncBatchNorm: a list is CUT behind a *_LOCAL operation, the caller all-gathers `sums` between the ranks, and the next list
+ *                       starts with the matching *_GLOBAL operation)
  * Input transform: SV_OP_CONV_PLANNED with p12 = coef (2, Kd) and i6 = relu, SV_OP_WGRAD[_DEFERRED] with p6 = coef (2, Cin) and i4 = relu read their
  * X through sv_conv_next_input_norm(coef, relu): X is then the RAW output of the convolution below, its BatchNorm (+ReLU) is applied as the rows are
  * gathered, and the normalised activation tensor is never written.
@@ -607,6 +616,10 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
 #define SV_OP_WGRAD_DEFERRED 8
 #define SV_OP_BN_FINALIZE 9
 #define SV_OP_BN_APPLY 10
+#define SV_OP_BN_STATS_LOCAL 11
+#define SV_OP_BN_FINALIZE_GLOBAL 12
+#define SV_OP_BN_BWD_SUMS_LOCAL 13
+#define SV_OP_BN_BWD_APPLY_GLOBAL 14
 int sv_run_ops(const int64_t* ops, int n_ops, void* stream);
 /* measurement form: events around every operation on `stream`, the call waits for the stream and writes each operation's elapsed milliseconds to
  * ms[0 .. n_ops) (bench.py's roofline block times the conv launches of the step's own launch lists with it) */
@@ -649,6 +662,26 @@ int sv_batchnorm_relu_backward(const float* x, const float* dy, int64_t n, int c
 int sv_batchnorm_relu_backward_partial(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,
                                        const float* save_mean, const float* save_invstd, int relu, void* scratch, int n_partials, float* dx,
                                        float* dgamma, float* dbeta, void* stream);
+/* ---- SyncBatchNorm (torch.nn.SyncBatchNorm in training mode over more than one rank): the two combines above cut in two around the exchange of the
+ * per-channel sums between the ranks.  Every rank makes its own sums in fp64 (*_local), the caller all-gathers them (rank-major), and every rank adds
+ * the gathered buffers in rank order in fp64 (*_global): the same bits on every rank, whatever the transport.  Row counts may differ per rank.
+ * With world = 1 the pairs reproduce sv_batchnorm_finalize_forward and sv_batchnorm_relu_backward_partial bit for bit.
+ * sums (2 * channels + 1 doubles) = sum x | sum x^2 | n, from n_partials workgroup partials in scratch (x NULL) or after the statistics pass over x */
+int sv_batchnorm_stats_local(const float* x, int64_t n, int channels, void* scratch, int n_partials, double* sums, void* stream);
+/* gathered (world, 2 * channels + 1) -> save_mean, save_invstd, running statistics (unbiased variance with the TOTAL row count), coef (2, channels) =
+ * scale | shift, num_batches_tracked += 1, *total_rows (device double, may be null) = the row count of all ranks, kept for the backward */
+int sv_batchnorm_finalize_global(const double* gathered, int world, int channels, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, float momentum, float eps, float* coef, float* save_mean, float* save_invstd,
+                                 int64_t* num_batches_tracked, double* total_rows, void* stream);
+/* dgamma, dbeta (LOCAL sums) and sums (2 * channels doubles) = sum dy | sum dy * xhat (dy behind the ReLU mask), from n_partials workgroup partials in
+ * scratch (the epilogue of sv_sparse_conv_dgrad_planned_bn) or, n_partials = 0, after the reduce pass over x, dy */
+int sv_batchnorm_backward_sums_local(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,
+                                     const float* save_mean, const float* save_invstd, int relu, void* scratch, int n_partials, float* dgamma,
+                                     float* dbeta, double* sums, void* stream);
+/* gathered (world, 2 * channels) and *total_rows -> dx (n, channels) = gamma * invstd * (dy - sum dy / N - xhat * sum(dy * xhat) / N), N the total count */
+int sv_batchnorm_backward_apply_global(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,
+                                       const float* save_mean, const float* save_invstd, int relu, const double* gathered, int world,
+                                       const double* total_rows, void* scratch, float* dx, void* stream);
 
 /* Ragged-group variant of sv_gemm_bias_act: row_group[M] (non-decreasing int32) names the group of every row; used after
  * sv_unique_rows, when each object keeps only its distinct points (ResamplePoints, vcn/datasets/data_transforms.py:254-262,

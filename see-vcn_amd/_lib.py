@@ -181,6 +181,10 @@ SIGNATURES = {
     "sv_conv_next_input_norm": (c_i, [c_p, c_i]),
     "sv_batchnorm_finalize_forward": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_batchnorm_apply": (c_i, [c_p, c_i64, c_i, c_p, c_i, c_p, c_p]),
+    "sv_batchnorm_stats_local": (c_i, [c_p, c_i64, c_i, c_p, c_i, c_p, c_p]),
+    "sv_batchnorm_finalize_global": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_batchnorm_backward_sums_local": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
+    "sv_batchnorm_backward_apply_global": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
     "sv_run_ops": (c_i, [c_p, c_i, c_p]),
     "sv_run_ops_timed": (c_i, [c_p, c_i, c_p, c_p]),
     "sv_run_ops_two_streams": (c_i, [c_p, c_i, c_p, c_p]),

@@ -69,12 +69,12 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_reduce(BnArgs a) {
 // round 5: ONE wave per channel, its <= 16 partial pairs per lane requested up front and the lane sums met by shuffles instead of the eight-barrier LDS
 // tree -- the step went 3.64 -> 3.78 ms (profiles/r05_fin_ab.txt): 32 load instructions of 64 different lines each through one wave's address unit take
 // longer than the four waves' shorter queues.  Measured with SEEVCN_DEBUG_SKIP_FINALIZE: the 12 forward launches cost the step 0.08 ms in all.)
-template <bool BWD>
-__global__ __launch_bounds__(BN_THREADS) void k_bn_finalize(BnArgs a) {
-  __shared__ double s0[BN_THREADS], s1[BN_THREADS];
-  const int c = blockIdx.x, tid = threadIdx.x;
-  if (!BWD && c == 0 && tid == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
-  double t0 = 0.0, t1 = 0.0;
+// the pieces of k_bn_finalize, shared with the SyncBatchNorm kernels below (which cut the combine in two around the exchange between ranks): the same
+// statements in the same order, so a world of one reproduces k_bn_finalize bit for bit (the library is built with -ffp-contract=off)
+// sums of channel c over the a.wgs workgroup partials; every thread of the workgroup calls it, thread 0 gets the result
+__device__ __forceinline__ void bn_combine(const BnArgs& a, int c, double* s0, double* s1, double& t0, double& t1) {
+  const int tid = threadIdx.x;
+  t0 = 0.0, t1 = 0.0;
   for (int w = tid; w < a.wgs; w += BN_THREADS) {
     t0 += (double)a.partial[(size_t)w * 2 * a.C + c];
     t1 += (double)a.partial[(size_t)w * 2 * a.C + a.C + c];
@@ -85,32 +85,89 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_finalize(BnArgs a) {
     if (tid < off) s0[tid] += s0[tid + off], s1[tid] += s1[tid + off];
     __syncthreads();
   }
-  if (tid != 0) return;
   t0 = s0[0], t1 = s1[0];
+}
+// forward: batch statistics, running statistics and coef = scale | shift of channel c from sum x (t0) and sum x^2 (t1) over n rows
+__device__ __forceinline__ void bn_finish_fwd(const BnArgs& a, int c, double t0, double t1, double n) {
   const float gm = a.gamma ? a.gamma[c] : 1.f, bb = a.beta ? a.beta[c] : 0.f;
-  if (!BWD) {
-    const double m = t0 / (double)a.n;
-    double var = t1 / (double)a.n - m * m;             // biased variance of the batch
-    var = var < 0.0 ? 0.0 : var;
-    const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
-    a.save_mean[c] = (float)m, a.save_invstd[c] = invstd;
-    if (a.running_mean) {
-      const double unbiased = a.n > 1 ? var * (double)a.n / (double)(a.n - 1) : var;
-      a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * (float)m;
-      a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * (float)unbiased;
-    }
-    const float scale = invstd * gm;                    // y = x * scale + shift
-    a.coef[c] = scale;
-    a.coef[a.C + c] = bn_shift((float)m, scale, bb);
-  } else {
-    const float invstd = a.save_invstd[c], m = a.save_mean[c];
-    a.dbeta[c] = (float)t0, a.dgamma[c] = (float)t1;
-    // dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat)),  xhat = (x - m) * invstd
-    a.coef[c] = gm * invstd;
-    a.coef[a.C + c] = (float)(t0 / (double)a.n);
-    a.coef[2 * a.C + c] = (float)(t1 / (double)a.n);
-    a.coef[3 * a.C + c] = m;
+  const double m = t0 / n;
+  double var = t1 / n - m * m;             // biased variance of the batch
+  var = var < 0.0 ? 0.0 : var;
+  const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
+  a.save_mean[c] = (float)m, a.save_invstd[c] = invstd;
+  if (a.running_mean) {
+    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+    a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * (float)m;
+    a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * (float)unbiased;
   }
+  const float scale = invstd * gm;                    // y = x * scale + shift
+  a.coef[c] = scale;
+  a.coef[a.C + c] = bn_shift((float)m, scale, bb);
+}
+// backward: the (4, C) coefficient block of k_bn_apply_bwd from sum dy (t0) and sum dy * xhat (t1) over n rows
+__device__ __forceinline__ void bn_coef_bwd(const BnArgs& a, int c, double t0, double t1, double n) {
+  const float gm = a.gamma ? a.gamma[c] : 1.f;
+  const float invstd = a.save_invstd[c], m = a.save_mean[c];
+  // dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat)),  xhat = (x - m) * invstd
+  a.coef[c] = gm * invstd;
+  a.coef[a.C + c] = (float)(t0 / n);
+  a.coef[2 * a.C + c] = (float)(t1 / n);
+  a.coef[3 * a.C + c] = m;
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_finalize(BnArgs a) {
+  __shared__ double s0[BN_THREADS], s1[BN_THREADS];
+  const int c = blockIdx.x;
+  if (!BWD && c == 0 && threadIdx.x == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
+  double t0, t1;
+  bn_combine(a, c, s0, s1, t0, t1);
+  if (threadIdx.x != 0) return;
+  if (!BWD) {
+    bn_finish_fwd(a, c, t0, t1, (double)a.n);
+  } else {
+    a.dbeta[c] = (float)t0, a.dgamma[c] = (float)t1;
+    bn_coef_bwd(a, c, t0, t1, (double)a.n);
+  }
+}
+
+// ---- SyncBatchNorm: the combine cut in two around the exchange between ranks.  A rank's sums leave the device as fp64 (sums | sums of squares | row
+// count, or sum dy | sum dy * xhat); the ranks all-gather them and every rank adds the gathered buffers IN RANK ORDER in fp64 -- no atomics, no
+// reduction order left to a backend -- so every rank computes the same bits (running statistics included) from the same buffer.
+// local half: k_bn_finalize's combine, the sums written out instead of used.  BWD: dgamma / dbeta are the LOCAL sums (the data-parallel wrapper averages
+// them like any parameter gradient)
+template <bool BWD>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_sums_local(BnArgs a, double* out) {
+  __shared__ double s0[BN_THREADS], s1[BN_THREADS];
+  const int c = blockIdx.x;
+  double t0, t1;
+  bn_combine(a, c, s0, s1, t0, t1);
+  if (threadIdx.x != 0) return;
+  out[c] = t0, out[a.C + c] = t1;
+  if (!BWD && c == 0) out[2 * a.C] = (double)a.n;
+  if (BWD) a.dbeta[c] = (float)t0, a.dgamma[c] = (float)t1;
+}
+// global half, forward: gathered (world, 2 C + 1), one thread per channel; the total row count goes to *total_rows for the backward
+__global__ void k_bn_finalize_global(BnArgs a, const double* gathered, int world, double* total_rows) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= a.C) return;
+  const size_t stride = 2 * (size_t)a.C + 1;
+  double t0 = gathered[c], t1 = gathered[a.C + c], n = gathered[2 * a.C];
+  for (int r = 1; r < world; ++r) t0 += gathered[r * stride + c], t1 += gathered[r * stride + a.C + c], n += gathered[r * stride + 2 * a.C];
+  if (c == 0) {
+    if (a.num_batches_tracked) *a.num_batches_tracked += 1;
+    if (total_rows) *total_rows = n;
+  }
+  bn_finish_fwd(a, c, t0, t1, n);
+}
+// global half, backward: gathered (world, 2 C) -> the coefficient block of k_bn_apply_bwd with the sums and the row count of all ranks
+__global__ void k_bn_coef_bwd_global(BnArgs a, const double* gathered, int world, const double* total_rows) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= a.C) return;
+  const size_t stride = 2 * (size_t)a.C;
+  double t0 = gathered[c], t1 = gathered[a.C + c];
+  for (int r = 1; r < world; ++r) t0 += gathered[r * stride + c], t1 += gathered[r * stride + a.C + c];
+  bn_coef_bwd(a, c, t0, t1, *total_rows);
 }
 
 __global__ __launch_bounds__(BN_THREADS) void k_bn_apply_fwd(BnArgs a) {
@@ -381,6 +438,85 @@ extern "C" int sv_batchnorm_relu_backward_partial(const float* x, const float* d
   bn_scratch(a, scratch);
   hipStream_t st = sv_stream(stream);
   bn_backward_tail(a, st);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// ---- SyncBatchNorm entry points (the kernels are next to k_bn_finalize).  `sums` / `gathered` / `total_rows` are fp64 device buffers of the caller.
+// A rank's own sums: from n_partials workgroup partials in `scratch` (x == NULL), or after the statistics pass over x (n, C).  sums[2 C + 1] = sum x | sum x^2 | n.
+extern "C" int sv_batchnorm_stats_local(const float* x, int64_t n, int channels, void* scratch, int n_partials, double* sums, void* stream) {
+  if (int rc = bn_common_check("sv_batchnorm_stats_local", n, channels)) return rc;
+  SV_CHECK_ARG(scratch && sums && (uintptr_t)sums % 8 == 0, "sv_batchnorm_stats_local: null or misaligned pointer");
+  SV_CHECK_ARG(x || (n_partials >= 1 && n_partials <= BN_MAX_WGS), "sv_batchnorm_stats_local: x, or 1..%d partials (got %d)", BN_MAX_WGS, n_partials);
+  BnArgs a{};
+  a.x = x, a.n = n, a.C = channels;
+  a.wgs = x ? bn_wgs(n, channels) : n_partials;
+  bn_scratch(a, scratch);
+  hipStream_t st = sv_stream(stream);
+  if (x) hipLaunchKernelGGL(k_bn_reduce<false>, dim3(a.wgs), dim3(BN_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_bn_sums_local<false>, dim3(channels), dim3(BN_THREADS), 0, st, a, sums);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// gathered (world, 2 C + 1), rank-major -> what sv_batchnorm_finalize_forward leaves (save_mean, save_invstd, running statistics with the TOTAL count,
+// coef = scale | shift, num_batches_tracked += 1) and *total_rows (may be null) = the row count of all ranks
+extern "C" int sv_batchnorm_finalize_global(const double* gathered, int world, int channels, const float* gamma, const float* beta, float* running_mean,
+                                            float* running_var, float momentum, float eps, float* coef, float* save_mean, float* save_invstd,
+                                            int64_t* num_batches_tracked, double* total_rows, void* stream) {
+  if (int rc = bn_common_check("sv_batchnorm_finalize_global", 1, channels)) return rc;
+  SV_CHECK_ARG(world >= 1, "sv_batchnorm_finalize_global: world size %d", world);
+  SV_CHECK_ARG(gathered && coef && save_mean && save_invstd && (uintptr_t)gathered % 8 == 0 && (uintptr_t)total_rows % 8 == 0,
+               "sv_batchnorm_finalize_global: null or misaligned pointer");
+  BnArgs a{};
+  a.gamma = gamma, a.beta = beta, a.running_mean = running_mean, a.running_var = running_var;
+  a.save_mean = save_mean, a.save_invstd = save_invstd, a.C = channels, a.momentum = momentum, a.eps = eps;
+  a.num_batches_tracked = num_batches_tracked;
+  a.coef = coef;
+  hipLaunchKernelGGL(k_bn_finalize_global, dim3(sv_div_up(channels, 64)), dim3(64), 0, sv_stream(stream), a, gathered, world, total_rows);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// A rank's own backward sums: from n_partials workgroup partials in `scratch` (left by sv_sparse_conv_dgrad_planned_bn), or with n_partials == 0 after the
+// reduce pass over x, dy.  Writes dgamma, dbeta (local sums) and sums[2 C] = sum dy | sum dy * xhat (dy behind the ReLU mask).
+extern "C" int sv_batchnorm_backward_sums_local(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,
+                                                const float* save_mean, const float* save_invstd, int relu, void* scratch, int n_partials, float* dgamma,
+                                                float* dbeta, double* sums, void* stream) {
+  if (int rc = bn_common_check("sv_batchnorm_backward_sums_local", n, channels)) return rc;
+  SV_CHECK_ARG(dgamma && dbeta && scratch && sums && (uintptr_t)sums % 8 == 0, "sv_batchnorm_backward_sums_local: null or misaligned pointer");
+  SV_CHECK_ARG(n_partials >= 0 && n_partials <= BN_MAX_WGS, "sv_batchnorm_backward_sums_local: 0..%d partials (got %d)", BN_MAX_WGS, n_partials);
+  SV_CHECK_ARG(n_partials > 0 || (x && dy && save_mean && save_invstd), "sv_batchnorm_backward_sums_local: the reduce pass needs x, dy, save_mean, save_invstd");
+  BnArgs a{};
+  a.x = x, a.dy = dy, a.gamma = gamma, a.beta = beta, a.dgamma = dgamma, a.dbeta = dbeta;
+  a.save_mean = const_cast<float*>(save_mean), a.save_invstd = const_cast<float*>(save_invstd);
+  a.n = n, a.C = channels, a.relu = relu;
+  a.wgs = n_partials ? n_partials : bn_wgs(n, channels);
+  bn_scratch(a, scratch);
+  hipStream_t st = sv_stream(stream);
+  if (!n_partials) hipLaunchKernelGGL(k_bn_reduce<true>, dim3(a.wgs), dim3(BN_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_bn_sums_local<true>, dim3(channels), dim3(BN_THREADS), 0, st, a, sums);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// gathered (world, 2 C), rank-major, and *total_rows (sv_batchnorm_finalize_global's) -> dx of this rank's n rows: the coefficients with the sums and the
+// count of all ranks, then the elementwise pass of sv_batchnorm_relu_backward
+extern "C" int sv_batchnorm_backward_apply_global(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,
+                                                  const float* save_mean, const float* save_invstd, int relu, const double* gathered, int world,
+                                                  const double* total_rows, void* scratch, float* dx, void* stream) {
+  if (int rc = bn_common_check("sv_batchnorm_backward_apply_global", n, channels)) return rc;
+  SV_CHECK_ARG(world >= 1, "sv_batchnorm_backward_apply_global: world size %d", world);
+  SV_CHECK_ARG(x && dy && dx && save_mean && save_invstd && scratch && gathered && total_rows && (uintptr_t)gathered % 8 == 0 && (uintptr_t)total_rows % 8 == 0,
+               "sv_batchnorm_backward_apply_global: null or misaligned pointer");
+  BnArgs a{};
+  a.x = x, a.dy = dy, a.out = dx, a.gamma = gamma, a.beta = beta;
+  a.save_mean = const_cast<float*>(save_mean), a.save_invstd = const_cast<float*>(save_invstd);
+  a.n = n, a.C = channels, a.relu = relu;
+  bn_scratch(a, scratch);
+  hipStream_t st = sv_stream(stream);
+  hipLaunchKernelGGL(k_bn_coef_bwd_global, dim3(sv_div_up(channels, 64)), dim3(64), 0, st, a, gathered, world, total_rows);
+  hipLaunchKernelGGL(k_bn_apply_bwd, dim3(sv_grid_1d(n * (channels / 4), BN_THREADS)), dim3(BN_THREADS), 0, st, a);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

@@ -153,6 +153,24 @@ static int run_ops(const int64_t* ops, int n_ops, void* stream, void* side_strea
       case SV_OP_BN_APPLY:
         rc = sv_batchnorm_apply(ptr_of<const float>(p[0]), n[0], (int)i[0], ptr_of<const float>(p[1]), (int)i[1], ptr_of<float>(p[2]), stream);
         break;
+      case SV_OP_BN_STATS_LOCAL:
+        rc = sv_batchnorm_stats_local(ptr_of<const float>(p[0]), n[0], (int)i[0], ptr_of<void>(p[1]), (int)i[1], ptr_of<double>(p[2]), stream);
+        break;
+      case SV_OP_BN_FINALIZE_GLOBAL:
+        rc = sv_batchnorm_finalize_global(ptr_of<const double>(p[0]), (int)i[1], (int)i[0], ptr_of<const float>(p[1]), ptr_of<const float>(p[2]), ptr_of<float>(p[3]),
+                                          ptr_of<float>(p[4]), (float)as_double(f[0]), (float)as_double(f[1]), ptr_of<float>(p[5]), ptr_of<float>(p[6]),
+                                          ptr_of<float>(p[7]), ptr_of<int64_t>(p[8]), ptr_of<double>(p[9]), stream);
+        break;
+      case SV_OP_BN_BWD_SUMS_LOCAL:
+        rc = sv_batchnorm_backward_sums_local(ptr_of<const float>(p[0]), ptr_of<const float>(p[1]), n[0], (int)i[0], ptr_of<const float>(p[2]),
+                                              ptr_of<const float>(p[3]), ptr_of<const float>(p[4]), ptr_of<const float>(p[5]), (int)i[1], ptr_of<void>(p[6]),
+                                              (int)i[2], ptr_of<float>(p[7]), ptr_of<float>(p[8]), ptr_of<double>(p[9]), stream);
+        break;
+      case SV_OP_BN_BWD_APPLY_GLOBAL:
+        rc = sv_batchnorm_backward_apply_global(ptr_of<const float>(p[0]), ptr_of<const float>(p[1]), n[0], (int)i[0], ptr_of<const float>(p[2]),
+                                                ptr_of<const float>(p[3]), ptr_of<const float>(p[4]), ptr_of<const float>(p[5]), (int)i[1],
+                                                ptr_of<const double>(p[7]), (int)i[2], ptr_of<const double>(p[8]), ptr_of<void>(p[6]), ptr_of<float>(p[9]), stream);
+        break;
       case SV_OP_WGRAD:
         if (st_side && (rc = fork_side()) != SV_OK) break;
         if (p[6]) sv_conv_next_input_norm(ptr_of<const float>(p[6]), (int)i[4]);

@@ -168,7 +168,7 @@ def run_sequential(layers, x):
             fuse_relu = isinstance(nxt, nn.ReLU)
             x = linear(x, w, m.bias, ACT_RELU if fuse_relu else ACT_NONE)
             i += 2 if fuse_relu else 1
-        elif isinstance(m, nn.BatchNorm1d) and norm.fusable(m, x):
+        elif norm.fusable(m, x):                                      # nn.BatchNorm1d, or a SyncBatchNorm that replaced one (spconv.norm.route)
             relu = isinstance(nxt, nn.ReLU)
             x = norm.batch_norm_relu(m, x, relu)
             i += 2 if relu else 1

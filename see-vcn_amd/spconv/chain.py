@@ -42,6 +42,7 @@ _wgrad_stream = {}
 # made when somebody reads them (LazyTap), the last block's in the list.  0: every block writes its normalised output (A/B runs, tests).
 BN_FOLD = os.environ.get("SEEVCN_BN_FOLD", "1") != "0"
 OP_CONV_PLANNED, OP_CONV_PLAIN, OP_BN_FWD, OP_BN_BWD, OP_WGRAD, OP_DGRAD_PLANNED_BN, OP_WGRAD_DEFERRED, OP_BN_FINALIZE, OP_BN_APPLY = 1, 2, 3, 5, 6, 7, 8, 9, 10
+OP_BN_STATS_LOCAL, OP_BN_FINALIZE_GLOBAL, OP_BN_BWD_SUMS_LOCAL, OP_BN_BWD_APPLY_GLOBAL = 11, 12, 13, 14
 WORDS = 32
 
 
@@ -75,6 +76,27 @@ def _run_two_streams(rows, dev):
     _lib.check(_lib.load().sv_run_ops_two_streams(arr.ctypes.data, len(rows), _lib.stream(), side.cuda_stream), "sv_run_ops_two_streams (chain backward)")
 
 
+class Cut:
+    """A place where a launch list is cut: the rows in front run, the ranks exchange a synced norm's per-channel sums (norm.exchange), the rows behind run."""
+
+    def __init__(self, local, gathered, group):
+        self.local, self.gathered, self.group = local, gathered, group
+
+
+def _run_cut(rows, run):
+    """run(segment) for every run of rows between the Cuts of `rows`, the exchange of each Cut in between.  A list without a Cut is one call, as it is."""
+    seg = []
+    for r in rows:
+        if isinstance(r, Cut):
+            run(seg)
+            norm.exchange(r.local, r.gathered, r.group)
+            seg = []
+        else:
+            seg.append(r)
+    if seg:
+        run(seg)
+
+
 class Block:
     """One conv -> norm (-> ReLU) block of a chain: the modules (parameters and running statistics stay theirs) and what is fixed about them."""
 
@@ -101,7 +123,7 @@ def _has_hooks(m):
 
 def flatten_blocks(groups):
     """groups: the backbone's stages in execution order (SparseSequential each).  -> list of Block, or None when a stage is not a plain sequence of
-    (SparseConvolution, BatchNorm1d, ReLU) triples.  The last block of every stage is a tap."""
+    (SparseConvolution, BatchNorm1d | SyncBatchNorm, ReLU) triples.  The last block of every stage is a tap."""
     from .conv import SparseConvolution
     from .modules import SparseSequential
     blocks = BlockList()
@@ -124,7 +146,7 @@ def flatten_blocks(groups):
             return None
         for j in range(0, len(mods), 3):
             conv, bn, relu = mods[j:j + 3]
-            if not (isinstance(conv, SparseConvolution) and type(bn) is torch.nn.BatchNorm1d and type(relu) is torch.nn.ReLU):
+            if not (isinstance(conv, SparseConvolution) and norm.route(bn) is not None and type(relu) is torch.nn.ReLU):
                 return None
             blocks.append(Block(conv, bn, True, False))
         blocks[-1].tap = True
@@ -201,6 +223,10 @@ class SparseChainFunction(torch.autograd.Function):
         n_part = lib.sv_conv_planned_partials()
         rows, x_ptr, n_src, keep = [], features.data_ptr(), features.shape[0], []
         frags = []
+        # a SyncBatchNorm over several ranks (norm.route): the list is cut behind the block's own sums, the ranks exchange them, the next list starts with
+        # the combine over all ranks.  Every rank keeps the total row count of each synced block on the device for the backward.
+        synced = [norm.route(b.bn) == norm.SYNCED for b in blocks]
+        totals = torch.empty((len(blocks),), dtype=torch.float64, device=dev) if any(synced) else None
         in_coef = None                                                                # (address, relu) of the transform the next conv applies on load
         for k, (b, rb) in enumerate(zip(blocks, rulebooks)):
             w, gamma, beta = params[3 * k:3 * k + 3]
@@ -223,7 +249,16 @@ class SparseChainFunction(torch.autograd.Function):
                 wt = wk.detach().permute(0, 2, 1).contiguous()                       # (K, C_out, C_in): the 3-channel input layer only
                 keep.append(wt)
                 rows.append(_row(OP_CONV_PLAIN, i=(b.K, b.cin, b.cout, 0), n=(n_src, rb.n_out), p=(x_ptr, rb.addr("nbr_out"), wt.data_ptr(), o_conv)))
-            if BN_FOLD:
+            if synced[k]:
+                local, gathered, group = norm.sync_buffers(b.bn, b.cout, dev)
+                rows.append(_row(OP_BN_STATS_LOCAL, i=(b.cout, n_part if partial else 0), n=(rb.n_out,), p=(None if partial else o_conv, scratch, local.data_ptr())))
+                rows.append(Cut(local, gathered, group))
+                rows.append(_row(OP_BN_FINALIZE_GLOBAL, i=(b.cout, gathered.shape[0]), f=b.mom_eps,
+                                 p=(gathered.data_ptr(), gamma.data_ptr(), beta.data_ptr(), b.bn.running_mean.data_ptr(), b.bn.running_var.data_ptr(), o_coef, o_mean,
+                                    o_istd, b.bn.num_batches_tracked.data_ptr(), totals.data_ptr() + 8 * k)))
+                if materialize[k]:
+                    rows.append(_row(OP_BN_APPLY, i=(b.cout, int(b.relu)), n=(rb.n_out,), p=(o_conv, o_coef, o_y)))
+            elif BN_FOLD:
                 rows.append(_row(OP_BN_FINALIZE, i=(b.cout, n_part if partial else 0), n=(rb.n_out,), f=b.mom_eps,
                                  p=(gamma.data_ptr(), beta.data_ptr(), b.bn.running_mean.data_ptr(), b.bn.running_var.data_ptr(), scratch, o_coef, o_mean, o_istd,
                                     b.bn.num_batches_tracked.data_ptr(), None if partial else o_conv)))
@@ -238,9 +273,12 @@ class SparseChainFunction(torch.autograd.Function):
             else:
                 x_ptr, in_coef = o_y, None
             n_src = rb.n_out
-        _run(rows, "sv_run_ops (chain forward)")
-        ctx.blocks, ctx.rulebooks, ctx.offs, ctx.frags, ctx.fold_in = blocks, rulebooks, offs, frags, fold_in
-        ctx.save_for_backward(features, arena, *params)
+        if totals is None:
+            _run(rows, "sv_run_ops (chain forward)")
+        else:
+            _run_cut(rows, lambda seg: _run(seg, "sv_run_ops (chain forward)"))
+        ctx.blocks, ctx.rulebooks, ctx.offs, ctx.frags, ctx.fold_in, ctx.synced = blocks, rulebooks, offs, frags, fold_in, synced
+        ctx.save_for_backward(features, arena, totals, *params)
         # a tap whose normalised output is written in the list is that tensor; the others hand out [raw conv output, coefficients] (see run_chain)
         outs = []
         for k, b in enumerate(blocks):
@@ -257,8 +295,8 @@ class SparseChainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         lib = _lib.load()
-        features, arena, *params = ctx.saved_tensors
-        blocks, rulebooks, offs, frags, fold_in = ctx.blocks, ctx.rulebooks, ctx.offs, ctx.frags, ctx.fold_in
+        features, arena, totals, *params = ctx.saved_tensors
+        blocks, rulebooks, offs, frags, fold_in, synced = ctx.blocks, ctx.rulebooks, ctx.offs, ctx.frags, ctx.fold_in, ctx.synced
         dev = arena.device
         L = len(blocks)
         ext, gi = [None] * L, 0                                                       # gradient that reaches a block's output from outside the chain
@@ -302,8 +340,17 @@ class SparseChainFunction(torch.autograd.Function):
             x_in = features.data_ptr() if k == 0 else abase + 4 * offs[k - 1][0 if fold_in[k] else 1]
             x_coef = (abase + 4 * offs[k - 1][4], int(blocks[k - 1].relu)) if fold_in[k] else (None, 0)
             scratch = norm._scratch(b.cout, dev)
-            rows.append(_row(OP_BN_BWD, i=(b.cout, int(b.relu), n_part_bwd), n=(rb.n_out,),
-                             p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), o_dconv, o_dg, o_db)))
+            if synced[k]:                                                              # this rank's two sums | exchange | the elementwise pass with everybody's
+                local, gathered, group = norm.sync_buffers(b.bn, b.cout, dev, backward=True)
+                rows.append(_row(OP_BN_BWD_SUMS_LOCAL, i=(b.cout, int(b.relu), n_part_bwd), n=(rb.n_out,),
+                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), o_dg, o_db, local.data_ptr())))
+                rows.append(Cut(local, gathered, group))
+                rows.append(_row(OP_BN_BWD_APPLY_GLOBAL, i=(b.cout, int(b.relu), gathered.shape[0]), n=(rb.n_out,),
+                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), gathered.data_ptr(),
+                                    totals.data_ptr() + 8 * k, o_dconv)))
+            else:
+                rows.append(_row(OP_BN_BWD, i=(b.cout, int(b.relu), n_part_bwd), n=(rb.n_out,),
+                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), o_dconv, o_dg, o_db)))
             n_part_bwd = 0
             rows.append(_row(OP_WGRAD_DEFERRED if DEFER_WGRAD_REDUCE else OP_WGRAD, i=(b.K, b.cin, b.cout, rb.n_in, x_coef[1]), n=(rb.n_out, b.cin, 1, b.K * b.cin),
                              p=(x_in, rb.addr("nbr_out"), o_dconv, wbase + 4 * woffs[k], wscratch.data_ptr() + poffs[k], wplans[k] or None, x_coef[0])))
@@ -326,7 +373,10 @@ class SparseChainFunction(torch.autograd.Function):
                                      p=(o_dconv, a_rows, a_perm, a_masks_p, a_tiles, frags[k].data_ptr(), o_dx, None,
                                         None, None, None if res is None else res.data_ptr(), None)))
                 dy_ptr = o_dx
-        if WGRAD_STREAM:
+        # cut lists (synced norms): every segment is a call of its own, so a weight gradient joins -- and a deferred reduction runs -- at the end of its segment
+        if totals is not None:
+            _run_cut(rows, (lambda seg: _run_two_streams(seg, dev)) if WGRAD_STREAM else (lambda seg: _run(seg, "sv_run_ops (chain backward)")))
+        elif WGRAD_STREAM:
             _run_two_streams(rows, dev)
         else:
             _run(rows, "sv_run_ops (chain backward)")

@@ -88,20 +88,22 @@ class SparseConvolution(SparseModule):
         return out
 
     def fusable_with(self, bn, x):
-        """True when forward_bn_relu may replace self -> bn (-> ReLU): no bias, a training-mode nn.BatchNorm1d with
+        """True when forward_bn_relu may replace self -> bn (-> ReLU): no bias, a training-mode nn.BatchNorm1d (or a torch.nn.SyncBatchNorm, norm.route()) with
         affine parameters and running statistics on a channel count the fused kernels take, fp32 CUDA features, at least two output rows."""
         from . import norm
-        return (self.bias is None and type(bn) is nn.BatchNorm1d and bn.training and bn.affine and bn.track_running_stats
+        return (self.bias is None and norm.route(bn) is not None and bn.training and bn.affine and bn.track_running_stats
                 and bn.momentum is not None and norm.channels_fusable(self.out_channels) and x.features.is_cuda
                 and x.features.dtype == torch.float32 and x.features.shape[0] > 1)
 
     def forward_bn_relu(self, x, bn, relu):
         """self -> bn (-> ReLU) as one autograd node (Fsp.SparseConvBNReLUFunction)."""
+        from . import norm
         rb = self.get_rulebook(x)
-        if rb.n_out < 2:
+        synced = norm.route(bn) == norm.SYNCED
+        if rb.n_out < 2 and not synced:                                               # synced: the other ranks bring the second value
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {(rb.n_out, self.out_channels)}")
         feats = Fsp.SparseConvBNReLUFunction.apply(x.features, self.weight_kio(), rb, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                                   bn.momentum, bn.eps, bool(relu), bn.num_batches_tracked)
+                                                   bn.momentum, bn.eps, bool(relu), bn.num_batches_tracked, bn if synced else None)
         return SparseConvTensor(feats, rb.out_indices, rb.out_shape, x.batch_size, x.grid, x.indice_dict)
 
 

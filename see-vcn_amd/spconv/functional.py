@@ -773,7 +773,7 @@ class SparseConvBNReLUFunction(torch.autograd.Function):
     are the plain torch ones."""
 
     @staticmethod
-    def forward(ctx, features, weight_kio, rulebook, gamma, beta, running_mean, running_var, momentum, eps, relu, num_batches_tracked):
+    def forward(ctx, features, weight_kio, rulebook, gamma, beta, running_mean, running_var, momentum, eps, relu, num_batches_tracked, sync_bn=None):
         from . import norm
         _lib.require_cuda(features, weight_kio)
         features = features.contiguous().float()
@@ -781,19 +781,27 @@ class SparseConvBNReLUFunction(torch.autograd.Function):
         cout, used = weight_kio.shape[2], []
         conv_out, ctx.frag_bwd = _conv_forward(features, weight_kio, rulebook, bn_partial=(lambda: used.append(1) or norm.partial_address(cout, features.device))
                                                if norm.STATS_IN_CONV else None)
-        y, mean, invstd = norm.bn_forward_raw(conv_out, gamma, beta, running_mean, running_var, momentum, eps, True, relu, num_batches_tracked,
-                                              n_partials=_lib.load().sv_conv_planned_partials() if used else 0)
+        n_partials = _lib.load().sv_conv_planned_partials() if used else 0
+        ctx.sync_bn, total = sync_bn, None
+        if sync_bn is not None:                        # a SyncBatchNorm over several ranks (norm.route): the per-channel sums are exchanged inside
+            y, mean, invstd, total = norm.bn_forward_synced(conv_out, sync_bn, relu, n_partials=n_partials)
+        else:
+            y, mean, invstd = norm.bn_forward_raw(conv_out, gamma, beta, running_mean, running_var, momentum, eps, True, relu, num_batches_tracked,
+                                                  n_partials=n_partials)
         ctx.rulebook, ctx.relu = rulebook, relu
-        ctx.save_for_backward(features, weight_kio, conv_out, gamma, beta, mean, invstd)
+        ctx.save_for_backward(features, weight_kio, conv_out, gamma, beta, mean, invstd, total)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         from . import norm
-        features, weight_kio, conv_out, gamma, beta, mean, invstd = ctx.saved_tensors
-        dconv, dgamma, dbeta = norm.bn_backward_raw(conv_out, dy.contiguous().float(), gamma, beta, mean, invstd, ctx.relu)
+        features, weight_kio, conv_out, gamma, beta, mean, invstd, total = ctx.saved_tensors
+        if ctx.sync_bn is not None:
+            dconv, dgamma, dbeta = norm.bn_backward_synced(conv_out, dy.contiguous().float(), ctx.sync_bn, gamma, beta, mean, invstd, total, ctx.relu)
+        else:
+            dconv, dgamma, dbeta = norm.bn_backward_raw(conv_out, dy.contiguous().float(), gamma, beta, mean, invstd, ctx.relu)
         gf, gw = _conv_backward(features, weight_kio, ctx.rulebook, ctx.frag_bwd, dconv, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return gf, gw, None, (dgamma if gamma is not None else None), (dbeta if beta is not None else None), None, None, None, None, None, None
+        return gf, gw, None, (dgamma if gamma is not None else None), (dbeta if beta is not None else None), None, None, None, None, None, None, None
 
 
 class DenseFunction(torch.autograd.Function):
