@@ -174,6 +174,17 @@ def voxel_backbone8x_forward(sd, features, coords, batch_size, sparse_shape):
     return res
 
 
+def basic_block_forward(sd, x, nbr, prefix):
+    """SparseBasicBlock (spconv_backbone.py:30-66) in eval mode on the submanifold table nbr: conv(bias) - bn - relu - conv(bias) - bn, + identity, relu;
+    sd[prefix + '.conv1.weight'] etc. in the 2.x layout."""
+    y = conv_forward(x, nbr, weight_to_kio(np.asarray(sd[prefix + ".conv1.weight"])), np.asarray(sd[prefix + ".conv1.bias"], np.float64))
+    y = _bn_relu(y, sd, prefix + ".bn1")
+    y = conv_forward(y, nbr, weight_to_kio(np.asarray(sd[prefix + ".conv2.weight"])), np.asarray(sd[prefix + ".conv2.bias"], np.float64))
+    g, b, m, v = (np.asarray(sd[f"{prefix}.bn2.{k}"], np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
+    y = (y - m) / np.sqrt(v + 1e-3) * g + b
+    return np.maximum(y + x, 0.0)
+
+
 def voxel_res_backbone8x_forward(sd, features, coords, batch_size, sparse_shape):
     """VoxelResBackBone8x.forward (spconv_backbone.py:241-293, layers :191-232; SparseBasicBlock :30-66) in eval mode: conv_input,
     two residual blocks per level (conv(bias) - bn - relu - conv(bias) - bn, + identity, relu; both convs of a block and both blocks of a
@@ -183,12 +194,7 @@ def voxel_res_backbone8x_forward(sd, features, coords, batch_size, sparse_shape)
         return weight_to_kio(np.asarray(sd[key]))
 
     def basic_block(x, nbr, prefix):
-        y = conv_forward(x, nbr, w(prefix + ".conv1.weight"), np.asarray(sd[prefix + ".conv1.bias"], np.float64))
-        y = _bn_relu(y, sd, prefix + ".bn1")
-        y = conv_forward(y, nbr, w(prefix + ".conv2.weight"), np.asarray(sd[prefix + ".conv2.bias"], np.float64))
-        g, b, m, v = (np.asarray(sd[f"{prefix}.bn2.{k}"], np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
-        y = (y - m) / np.sqrt(v + 1e-3) * g + b
-        return np.maximum(y + x, 0.0)
+        return basic_block_forward(sd, x, nbr, prefix)
 
     shape = tuple(int(s) for s in sparse_shape)
     nbr = rulebook_subm(coords, shape, 3)

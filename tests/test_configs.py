@@ -62,14 +62,63 @@ def test_hip_centerpoint_res_backbone_at_config5_size(cuda, hip_lib):
     assert_close_per_channel(t.features.cpu().numpy(), f, name="conv_out")
     assert bd["multi_scale_3d_features"]["x_conv4"].features.shape[1] == 128           # the 128 -> 128 residual layers ran
 
-    # whole detector: train step (targets, losses, backward through the residual blocks) and eval decode
+    # whole detector: train step (targets, losses, backward through the residual blocks) and eval decode.  The backward of the residual backbone is held to
+    # the float64 oracle for the sampled stages below (tests/test_spconv.py holds ALL of it on 2 scenes); the other layers are checked for finite, non-zero gradients.
+    from oracle import spconv_train as ost
+    from test_spconv import HINT_BAND, HINT_CAP, _check_conv_bias_gradients, _res_branch_hooks
     net.train()
+    taps, branches = {}, {}
+
+    def keep_taps(_m, _i, out):                                                  # the stage boundaries of THIS step, their gradients retained
+        taps.update(out["multi_scale_3d_features"])
+        taps["out"] = out["encoded_spconv_tensor"]
+        for name in ("x_conv3", "x_conv4", "out"):
+            taps[name].features.retain_grad()
+
+    hooks = _res_branch_hooks(net.backbone_3d, branches, only=("conv4", "conv_out")) + [net.backbone_3d.register_forward_hook(keep_taps)]
     ret, tb, _ = net(dict(batch))
+    for h in hooks:
+        h.remove()
     assert torch.isfinite(ret["loss"]) and "rpn_loss" in tb
     ret["loss"].backward()
+    grads = {k: p.grad for k, p in net.backbone_3d.named_parameters()}
     for key in ("conv4.1.conv1.weight", "conv4.2.conv2.weight", "conv1.0.conv1.bias", "conv_out.0.weight"):
-        g = dict(net.backbone_3d.named_parameters())[key].grad
+        g = grads[key]
         assert g is not None and torch.isfinite(g).all() and float(g.abs().max()) > 0, key
+    # sampled stages at this size, the step's own tensors on both sides (as test_hip_train_step_gradients_of_sampled_stages_at_16_scenes does for the plain
+    # backbone): x_conv3 -> x_conv4 = the 64 -> 128 strided block + two 128-channel SparseBasicBlocks, x_conv4 -> out = conv_out.  Stage output, input gradient and
+    # every conv weight / BatchNorm gradient per channel; the conv biases by the rounding-noise bound of tests/test_spconv.py; ReLU branches as hints within 1e-4.
+    import time
+    stages = [("x_conv3", "x_conv4", [("conv4.0.0.weight", "conv4.0.1", "sparse", 3, 2, (0, 1, 1)), ("basic", "conv4.1"), ("basic", "conv4.2")], 3 + 2 * 6),
+              ("x_conv4", "out", [("conv_out.0.weight", "conv_out.1", "sparse", (3, 1, 1), (2, 1, 1), 0)], 3)]
+    for src, dst, layers, n_params in stages:
+        t0 = time.time()
+        xin, yout = taps[src], taps[dst]
+        assert xin.features.grad is not None and yout.features.grad is not None, (src, dst)
+        prefixes = tuple(l[1] if l[0] == "basic" else l[0].rsplit(".0.weight", 1)[0] for l in layers)
+        hints = {k: v for k, v in branches.items() if k.startswith(prefixes)}
+        assert len(hints) == sum(2 if l[0] == "basic" else 1 for l in layers), sorted(hints)
+        ref, leaves, oc, oshape, info = ost.res_stage_train_chain(bsd, layers, xin.features.detach().cpu().numpy(), xin.indices.cpu().numpy(), xin.spatial_shape,
+                                                                  branch_hints=hints, hint_band=HINT_BAND)
+        assert info["hinted"] == sum(h.size for h in hints.values()) and info["overridden"] <= HINT_CAP * info["hinted"], (dst, info["overridden"], info["hinted"])
+        assert np.array_equal(yout.indices.cpu().numpy(), oc) and list(yout.spatial_shape) == list(oshape), dst
+        assert_close_per_channel(yout.features.detach().cpu().numpy(), ref.detach().numpy(), name=f"res {dst} features (config 5, train)")
+        ref.backward(yout.features.grad.detach().cpu().double())
+        assert_close_per_channel(xin.features.grad.cpu().numpy(), leaves["input"].grad.numpy(), rtol=2e-3, atol_frac=2e-4, name=f"res d loss / d {src} (config 5)")
+        checked, bias_grads = 0, {}
+        for k in leaves:
+            if k == "input":
+                continue
+            got = grads[k].detach().cpu().numpy()
+            if k.endswith(".bias") and ".conv" in k:
+                bias_grads[k] = got
+                continue
+            assert_close_per_channel(osp.weight_to_kio(got) if got.ndim == 5 else got, leaves[k].grad.numpy(), rtol=2e-3, atol_frac=2e-3, name=f"res grad {k} (config 5)")
+            checked += 1
+        needed = []
+        assert checked + _check_conv_bias_gradients(bias_grads, info, needed) == n_params + (4 if n_params > 3 else 0), (dst, checked)
+        print(f"config 5 stage {src} -> {dst}: {xin.features.shape[0]} -> {yout.features.shape[0]} rows, branches from the device {info['overridden']} of {info['hinted']}, "
+              f"bias f needed {max(needed) if needed else 0:.3f}, oracle {time.time() - t0:.1f} s")
     net.eval()
     with torch.no_grad():
         preds, recall = net(dict(batch))

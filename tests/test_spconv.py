@@ -104,6 +104,133 @@ def test_oracle_backward_matches_autograd_of_dense_conv():
     np.testing.assert_allclose(gw, osp.weight_to_kio(w.grad.numpy()), rtol=1e-9, atol=1e-9)
 
 
+def _dense_conv_rows(x, coords, shape, w2x, stride, padding, out_coords, batch):
+    """Rows of F.conv3d(densified x) at out_coords: the sparse conv restricted to its active output sites, without oracle/spconv.py's gather loops."""
+    ci = [torch.from_numpy(np.asarray(coords[:, i], np.int64)) for i in range(4)]
+    dense = torch.zeros(batch, *shape, x.shape[1], dtype=x.dtype).index_put((ci[0], ci[1], ci[2], ci[3]), x).permute(0, 4, 1, 2, 3)
+    o = F.conv3d(dense, w2x.permute(0, 4, 1, 2, 3), stride=stride, padding=padding)
+    oc = [torch.from_numpy(np.asarray(out_coords[:, i], np.int64)) for i in range(4)]
+    return o[oc[0], :, oc[1], oc[2], oc[3]]
+
+
+def test_oracle_residual_stage_chain_equals_dense_conv3d_autograd():
+    """oracle/spconv_train.py res_stage_train_chain (strided conv-BN-ReLU 16 -> 32, then two SparseBasicBlocks of 32 channels with conv biases) against
+    the same stage built from F.conv3d on the densified tensor restricted to the active sites + torch's batch_norm on the gathered rows, under autograd
+    in float64: output, input gradient and every parameter gradient."""
+    from oracle import spconv_train as ost
+    rng = np.random.default_rng(12)
+    batch, shape = 2, (9, 20, 18)
+    coords = _rand_coords(rng, 420, batch, shape)
+    feats = rng.normal(size=(len(coords), 16))
+    sd = {"down.0.weight": rng.normal(size=(32, 3, 3, 3, 16)) * 0.1}
+    for bn in ("down.1", "a.bn1", "a.bn2", "b.bn1", "b.bn2"):
+        sd[bn + ".weight"], sd[bn + ".bias"] = rng.uniform(0.5, 1.5, size=32), rng.normal(size=32) * 0.3
+    for cv in ("a.conv1", "a.conv2", "b.conv1", "b.conv2"):
+        sd[cv + ".weight"], sd[cv + ".bias"] = rng.normal(size=(32, 3, 3, 3, 32)) * 0.1, rng.normal(size=32)
+    layers = [("down.0.weight", "down.1", "sparse", 3, 2, 1), ("basic", "a"), ("basic", "b")]
+    out, leaves, oc, oshape, info = ost.res_stage_train_chain(sd, layers, feats, coords, shape)
+    assert 100 < len(oc) < len(coords) and info["overridden"] == 0 and info["hinted"] == 0
+    go = torch.from_numpy(rng.normal(size=tuple(out.shape)))
+    (out * go).sum().backward()
+
+    P = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=True) for k, v in sd.items()}
+    x0 = torch.tensor(feats, requires_grad=True)
+    bnf = lambda x, bn: F.batch_norm(x, None, None, P[bn + ".weight"], P[bn + ".bias"], True, 0.01, 1e-3)
+    x = torch.relu(bnf(_dense_conv_rows(x0, coords, shape, P["down.0.weight"], 2, 1, oc, batch), "down.1"))
+    for blk in ("a", "b"):
+        y = _dense_conv_rows(x, oc, oshape, P[blk + ".conv1.weight"], 1, 1, oc, batch) + P[blk + ".conv1.bias"]
+        y = torch.relu(bnf(y, blk + ".bn1"))
+        y = _dense_conv_rows(y, oc, oshape, P[blk + ".conv2.weight"], 1, 1, oc, batch) + P[blk + ".conv2.bias"]
+        x = torch.relu(bnf(y, blk + ".bn2") + x)
+    (x * go).sum().backward()
+    np.testing.assert_allclose(out.detach().numpy(), x.detach().numpy(), rtol=1e-9, atol=1e-9)
+    assert float((out.detach() == 0).double().mean()) > 0.05 and float((out.detach() > 0).double().mean()) > 0.05     # both ReLU branches are taken
+    np.testing.assert_allclose(leaves["input"].grad.numpy(), x0.grad.numpy(), rtol=1e-9, atol=1e-9)
+    assert set(leaves) == set(sd) | {"input"}
+    for k in sd:
+        want = P[k].grad.numpy()
+        np.testing.assert_allclose(leaves[k].grad.numpy(), osp.weight_to_kio(want) if want.ndim == 5 else want, rtol=1e-9, atol=1e-9, err_msg=k)
+    # a conv bias in front of a batch-statistics BatchNorm has a zero gradient; the statistics reported are those of the BatchNorm's input
+    assert float(leaves["a.conv1.bias"].grad.abs().max()) < 1e-9 * float(leaves["a.bn1.bias"].grad.abs().max())
+    mean, var, rows = info["bn_stats"]["b.bn2"]
+    zin = info["bn_in"]["b.bn2"].detach().numpy()
+    assert rows == len(oc)
+    np.testing.assert_allclose(mean, zin.mean(0), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(var, zin.var(0), rtol=1e-12, atol=1e-12)
+
+
+# ---- the conv biases of VoxelResBackBone8x in training.  A bias in front of a batch-statistics BatchNorm has a mathematically zero gradient: what any evaluation
+# holds there is rounding noise, so it is bounded instead of compared: per channel c, |grad_bias[c]| <= f * 2**-24 * sum_rows |dz[:, c]|, dz = the float64 chain's
+# gradient at that BatchNorm's INPUT (the bias gradient is its column sum).  f comes from the reference, not from the device: the same oracle chain evaluated in
+# float32 on the CPU (input of the 2-scene test below) needs f_ref = max over all 16 conv biases and their channels = 0.763 (per layer 0.23 .. 0.76); the device is
+# allowed 16 x that -- it sums the rows in plan / tree order and forms the BatchNorm backward from per-workgroup partials: noise of the same kind, another draw.
+# A real gradient is larger by about the row count over 2**-24.  test_oracle_res_backbone_chain_float32_vs_float64 re-derives f_ref and checks that the bound rejects
+# the column sum of the gradient BEHIND the BatchNorm (what a bias placed after the norm would receive) in every channel (smallest ratio there: 22.9).
+BIAS_GRAD_F_REF = 0.763
+BIAS_GRAD_F = 16 * BIAS_GRAD_F_REF
+RES_CHAIN_INPUT = dict(n_scenes=2, seed=2000, n_az=90)          # float32 vs float64 oracle on this input: 1 of 12 197 920 ReLU branches differs (cap 1e-4: 1 219)
+HINT_BAND, HINT_CAP = 1e-4, 1e-4
+KITTI_GEOMETRY = ([0, -40, -3, 70.4, 40, 1], [0.05, 0.05, 0.1], [1408, 1600, 40])
+
+
+def _conv_bias_bn(key):
+    """'<block>.conv1.bias' -> '<block>.bn1': the BatchNorm a SparseBasicBlock's conv bias sits in front of."""
+    return key.replace(".conv1.bias", ".bn1").replace(".conv2.bias", ".bn2")
+
+
+def test_oracle_res_backbone_chain_float32_vs_float64():
+    """The reference alone, on the input of the 2-scene GPU test (voxelised by the oracle): (1) the composition of res_backbone8x_train_chain equals the eval-mode
+    oracle (oracle/spconv.py voxel_res_backbone8x_forward, which the device's eval forward is held to) once that is given the chain's batch statistics as running
+    statistics; (2) float32 and float64 evaluations take different ReLU branches at far fewer positions than the cap the GPU test sets on overridden hints;
+    (3) f_ref of the bias rule above is what the float32 chain needs, and the rule at f = 16 f_ref rejects a plausible wrong value in every channel."""
+    import seevcn_amd.synth as synth
+    from oracle import spconv_train as ost, voxelize as ov
+    from seeding import seeded_state_dict
+    from seevcn_amd.pcdet.models import backbones_3d
+    pts, _ = synth.make_scene_batch(RES_CHAIN_INPUT["n_scenes"], seed=RES_CHAIN_INPUT["seed"], n_az=RES_CHAIN_INPUT["n_az"])
+    pc_range, vs, grid = KITTI_GEOMETRY
+    feats, coords, _ = ov.dynamic_mean_vfe(pts, pc_range, vs, grid)
+    m = backbones_3d.__all__["VoxelResBackBone8x"]({}, 3, grid)
+    sd = {k: v.numpy() for k, v in seeded_state_dict(m, seed=1).items()}
+    run, threads = {}, torch.get_num_threads()
+    torch.set_num_threads(16)                 # torch splits its float32 reductions by thread: f_ref was taken at 16 (0.763; 1.33 with 8)
+    try:
+        for dt in (torch.float64, torch.float32):
+            dense, leaves, info = ost.res_backbone8x_train_chain(sd, feats, coords, 2, m.sparse_shape, dtype=dt)
+            G = torch.from_numpy(np.random.default_rng(5).normal(size=tuple(dense.shape)).astype(np.float32))
+            (dense * G.to(dt)).sum().backward()
+            run[dt] = (leaves, info)
+    finally:
+        torch.set_num_threads(threads)
+    (l64, i64), (l32, i32) = run[torch.float64], run[torch.float32]
+    assert set(l64) == {k for k, _ in m.named_parameters()} | {"input"} and len(i64["bn_stats"]) == 21
+    # (1) composition
+    sd_eval = dict(sd)
+    for bn, (mean, var, rows) in i64["bn_stats"].items():
+        sd_eval[bn + ".running_mean"], sd_eval[bn + ".running_var"] = mean, var
+    ref = osp.voxel_res_backbone8x_forward(sd_eval, feats, coords, 2, m.sparse_shape)
+    for name, (f, c, shape) in i64["taps"].items():
+        assert np.array_equal(c, ref[name][1]) and tuple(shape) == tuple(ref[name][2]), name
+        np.testing.assert_allclose(f.detach().numpy(), ref[name][0], rtol=1e-9, atol=1e-9, err_msg=name)
+    # (2) ReLU branches
+    differ = sum(int(((i64["pre_act"][k] > 0) != (i32["pre_act"][k] > 0)).sum()) for k in i64["pre_act"])
+    total = sum(v.numel() for v in i64["pre_act"].values())
+    assert len(i64["pre_act"]) == 5 + 16 and differ <= 0.1 * HINT_CAP * total, (differ, total)
+    # (3) conv biases
+    eps32, f_ref, biases = 2.0 ** -24, 0.0, [k for k in l64 if k.endswith(".bias") and ".conv" in k]
+    assert len(biases) == 16
+    for k in biases:
+        bn = _conv_bias_bn(k)
+        unit = eps32 * np.abs(i64["bn_in"][bn].grad.numpy()).sum(0)
+        f_ref = max(f_ref, float((np.abs(l32[k].grad.numpy().astype(np.float64)) / unit).max()))
+        assert (np.abs(l64[k].grad.numpy()) <= 1e-6 * unit).all(), k                         # zero in exact arithmetic: float64 is 8 orders below float32
+        behind = np.abs(i64["bn_out"][bn].grad.numpy().sum(0))
+        assert (behind > BIAS_GRAD_F * unit).all(), (k, float((behind / unit).min()))
+    print(f"float32 vs float64 oracle: {differ} of {total} branches differ; f_ref {f_ref:.3f}")
+    # the summation order of torch's float32 reductions is not fixed across builds and thread counts: the same kind of noise, within a factor 2
+    assert 0.5 * BIAS_GRAD_F_REF <= f_ref <= 2.0 * BIAS_GRAD_F_REF, f_ref
+
+
 def test_shim_api_surface():
     import seevcn_amd.spconv as spconv
     from seevcn_amd.pcdet.models import backbones_3d
@@ -519,6 +646,155 @@ def test_hip_backbone8x_train_step_gradients_vs_oracle_chain(cuda, hip_lib):
     assert checked == 12 + 24
     # running statistics moved like torch's BatchNorm1d (momentum 0.01, unbiased variance)
     assert int(m.conv_out[1].num_batches_tracked) == 1 and float((m.conv_out[1].running_mean - sd["conv_out.1.running_mean"].to(cuda)).abs().max()) > 0
+
+
+def _res_branch_hooks(m, recorded, only=("",)):
+    """Forward hooks that record the ReLU branches VoxelResBackBone8x took, under the hint keys of oracle/spconv_train.py _Layers: a conv-BN-ReLU block
+    under its conv key, a SparseBasicBlock's output under its prefix and the ReLU behind bn1 (the input of conv2) under '<prefix>.bn1'; `only`: module
+    name prefixes to record.  -> hooks"""
+    hooks = []
+    for name, mod in m.named_modules():
+        if not name.startswith(tuple(only)):
+            continue
+        if type(mod).__name__ == "SparseBasicBlock":
+            hooks.append(mod.register_forward_hook(lambda _m, _i, out, k=name: recorded.__setitem__(k, (out.features.detach() > 0).cpu().numpy())))
+            hooks.append(mod.conv2.register_forward_hook(lambda _m, i, _o, k=name + ".bn1": recorded.__setitem__(k, (i[0].features.detach() > 0).cpu().numpy())))
+        elif name == "conv_input" or name == "conv_out" or name in ("conv2.0", "conv3.0", "conv4.0"):
+            hooks.append(mod.register_forward_hook(lambda _m, _i, out, k=name + ".0.weight": recorded.__setitem__(k, (out.features.detach() > 0).cpu().numpy())))
+    return hooks
+
+
+def _check_conv_bias_gradients(named_grads, info, needed):
+    """The bias rule (BIAS_GRAD_F above) for every '<block>.convN.bias' of named_grads {key: numpy}; info: the float64 chain's, after its backward.  -> count"""
+    count = 0
+    for key, got in named_grads.items():
+        if not (key.endswith(".bias") and ".conv" in key):
+            continue
+        unit = 2.0 ** -24 * np.abs(info["bn_in"][_conv_bias_bn(key)].grad.numpy()).sum(0)
+        ratio = np.abs(got.astype(np.float64)) / unit
+        needed.append(float(ratio.max()))
+        assert np.isfinite(got).all() and (ratio <= BIAS_GRAD_F).all(), (key, float(ratio.max()), BIAS_GRAD_F)
+        count += 1
+    return count
+
+
+@pytest.mark.gpu
+def test_hip_res_backbone8x_train_step_gradients_vs_oracle_chain(cuda, hip_lib):
+    """DynMeanVFE -> VoxelResBackBone8x (TRAIN mode; the module-by-module path: spconv/chain.py declines conv biases and residual blocks) ->
+    HeightCompression -> loss -> backward on 2 scenes against the float64 chain (oracle/spconv_train.py res_backbone8x_train_chain): features and
+    coordinates at every tap, the input gradient, all 21 conv weight and 42 BatchNorm parameter gradients element-wise per channel, the 16 conv biases by
+    the rounding-noise bound above, the running statistics of all 21 BatchNorms after the step.  The oracle follows the device's ReLU branch only where
+    its own pre-activation is within 1e-4 of zero; at most 1e-4 of the activations may be decided that way."""
+    import seevcn_amd.synth as synth
+    from oracle import spconv_train as ost
+    from seeding import seeded_state_dict
+    from tolerances import assert_close_per_channel
+    from seevcn_amd.pcdet.models import backbones_3d
+    from seevcn_amd.pcdet.models.backbones_2d import map_to_bev
+    from seevcn_amd.pcdet.models.backbones_3d import vfe
+    pts, _ = synth.make_scene_batch(RES_CHAIN_INPUT["n_scenes"], seed=RES_CHAIN_INPUT["seed"], n_az=RES_CHAIN_INPUT["n_az"])
+    pc_range, vs, grid = KITTI_GEOMETRY
+    bd = {"batch_size": 2, "points": torch.from_numpy(pts).to(cuda)}
+    bd = vfe.__all__["DynMeanVFE"](model_cfg={}, num_point_features=3, voxel_size=vs, grid_size=grid, point_cloud_range=pc_range)(bd)
+    m = backbones_3d.__all__["VoxelResBackBone8x"]({}, 3, grid)
+    sd = seeded_state_dict(m, seed=1)
+    m.load_state_dict(sd)
+    m = m.to(cuda).train()
+    feats = bd["voxel_features"].detach().clone().requires_grad_(True)
+    bd["voxel_features"] = feats
+    branches = {}
+    hooks = _res_branch_hooks(m, branches)
+    bd = map_to_bev.__all__["HeightCompression"]({"NUM_BEV_FEATURES": 256})(m(bd))
+    for h in hooks:
+        h.remove()
+    assert len(branches) == 5 + 16
+    dense = bd["spatial_features"]
+    G = torch.from_numpy(np.random.default_rng(5).normal(size=tuple(dense.shape)).astype(np.float32))
+    (dense * G.to(cuda)).sum().backward()
+
+    sdn = {k: v.numpy() for k, v in sd.items()}
+    ref_dense, leaves, info = ost.res_backbone8x_train_chain(sdn, feats.detach().cpu().numpy(), bd["voxel_coords"].cpu().numpy(), 2, m.sparse_shape,
+                                                             branch_hints=branches, hint_band=HINT_BAND)
+    print(f"ReLU branches taken from the device: {info['overridden']} of {info['hinted']} (cap {HINT_CAP * info['hinted']:.0f})")
+    assert info["hinted"] == sum(b.size for b in branches.values()) and info["overridden"] <= HINT_CAP * info["hinted"], (info["overridden"], info["hinted"])
+    (ref_dense * G.double()).sum().backward()
+    taps = dict(bd["multi_scale_3d_features"])
+    taps["out"] = bd["encoded_spconv_tensor"]
+    for name in ("x_conv1", "x_conv2", "x_conv3", "x_conv4", "out"):
+        f, c, shape = info["taps"][name]
+        assert np.array_equal(taps[name].indices.cpu().numpy(), c) and list(taps[name].spatial_shape) == list(shape), name
+        assert_close_per_channel(taps[name].features.detach().cpu().numpy(), f.detach().numpy(), name=f"res {name} features (train-mode BN)")
+    assert_close_per_channel(feats.grad.cpu().numpy(), leaves["input"].grad.numpy(), rtol=2e-3, atol_frac=2e-4, name="res d loss / d voxel_features")
+    checked, grads = 0, {}
+    for key, p in m.named_parameters():
+        assert p.grad is not None, key
+        got = p.grad.detach().cpu().numpy()
+        grads[key] = got
+        if key.endswith(".bias") and ".conv" in key:
+            continue                                                       # zero in exact arithmetic: bounded below
+        if got.ndim == 5:                                                  # (C_out, kz, ky, kx, C_in) -> (K, C_in, C_out)
+            got = osp.weight_to_kio(got)
+        assert_close_per_channel(got, leaves[key].grad.numpy(), rtol=2e-3, atol_frac=2e-3, name="res grad " + key)
+        checked += 1
+    assert checked == 21 + 42
+    needed = []
+    assert _check_conv_bias_gradients(grads, info, needed) == 16
+    print(f"conv bias gradients: f needed {max(needed):.3f} (allowed {BIAS_GRAD_F:.2f})")
+    # running statistics moved like torch's BatchNorm1d: (1 - momentum) * old + momentum * batch, the variance unbiased
+    bns = {k: mod for k, mod in m.named_modules() if isinstance(mod, torch.nn.BatchNorm1d)}
+    assert set(bns) == set(info["bn_stats"]) and len(bns) == 21
+    for k, mod in bns.items():
+        mean, var, rows = info["bn_stats"][k]
+        assert int(mod.num_batches_tracked) == 1, k
+        np.testing.assert_allclose(mod.running_mean.cpu().numpy(), 0.99 * sdn[k + ".running_mean"].astype(np.float64) + 0.01 * mean, rtol=1e-5, atol=1e-6, err_msg=k)
+        np.testing.assert_allclose(mod.running_var.cpu().numpy(), 0.99 * sdn[k + ".running_var"].astype(np.float64) + 0.01 * var * rows / (rows - 1),
+                                   rtol=1e-5, atol=1e-6, err_msg=k)
+
+
+@pytest.mark.gpu
+def test_hip_basic_block_with_running_statistics_uses_its_conv_biases(cuda, hip_lib):
+    """One SparseBasicBlock(32, 32) whose BatchNorms are in eval mode (running statistics): there the conv biases have REAL gradients.  Forward, input, weight,
+    bias and BatchNorm gradients against the float64 composition conv(+bias) -> bn -> ReLU -> conv(+bias) -> bn -> + identity -> ReLU."""
+    from oracle import spconv_train as ost
+    from seeding import seeded_state_dict
+    from tolerances import assert_close_per_channel
+    import seevcn_amd.spconv as spconv
+    from seevcn_amd.pcdet.models.backbones_3d.spconv_backbone import SparseBasicBlock
+    from functools import partial
+    rng = np.random.default_rng(31)
+    batch, shape = 2, (9, 48, 40)
+    coords = _rand_coords(rng, 2500, batch, shape)
+    feats = rng.normal(size=(len(coords), 32)).astype(np.float32)
+    blk = SparseBasicBlock(32, 32, norm_fn=partial(torch.nn.BatchNorm1d, eps=1e-3, momentum=0.01), indice_key="res")
+    sd = seeded_state_dict(blk, seed=4)
+    blk.load_state_dict(sd)
+    blk = blk.to(cuda).eval()
+    x = torch.from_numpy(feats).to(cuda).requires_grad_(True)
+    out = blk(spconv.SparseConvTensor(x, torch.from_numpy(coords).to(cuda), list(shape), batch)).features
+    go = rng.normal(size=tuple(out.shape)).astype(np.float32)
+    out.backward(torch.from_numpy(go).to(cuda))
+
+    params = {k for k, _ in blk.named_parameters()}
+    P = {k: (torch.from_numpy(osp.weight_to_kio(v.numpy())) if v.dim() == 5 else v.clone()).double().requires_grad_(k in params) for k, v in sd.items()}
+    nbr = osp.rulebook_subm(coords, shape, 3)
+    bn = lambda t, k: F.batch_norm(t, P[k + ".running_mean"], P[k + ".running_var"], P[k + ".weight"], P[k + ".bias"], False, 0.01, 1e-3)
+    x64 = torch.from_numpy(feats).double().requires_grad_(True)
+    y = torch.relu(bn(ost.sparse_conv(x64, P["conv1.weight"], nbr) + P["conv1.bias"], "bn1"))
+    y = torch.relu(bn(ost.sparse_conv(y, P["conv2.weight"], nbr) + P["conv2.bias"], "bn2") + x64)
+    y.backward(torch.from_numpy(go).double())
+    assert 0.05 < float((y == 0).double().mean()) < 0.95
+    assert_close_per_channel(out.detach().cpu().numpy(), y.detach().numpy(), name="basic block (eval BN) output")
+    assert_close_per_channel(x.grad.cpu().numpy(), x64.grad.numpy(), rtol=2e-3, atol_frac=2e-4, name="basic block (eval BN) input gradient")
+    checked = 0
+    for key, p in blk.named_parameters():
+        got = p.grad.detach().cpu().numpy()
+        if got.ndim == 5:
+            got = osp.weight_to_kio(got)
+        assert float(np.abs(P[key].grad.numpy()).max()) > 1e-2, key                       # a real gradient, the biases' included
+        assert_close_per_channel(got, P[key].grad.numpy(), rtol=2e-3, atol_frac=2e-3, name="basic block (eval BN) grad " + key)
+        checked += 1
+    assert checked == 2 + 2 + 4
+    assert int(blk.bn1.num_batches_tracked) == 0 and torch.equal(blk.bn2.running_mean.cpu(), sd["bn2.running_mean"])
 
 
 @pytest.mark.gpu
@@ -1222,3 +1498,203 @@ def test_hip_input_norm_on_load_is_bit_identical_to_the_separate_pass(cuda, hip_
     lib.sv_conv_next_input_norm(coef.data_ptr(), 1)
     with pytest.raises(_lib.SeevcnHipError, match="input transform"):
         Fsp.gather_gemm(x, rb.nbr_out, w.permute(0, 2, 1).contiguous(), rb.n_out)
+
+
+# ---------------------------------------------------------------------------------- the fused epilogue of the forward conv kernels (inference form)
+# epi(v) = relu?( (v + bias?) * scale? + shift? + residual? ) -- the order include/seevcn_hip.h states and conv_epilogue (csrc/sparse_conv.hip) applies
+EPILOGUES = {"bias": ("bias",), "scale+shift": ("scale", "shift"), "residual": ("residual",), "relu": ("relu",), "bias+relu": ("bias", "relu"),
+             "scale+shift+relu": ("scale", "shift", "relu"), "all": ("bias", "scale", "shift", "residual", "relu")}
+
+
+def _epilogue_terms(rng, n_rows, nc, cuda):
+    """numpy and device copies of the four tensors: scale in +-[0.5, 1.5], the others O(1) -- the output keeps the scale of the bare conv"""
+    t = {"bias": rng.normal(size=nc), "scale": rng.uniform(0.5, 1.5, size=nc) * rng.choice([-1.0, 1.0], size=nc), "shift": rng.normal(size=nc),
+         "residual": rng.normal(size=(n_rows, nc))}
+    t = {k: v.astype(np.float32) for k, v in t.items()}
+    return t, {k: torch.from_numpy(v).to(cuda) for k, v in t.items()}
+
+
+def _epilogue_ref(conv64, t, names):
+    v = np.array(conv64, np.float64)
+    if "bias" in names:
+        v = v + t["bias"].astype(np.float64)
+    if "scale" in names:
+        v = v * t["scale"].astype(np.float64) + t["shift"].astype(np.float64)
+    if "residual" in names:
+        v = v + t["residual"].astype(np.float64)
+    if "relu" in names:
+        assert (v < 0).any() and (v > 0).any(), "the ReLU must be seen to clip"
+        v = np.maximum(v, 0.0)
+    return v
+
+
+def _epilogue_kwargs(dev, names):
+    return dict(bias=dev["bias"] if "bias" in names else None, scale=dev["scale"] if "scale" in names else None, shift=dev["shift"] if "shift" in names else None,
+                residual=dev["residual"] if "residual" in names else None, relu="relu" in names)
+
+
+def _epilogue_tables(cuda, big=False):
+    """[(tag, Rulebook)]: a submanifold and a stride-2 table whose row counts are no multiple of 16 (padding rows in the last tile), one with fewer than 16
+    rows, and with big=True a synthetic 80 003-row table: more 16-row tiles than 9/8 of a launch's waves, so that a 64-column layer gets two tiles per wave."""
+    from seevcn_amd.spconv import functional as Fsp
+    rng = np.random.default_rng(41)
+    shape = (9, 48, 40)
+    coords = torch.from_numpy(_rand_coords(rng, 2503, 2, shape)).to(cuda)
+    tiny = torch.from_numpy(_rand_coords(rng, 11, 1, (5, 8, 8))).to(cuda)
+    tables = [("submanifold", Fsp.build_subm_rulebook(coords, 2, list(shape), [3, 3, 3])),
+              ("stride 2", Fsp.build_sparse_rulebook(coords, 2, list(shape), [3, 3, 3], [2, 2, 2], [1, 1, 1])),
+              ("11 rows", Fsp.build_subm_rulebook(tiny, 1, [5, 8, 8], [3, 3, 3]))]
+    assert tables[0][1].n_out == 2503 and tables[1][1].n_out == 717 and tables[2][1].n_out == 11           # 2503 = 16 * 156 + 7, 717 = 16 * 44 + 13
+    if big:
+        n = 80_003
+        tables.append(("80 003 rows", Fsp.Rulebook(_synthetic_lidar_table(n, 27, cuda), None, None, None, n, n, False, [3, 3, 3])))
+    return tables
+
+
+def _epilogue_operands(rng, rb, cin, cout, cuda):
+    K = int(rb.nbr_out.shape[0])
+    x = rng.normal(size=(rb.n_in, cin)).astype(np.float32)
+    w = (rng.normal(size=(K, cin, cout)) * 1.5 / np.sqrt(0.4 * K * cin)).astype(np.float32)
+    nbr = rb.nbr_out.cpu().numpy()
+    return K, x, w, nbr, torch.from_numpy(x).to(cuda), torch.from_numpy(w).to(cuda), osp.conv_forward(x, nbr, w)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cin,cout", [(3, 16), (4, 16), (5, 7), (16, 16), (32, 64), (64, 64)])
+def test_hip_conv_fused_epilogue_of_the_plain_entry_vs_float64(cuda, hip_lib, cin, cout):
+    """sv_sparse_conv_gather_gemm with bias / scale + shift / residual / relu, each alone and together, against float64: C_in 3 and 4 take
+    k_spconv_small_cin, (5, 7) k_spconv_valu, the multiples of 16 k_spconv_rs -- the same conv_epilogue behind three different accumulator layouts."""
+    from seevcn_amd.spconv import functional as Fsp
+    rng = np.random.default_rng(100 * cin + cout)
+    for tag, rb in _epilogue_tables(cuda):
+        K, x, w, nbr, xd, wd, conv64 = _epilogue_operands(rng, rb, cin, cout, cuda)
+        wt = wd.permute(0, 2, 1).contiguous()
+        t, dev = _epilogue_terms(rng, rb.n_out, cout, cuda)
+        assert _ok(Fsp.gather_gemm(xd, rb.nbr_out, wt, rb.n_out).cpu().numpy(), conv64, name=f"plain entry {cin}->{cout}, {tag}, no epilogue")
+        for name, terms in EPILOGUES.items():
+            y = Fsp.gather_gemm(xd, rb.nbr_out, wt, rb.n_out, **_epilogue_kwargs(dev, terms))
+            assert _ok(y.cpu().numpy(), _epilogue_ref(conv64, t, terms), name=f"plain entry {cin}->{cout}, {tag}, epilogue {name}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cin,cout", [(16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128), (64, 192)])
+def test_hip_conv_fused_epilogue_of_the_planned_kernel_vs_float64(cuda, hip_lib, cin, cout):
+    """sv_sparse_conv_gather_gemm_planned with an epilogue: k_spconv_rs3 then leaves its whole-row store path for per-accumulator stores through
+    conv_epilogue, addressed over the launch's column block (grid.y = C_out / 64: 1, 2, 3 here), the table's total width and the -1 padding rows.
+    Every term alone and all together against float64, on tables with padding rows, with 4, 1 and (64 -> 64, 80 003 rows) 2 tiles per wave;
+    bit-identical to the plain entry with the same epilogue where that runs its MFMA kernel (C_out / 16 in 1, 2, 4, 8: include/seevcn_hip.h "same summation
+    order"; 192 columns go to its VALU kernel: tolerance); table_k_reversed; an input transform and an epilogue in one launch; the launch-list forms."""
+    from seevcn_amd import _lib
+    from seevcn_amd.spconv import chain, functional as Fsp
+    lib = hip_lib
+    rng = np.random.default_rng(100 * cin + cout)
+    for tag, rb in _epilogue_tables(cuda, big=(cin, cout) == (64, 64)):
+        K, x, w, nbr, xd, wd, conv64 = _epilogue_operands(rng, rb, cin, cout, cuda)
+        assert lib.sv_conv_mfma_kernel_applies(K, cin, cout, rb.n_in) == 1
+        plan = rb.plan("fwd", cin, cout)
+        assert plan is not None and plan[3] is False
+        want_g = 4 if cout <= 32 else (2 if rb.n_out > 80_000 else 1)
+        assert plan[2] == lib.sv_conv_tiles_per_wave(rb.n_out, cin, cout) == want_g, (tag, plan[2])
+        ff, _ = Fsp.fragment_cache.get(wd)
+        wt = wd.permute(0, 2, 1).contiguous()
+        t, dev = _epilogue_terms(rng, rb.n_out, cout, cuda)
+        plain_is_mfma = cout // 16 in (1, 2, 4, 8)
+        for name, terms in EPILOGUES.items():
+            kw = _epilogue_kwargs(dev, terms)
+            y = Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, cin, cout, **kw)
+            assert _ok(y.cpu().numpy(), _epilogue_ref(conv64, t, terms), name=f"planned {cin}->{cout}, {tag}, epilogue {name}")
+            y_plain = Fsp.gather_gemm(xd, rb.nbr_out, wt, rb.n_out, **kw)
+            if plain_is_mfma:
+                assert torch.equal(y, y_plain), (tag, name, "planned vs plain entry")
+            else:
+                assert _ok(y_plain.cpu().numpy(), _epilogue_ref(conv64, t, terms), name=f"plain entry {cin}->{cout}, {tag}, epilogue {name}")
+        terms = EPILOGUES["all"]
+        kw = _epilogue_kwargs(dev, terms)
+        y_all = Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, cin, cout, **kw)
+        # the launch-list forms unpack the same four pointers and relu from the operation record (csrc/sequencer.hip)
+        tp, tile_of, g, _rev = plan
+        y2 = torch.full_like(y_all, float("nan"))
+        chain._run([chain._row(chain.OP_CONV_PLANNED, i=(g, K, cin, cout, 1, 0), n=(rb.n_in, rb.n_out),
+                               p=(xd.data_ptr(), tp.rows.data_ptr(), tp.perm.data_ptr(), tp.masks_p.data_ptr(), tile_of.data_ptr(), ff.data_ptr(), y2.data_ptr(),
+                                  dev["bias"].data_ptr(), dev["scale"].data_ptr(), dev["shift"].data_ptr(), dev["residual"].data_ptr(), None))], "planned conv with an epilogue")
+        assert torch.equal(y2, y_all), (tag, "SV_OP_CONV_PLANNED")
+        y3 = torch.full_like(y_all, float("nan"))
+        chain._run([chain._row(chain.OP_CONV_PLAIN, i=(K, cin, cout, 1), n=(rb.n_in, rb.n_out),
+                               p=(xd.data_ptr(), rb.nbr_out.data_ptr(), wt.data_ptr(), y3.data_ptr(), dev["bias"].data_ptr(), dev["scale"].data_ptr(),
+                                  dev["shift"].data_ptr(), dev["residual"].data_ptr()))], "plain conv with an epilogue")
+        assert torch.equal(y3, Fsp.gather_gemm(xd, rb.nbr_out, wt, rb.n_out, **kw)), (tag, "SV_OP_CONV_PLAIN")
+        if tag != "submanifold":
+            continue
+        # table_k_reversed: offset k reads table entry K - 1 - k
+        y = Fsp.gather_gemm_planned(xd, (tp, tile_of, g, True), ff, rb.n_out, K, cin, cout, **kw)
+        assert _ok(y.cpu().numpy(), _epilogue_ref(osp.conv_forward(x, nbr[::-1], w), t, terms), name=f"planned {cin}->{cout}, reversed table, epilogue all")
+        # input transform (the BatchNorm + ReLU of the layer below applied on load) and output epilogue in one launch; an absent neighbour contributes 0
+        coef = np.concatenate([rng.uniform(0.5, 1.5, size=cin) * rng.choice([-1.0, 1.0], size=cin), rng.normal(size=cin) * 0.5]).astype(np.float32)
+        coef_d = torch.from_numpy(coef).to(cuda)
+        for in_relu in (1, 0):
+            xin = x.astype(np.float64) * coef[:cin] + coef[cin:]
+            xin = np.maximum(xin, 0.0) if in_relu else xin
+            lib.sv_conv_next_input_norm(coef_d.data_ptr(), in_relu)
+            y = Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, cin, cout, **kw)
+            assert _ok(y.cpu().numpy(), _epilogue_ref(osp.conv_forward(xin, nbr, w), t, terms), name=f"planned {cin}->{cout}, input transform (relu {in_relu}) + epilogue all")
+        assert torch.equal(Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, cin, cout, **kw), y_all)               # the transform was consumed
+
+
+@pytest.mark.gpu
+def test_hip_conv_epilogue_argument_errors(cuda, hip_lib):
+    """scale without shift (and shift without scale), and BatchNorm partial sums together with any epilogue term, are SV_ERR_ARG: nothing is launched."""
+    from seevcn_amd import _lib
+    from seevcn_amd.spconv import functional as Fsp, norm
+    rng = np.random.default_rng(7)
+    tag, rb = _epilogue_tables(cuda)[0]
+    K, x, w, nbr, xd, wd, conv64 = _epilogue_operands(rng, rb, 16, 16, cuda)
+    t, dev = _epilogue_terms(rng, rb.n_out, 16, cuda)
+    plan, (ff, _) = rb.plan("fwd", 16, 16), Fsp.fragment_cache.get(wd)
+    wt = wd.permute(0, 2, 1).contiguous()
+    for kw in (dict(scale=dev["scale"]), dict(shift=dev["shift"]), dict(scale=dev["scale"], bias=dev["bias"], relu=True)):
+        with pytest.raises(_lib.SeevcnHipError, match=r"\(code 1\).*scale and shift go together"):
+            Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, 16, 16, **kw)
+        with pytest.raises(_lib.SeevcnHipError, match=r"\(code 1\).*scale and shift go together"):
+            Fsp.gather_gemm(xd, rb.nbr_out, wt, rb.n_out, **kw)
+    partial = norm.partial_address(16, cuda)
+    for terms in EPILOGUES.values():
+        with pytest.raises(_lib.SeevcnHipError, match=r"\(code 1\).*plain epilogue only"):
+            Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, 16, 16, bn_partial=partial, **_epilogue_kwargs(dev, terms))
+    assert _ok(Fsp.gather_gemm_planned(xd, plan, ff, rb.n_out, K, 16, 16, bn_partial=partial).cpu().numpy(), conv64, name="plain epilogue with partial sums")
+
+
+@pytest.mark.gpu
+def test_hip_basic_block_inference_as_two_planned_launches_with_folded_batchnorm(cuda, hip_lib):
+    """What the epilogue is for: SparseBasicBlock(64, 64) in eval mode as two planned launches -- conv bias as `bias`, BatchNorm folded into
+    scale = g / sqrt(var + eps), shift = b - mean * scale, the identity as `residual`, relu -- equals the module's own eval forward and the float64 block."""
+    from functools import partial
+    from seeding import seeded_state_dict
+    import seevcn_amd.spconv as spconv
+    from seevcn_amd.pcdet.models.backbones_3d.spconv_backbone import SparseBasicBlock
+    from seevcn_amd.spconv import functional as Fsp
+    rng = np.random.default_rng(51)
+    shape = (9, 48, 40)
+    coords = torch.from_numpy(_rand_coords(rng, 2503, 2, shape)).to(cuda)
+    feats = rng.normal(size=(2503, 64)).astype(np.float32)
+    blk = SparseBasicBlock(64, 64, norm_fn=partial(torch.nn.BatchNorm1d, eps=1e-3, momentum=0.01), indice_key="res")
+    sd = seeded_state_dict(blk, seed=8)
+    blk.load_state_dict(sd)
+    blk = blk.to(cuda).eval()
+    x = torch.from_numpy(feats).to(cuda)
+    with torch.no_grad():
+        t_in = spconv.SparseConvTensor(x, coords, list(shape), 2)
+        want_module = blk(t_in).features
+        rb = t_in.indice_dict["res"]
+        plan = rb.plan("fwd", 64, 64)
+        assert plan is not None
+        y = x
+        for conv, bn, residual in ((blk.conv1, blk.bn1, None), (blk.conv2, blk.bn2, x)):
+            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+            shift = bn.bias - bn.running_mean * scale
+            ff, _ = Fsp.fragment_cache.get(conv.weight_kio())
+            y = Fsp.gather_gemm_planned(y, plan, ff, rb.n_out, 27, 64, 64, bias=conv.bias.detach(), scale=scale, shift=shift, residual=residual, relu=True)
+    ref = osp.basic_block_forward({"b." + k: v.numpy() for k, v in sd.items()}, feats.astype(np.float64), rb.nbr_out.cpu().numpy(), "b")
+    assert (ref == 0).mean() > 0.05 and (ref > 0).mean() > 0.05
+    assert _ok(y.cpu().numpy(), ref, name="basic block as two fused launches vs float64")
+    assert _ok(want_module.cpu().numpy(), ref, name="basic block module (eval) vs float64")
+    assert _ok(y.cpu().numpy(), want_module.cpu().numpy().astype(np.float64), name="basic block as two fused launches vs the module")
