@@ -272,7 +272,11 @@ int sv_conv_weight_fragments_batch(const void* descs_device, int n_layers, int64
  * separate pass (fused multiply-add, then max): consumers see bit-identical values; absent neighbours contribute 0.  coef = NULL clears it.
  * Entry points that cannot apply it (the plain k-major conv, non-MFMA weight-gradient shapes) fail with SV_ERR_ARG. */
 int sv_conv_next_input_norm(const float* coef, int relu);
-/* table_k_reversed: offset k reads table entry K-1-k (a submanifold table serving its own data gradient, no flipped copy). */
+/* table_k_reversed: offset k reads table entry K-1-k (a submanifold table serving its own data gradient, no flipped copy).
+ * Epilogue (bias, scale + shift, residual, relu as for sv_sparse_conv_gather_gemm; per element: add bias, ONE fused multiply-add -- the instruction of
+ * sv_batchnorm_apply, so a folded eval-mode BatchNorm gives the bits of the separate pass --, add residual, max with 0): when Y and every term given are
+ * 16-byte aligned the launch stores whole rows (16 bytes per lane, the residual read the same way), otherwise 4 bytes per accumulator; the values are
+ * the same.  residual must not alias Y (not checked: a residual that overlaps Y at a shifted address is read after other lanes wrote it).  Rows the table pads with (-1) are neither read nor written. */
 int sv_sparse_conv_gather_gemm_planned(const float* X, int64_t n_src, const int32_t* table_rows, const int32_t* perm, const int32_t* masks_p,
                                        const int32_t* tile_of, int tiles_per_wave,
                                        const float* wfrag, float* Y, int64_t n_rows, int K, int Kd, int Nc, const float* bias,
@@ -601,11 +605,13 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
  *                       n = rows; i = channels, relu, world
  *                       (SyncBatchNorm: a list is CUT behind a *_LOCAL operation, the caller all-gathers `sums` between the ranks, and the next list
  *                       starts with the matching *_GLOBAL operation)
+ *   SV_OP_BN_EVAL_COEF_BATCH   sv_batchnorm_eval_coef_batch: p0 = HOST address of the job table (read before sv_run_ops returns); i = n_jobs
  * Input transform: SV_OP_CONV_PLANNED with p12 = coef (2, Kd) and i6 = relu, SV_OP_WGRAD[_DEFERRED] with p6 = coef (2, Cin) and i4 = relu read their
  * X through sv_conv_next_input_norm(coef, relu): X is then the RAW output of the convolution below, its BatchNorm (+ReLU) is applied as the rows are
  * gathered, and the normalised activation tensor is never written.
  * Used by seevcn_amd/spconv/chain.py: the forward and the backward of a conv -> BatchNorm -> ReLU chain (VoxelBackBone8x, spconv_backbone.py:128-180)
- * as two calls inside one autograd node. */
+ * as two calls inside one autograd node; and the eval-mode forward of both 3-D backbones as one call (SV_OP_BN_EVAL_COEF_BATCH + one conv per layer,
+ * BatchNorm, conv bias, identity and ReLU in the convs' epilogues). */
 #define SV_OP_WORDS 32
 #define SV_OP_CONV_PLANNED 1
 #define SV_OP_CONV_PLAIN 2
@@ -620,6 +626,7 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
 #define SV_OP_BN_FINALIZE_GLOBAL 12
 #define SV_OP_BN_BWD_SUMS_LOCAL 13
 #define SV_OP_BN_BWD_APPLY_GLOBAL 14
+#define SV_OP_BN_EVAL_COEF_BATCH 15
 int sv_run_ops(const int64_t* ops, int n_ops, void* stream);
 /* measurement form: events around every operation on `stream`, the call waits for the stream and writes each operation's elapsed milliseconds to
  * ms[0 .. n_ops) (bench.py's roofline block times the conv launches of the step's own launch lists with it) */
@@ -652,6 +659,12 @@ int sv_batchnorm_relu_forward_partial(const float* x, int64_t n, int channels, c
 int sv_batchnorm_finalize_forward(const float* x /* NULL: partials in scratch; else the statistics pass over x runs first */, int64_t n, int channels, const float* gamma, const float* beta, float* running_mean, float* running_var,
                                   float momentum, float eps, void* scratch, int n_partials, float* coef, float* save_mean, float* save_invstd,
                                   int64_t* num_batches_tracked, void* stream);
+/* Eval-mode coefficients of n_jobs BatchNorm layers in one launch: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale -- what
+ * F.batch_norm(..., training=False) inside post_act_block / SparseBasicBlock (spconv_backbone.py:8-66) derives from the running statistics on every call,
+ * and bit for bit what sv_batchnorm_relu_forward(training = 0) computes for its own elementwise pass.  jobs_host: n_jobs rows of 8 int64 = {gamma | 0,
+ * beta | 0, running_mean, running_var, coef_out (2 * C floats: scale | shift, 16-byte aligned), C, eps (bits of a double), 0} (device addresses; the table
+ * itself is host memory, read before the call returns).  The consumers are the epilogues of the convolutions (scale = coef_out, shift = coef_out + C). */
+int sv_batchnorm_eval_coef_batch(const int64_t* jobs_host, int n_jobs, void* stream);
 /* y = [relu](x * scale + shift), coef (2, channels) = scale | shift: the elementwise pass on its own */
 int sv_batchnorm_apply(const float* x, int64_t n, int channels, const float* coef, int relu, float* y, void* stream);
 int sv_batchnorm_relu_backward(const float* x, const float* dy, int64_t n, int channels, const float* gamma, const float* beta,

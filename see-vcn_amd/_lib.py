@@ -180,6 +180,7 @@ SIGNATURES = {
     "sv_batchnorm_relu_backward_partial": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
     "sv_conv_next_input_norm": (c_i, [c_p, c_i]),
     "sv_batchnorm_finalize_forward": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_batchnorm_eval_coef_batch": (c_i, [c_p, c_i, c_p]),
     "sv_batchnorm_apply": (c_i, [c_p, c_i64, c_i, c_p, c_i, c_p, c_p]),
     "sv_batchnorm_stats_local": (c_i, [c_p, c_i64, c_i, c_p, c_i, c_p, c_p]),
     "sv_batchnorm_finalize_global": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),

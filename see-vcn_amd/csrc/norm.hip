@@ -6,6 +6,8 @@
 // it took 67-71 us instead of 12 + 5; with write-through (sc1) partials, a drained arrival counter and an acquire in the last arriver only
 // it took 30-34 us -- one workgroup reading 1024 x 2 x C partials from memory is slower than C workgroups doing it in a launch of their
 // own -- and one test saw a stale partial at 4 workgroups per CU.  A kernel boundary costs 1.5 us here; three launches it is.)
+#include <string.h>
+
 #include "common.h"
 
 #include "norm.h"
@@ -288,13 +290,71 @@ static void bn_backward_tail(const BnArgs& a, hipStream_t st) {
 }
 
 // eval mode: per-channel scale/shift from the running statistics (one tiny launch), then the same apply kernel
+// channel c of coef (2, C) = scale | shift from the running statistics: the ONE place this arithmetic is written, so that the module path
+// (k_bn_eval_coef) and the eval chain (k_bn_eval_coef_batch) hand the same bits to the kernels that apply them
+__device__ __forceinline__ void bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                                             float* coef, int C, int c) {
+  const float invstd = 1.f / sqrtf(running_var[c] + eps);
+  const float gm = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
+  coef[c] = invstd * gm;
+  coef[C + c] = bb - running_mean[c] * invstd * gm;
+}
+
 __global__ void k_bn_eval_coef(BnArgs a) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= a.C) return;
-  const float invstd = 1.f / sqrtf(a.running_var[c] + a.eps);
-  const float gm = a.gamma ? a.gamma[c] : 1.f, bb = a.beta ? a.beta[c] : 0.f;
-  a.coef[c] = invstd * gm;
-  a.coef[a.C + c] = bb - a.running_mean[c] * invstd * gm;
+  bn_eval_coef(a.gamma, a.beta, a.running_mean, a.running_var, a.eps, a.coef, a.C, c);
+}
+
+// The same for every BatchNorm of a network in one launch (the eval chain of seevcn_amd/spconv/chain.py): one workgroup per layer, the layers'
+// descriptors in the kernel's argument block.
+struct BnEvalCoefJob {
+  const float *gamma, *beta, *running_mean, *running_var;
+  float* coef;
+  int C;
+  float eps;
+};
+constexpr int BN_EVAL_JOBS = 64;
+struct BnEvalCoefBatch {
+  BnEvalCoefJob j[BN_EVAL_JOBS];
+};
+static_assert(sizeof(BnEvalCoefBatch) <= 3900, "kernel argument block");
+
+__global__ __launch_bounds__(128) void k_bn_eval_coef_batch(BnEvalCoefBatch b) {
+  const BnEvalCoefJob& J = b.j[blockIdx.x];
+  for (int c = threadIdx.x; c < J.C; c += 128) bn_eval_coef(J.gamma, J.beta, J.running_mean, J.running_var, J.eps, J.coef, J.C, c);
+}
+
+// Eval-mode coefficients of n_jobs BatchNorm layers (what F.batch_norm(..., training=False) inside post_act_block / SparseBasicBlock derives from the
+// running statistics on every call; reference spconv_backbone.py:8-66) in ONE launch per BN_EVAL_JOBS layers (the job table travels in the kernel's argument block).  jobs_host: n_jobs rows of 8 int64 =
+// {gamma | 0, beta | 0, running_mean, running_var, coef_out, C, eps (bits of a double), 0}.
+extern "C" int sv_batchnorm_eval_coef_batch(const int64_t* jobs_host, int n_jobs, void* stream) {
+  SV_CHECK_ARG(n_jobs >= 0 && (jobs_host || n_jobs == 0), "sv_batchnorm_eval_coef_batch: bad arguments");
+  if (n_jobs == 0) return SV_OK;
+  for (int q = 0; q < n_jobs; ++q) {               // every job is checked before the first launch: an argument error launches nothing
+    const int64_t* r = jobs_host + 8 * (size_t)q;
+    SV_CHECK_ARG(r[2] && r[3] && r[4], "sv_batchnorm_eval_coef_batch: job %d: null pointer", q);
+    SV_CHECK_ARG(r[5] >= 1 && r[5] <= BN_MAX_C, "sv_batchnorm_eval_coef_batch: job %d: 1..%d channels (got %lld)", q, BN_MAX_C, (long long)r[5]);
+    SV_CHECK_ARG((uintptr_t)r[4] % 16 == 0, "sv_batchnorm_eval_coef_batch: job %d: coef_out must be 16-byte aligned", q);
+  }
+  hipStream_t st = sv_stream(stream);
+  for (int q0 = 0; q0 < n_jobs; q0 += BN_EVAL_JOBS) {
+    BnEvalCoefBatch b;
+    const int nb = n_jobs - q0 < BN_EVAL_JOBS ? n_jobs - q0 : BN_EVAL_JOBS;
+    for (int q = 0; q < nb; ++q) {
+      const int64_t* r = jobs_host + 8 * (size_t)(q0 + q);
+      BnEvalCoefJob& J = b.j[q];
+      J.gamma = reinterpret_cast<const float*>((uintptr_t)r[0]), J.beta = reinterpret_cast<const float*>((uintptr_t)r[1]);
+      J.running_mean = reinterpret_cast<const float*>((uintptr_t)r[2]), J.running_var = reinterpret_cast<const float*>((uintptr_t)r[3]);
+      J.coef = reinterpret_cast<float*>((uintptr_t)r[4]);
+      double eps;
+      memcpy(&eps, &r[6], sizeof eps);
+      J.C = (int)r[5], J.eps = (float)eps;
+    }
+    hipLaunchKernelGGL(k_bn_eval_coef_batch, dim3(nb), dim3(128), 0, st, b);
+  }
+  SV_LAUNCH_CHECK();
+  return SV_OK;
 }
 
 static int bn_wgs(int64_t n, int C) {

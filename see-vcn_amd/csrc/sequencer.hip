@@ -171,6 +171,9 @@ static int run_ops(const int64_t* ops, int n_ops, void* stream, void* side_strea
                                                 ptr_of<const float>(p[3]), ptr_of<const float>(p[4]), ptr_of<const float>(p[5]), (int)i[1],
                                                 ptr_of<const double>(p[7]), (int)i[2], ptr_of<const double>(p[8]), ptr_of<void>(p[6]), ptr_of<float>(p[9]), stream);
         break;
+      case SV_OP_BN_EVAL_COEF_BATCH:
+        rc = sv_batchnorm_eval_coef_batch(ptr_of<const int64_t>(p[0]), (int)i[0], stream);      // p0: the HOST job table
+        break;
       case SV_OP_WGRAD:
         if (st_side && (rc = fork_side()) != SV_OK) break;
         if (p[6]) sv_conv_next_input_norm(ptr_of<const float>(p[6]), (int)i[4]);

@@ -69,7 +69,7 @@ struct ConvArgs {
 
 __device__ __forceinline__ float conv_epilogue(float v, int col, int64_t row, const ConvArgs& a) {
   if (a.bias) v += a.bias[col];
-  if (a.scale) v = v * a.scale[col] + a.shift[col];
+  if (a.scale) v = bn_act(v, a.scale[col], a.shift[col]);       // the fused multiply-add of k_bn_apply_fwd: a folded BatchNorm gives the separate pass's bits
   if (a.residual) v += a.residual[row * a.Nc + col];
   if (a.relu) v = fmaxf(v, 0.f);
   return v;
@@ -1273,6 +1273,7 @@ struct PlanView {
   int prio;                 // SEEVCN_RS3_PRIO (A/B): 1 = s_setprio 3 for a pass's prologue, 2 = for its epilogue too; the main loop runs at 0
   const float* in_coef;     // FIN instances: (2, Kd) scale | shift applied to every gathered X value (+ ReLU when in_relu); see InNorm
   int in_relu;
+  int epi_rows;             // a launch with an epilogue stores whole rows through the staging tile (its terms and Y are 16-byte aligned); 0: per accumulator
 };
 
 // DBG: 0 production; 1 the measurement switches of PlanView::debug (+ trace); 2 per-wave trace only (the production loop + a few s_memtime per pass)
@@ -1782,7 +1783,47 @@ __global__ __launch_bounds__(256, PL_WAVES_PER_SIMD) void k_spconv_rs3(ConvArgs 
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // the next pass refills the index block
+  } else if (pv.epi_rows) {
+    // Whole rows out with an epilogue (every launch of an eval-mode forward): the same staging tile, then a lane applies the epilogue to its 16-byte
+    // piece -- bias / scale / shift of its four columns as one float4 each, the residual row piece as one 16-byte load -- and stores it.  Per
+    // element the operations of conv_epilogue in its order (add, one fused multiply-add, add, max): the bits of the per-accumulator form below.
+    // Padding rows (row < 0) are neither read nor written.
+    float* T = reinterpret_cast<float*>(&s_idx[0][0]);
+    constexpr int TP = NT * 16 + 4;
+    constexpr int C4N = NT * 4;                                       // 16-byte pieces per row
+#pragma unroll
+    for (int g = 0; g < RS_G; ++g) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T[(kk_e * 4 + r) * TP + t * 16 + li_e] = acc[g][t][r];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+      for (int i = 0; i < (16 * C4N + 63) / 64; ++i) {
+        const int f = lane_e + 64 * i, rw = f / C4N, c4 = f % C4N;
+        if (16 * C4N % 64 == 0 || f < 16 * C4N) {
+          const int64_t row = s_idx[RS3_KMAX][g * 16 + rw];
+          if (row >= 0) {
+            const int col = col_tile0 * 16 + c4 * 4;
+            f32x4 v = *reinterpret_cast<const f32x4*>(T + rw * TP + c4 * 4);
+            if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + col);
+            if (a.scale) {
+              const f32x4 sc = *reinterpret_cast<const f32x4*>(a.scale + col), sh = *reinterpret_cast<const f32x4*>(a.shift + col);
+              v = (f32x4){bn_act(v[0], sc[0], sh[0]), bn_act(v[1], sc[1], sh[1]), bn_act(v[2], sc[2], sh[2]), bn_act(v[3], sc[3], sh[3])};
+            }
+            if (a.residual) v += *reinterpret_cast<const f32x4*>(a.residual + row * pv.nc_total + col);
+            if (a.relu) v = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+            *reinterpret_cast<f32x4*>(a.Y + row * pv.nc_total + col) = v;
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // the next pass refills the index block
   } else {
+    // epilogue terms that are not 16-byte aligned (or SEEVCN_RS3_EPI_ROWS=0, A/B): straight from the accumulators, 4-byte accesses
 #pragma unroll
     for (int g = 0; g < RS_G; ++g)
 #pragma unroll
@@ -1942,6 +1983,9 @@ static int conv_planned(const float* X, int64_t n_src, const int32_t* table_rows
   pv.prio = prio;
   pv.trace = g_conv_trace;
   pv.in_coef = in.coef, pv.in_relu = in.relu;
+  // SEEVCN_RS3_EPI_ROWS=0 (A/B): epilogue launches store per accumulator, as they did before the whole-row form existed
+  static const int epi_rows = getenv("SEEVCN_RS3_EPI_ROWS") ? atoi(getenv("SEEVCN_RS3_EPI_ROWS")) : 1;
+  pv.epi_rows = (epi_rows && (((uintptr_t)Y | (uintptr_t)bias | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)residual) & 15) == 0) ? 1 : 0;
   SV_CHECK_ARG(!in.coef || (!pv.debug && !pv.trace && (uintptr_t)in.coef % 16 == 0), "sparse_conv (planned): an input transform needs a production instance and 16-byte aligned coefficients");
   const int nc_blk = Nc > 64 ? 64 : Nc;
   const dim3 grid((unsigned)(PL_REGIONS * PL_REGION_WAVES / 4), (unsigned)(Nc / nc_blk));

@@ -56,6 +56,9 @@ class SparseBasicBlock(spconv.SparseModule):
         return out
 
 
+chain.register_residual_block(SparseBasicBlock)         # the eval list (chain.flatten_eval) takes blocks whose forward is the one above
+
+
 class _BackBone8xBase(nn.Module):
     def _finish(self, batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out):
         # same keys as the reference (spconv_backbone.py:159-178)
@@ -80,6 +83,21 @@ class _BackBone8xBase(nn.Module):
             self.__dict__['_seevcn_chain'] = hit
         return hit[1]
 
+    def _eval_entries(self):
+        """The stages as one list of eval entries, one per convolution (chain.flatten_eval: residual blocks and conv biases included), or None; the
+        same taps and the same cache key as _chain_blocks."""
+        from ....spconv import conv as sconv
+        epoch = sconv._registration_epoch[0]
+        hit = self.__dict__.get('_seevcn_eval_chain')
+        if hit is None or hit[0] != epoch:
+            entries = chain.flatten_eval([self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out])
+            if entries is not None:
+                for e in entries[:len(chain.flatten_eval([self.conv_input]) or [])]:
+                    e.tap = False                                     # conv_input feeds conv1 only
+            hit = (epoch, entries)
+            self.__dict__['_seevcn_eval_chain'] = hit
+        return hit[1]
+
     def forward_stages(self, batch_dict):
         """forward() as a generator that yields between the backbone's stages (a caller with other work to enqueue in between, bench.py, steps
         through it); the value of the StopIteration is the batch_dict."""
@@ -96,6 +114,10 @@ class _BackBone8xBase(nn.Module):
         blocks = self._chain_blocks()
         if self.training and chain.applicable(blocks, input_sp_tensor):
             x_conv1, x_conv2, x_conv3, x_conv4, out = chain.run_chain(blocks, input_sp_tensor)
+            return self._finish(batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out)
+        # eval without gradients (both backbones, residual blocks included): one launch list, every BatchNorm folded into its conv's epilogue
+        elif not self.training and chain.eval_applicable(self._eval_entries(), input_sp_tensor):
+            x_conv1, x_conv2, x_conv3, x_conv4, out = chain.run_eval_chain(self._eval_entries(), input_sp_tensor)
             return self._finish(batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out)
         x = self.conv_input(input_sp_tensor)
         x_conv1 = self.conv1(x)

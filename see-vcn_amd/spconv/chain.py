@@ -1,12 +1,20 @@
-"""A chain of [sparse conv -> BatchNorm1d -> ReLU] blocks as ONE autograd node over the launch-list executor (sv_run_ops, csrc/sequencer.hip).
+"""Chains of sparse conv blocks over the launch-list executor (sv_run_ops, csrc/sequencer.hip): the training step of a [sparse conv -> BatchNorm1d ->
+ReLU] chain as ONE autograd node, and the eval-mode forward of both 3-D backbones as one list without an autograd node.
 
-The reference's VoxelBackBone8x.forward (detector3d/pcdet/models/backbones_3d/spconv_backbone.py:128-180) is 13 such blocks; through the module
+The reference's VoxelBackBone8x.forward (detector3d/pcdet/models/backbones_3d/spconv_backbone.py:128-180) is 12 such blocks; through the module
 tree each block costs the host an autograd node, three output allocations and two or three ctypes calls per direction (2.2 ms of Python per
 step for 4.0 ms of GPU time on the bench workload).  Here the forward of the whole chain is written as one list of operations -- every
 argument is known before the first kernel runs: the rulebooks and plans are built ahead, the activations are slices of one allocation -- and
 enqueued with one call; the backward (BatchNorm backward, weight gradient, data gradient per block, last to first) likewise.  Same kernels,
 same arithmetic, same parameters and running statistics as the per-module path (SparseSequential), which stays the fallback for anything
-this does not take (eval mode, hooks, a conv bias, a layer without a plan for its data gradient, residual blocks)."""
+this does not take (hooks, a conv bias or residual blocks in training mode, a layer without a plan for its data gradient).
+
+Eval mode (flatten_eval / eval_applicable / run_eval_chain; tools/test.py of the reference, the post_processing + recall path): the list is one
+launch that makes every BatchNorm's (scale, shift) from its running statistics (SV_OP_BN_EVAL_COEF_BATCH) and one convolution per layer whose
+epilogue applies conv bias, folded BatchNorm, the identity of a residual block (SparseBasicBlock, spconv_backbone.py:30-66) and the ReLU -- every
+activation is written once, normalised.  It stands down (module tree) when gradients are enabled, a norm is in training mode or keeps no running
+statistics, the input is empty, anything walked carries a hook, a residual block has a downsample module or a forward of its own, or SEEVCN_CHAIN=0 /
+SEEVCN_EVAL_CHAIN=0."""
 import os
 import struct
 
@@ -41,8 +49,11 @@ _wgrad_stream = {}
 # tensor and one launch per block less; the values a consumer sees are bit for bit those of the separate pass.  Tensors that leave the chain (taps) are
 # made when somebody reads them (LazyTap), the last block's in the list.  0: every block writes its normalised output (A/B runs, tests).
 BN_FOLD = os.environ.get("SEEVCN_BN_FOLD", "1") != "0"
+# 0: an eval-mode backbone forward walks the module tree (conv, BatchNorm coefficients and the elementwise pass as launches of their own) instead of
+# running as one launch list with the BatchNorms folded into the convs' epilogues (run_eval_chain) -- A/B runs, tests.  Bitwise the same outputs.
+EVAL_CHAIN_OFF = os.environ.get("SEEVCN_EVAL_CHAIN", "1") == "0"
 OP_CONV_PLANNED, OP_CONV_PLAIN, OP_BN_FWD, OP_BN_BWD, OP_WGRAD, OP_DGRAD_PLANNED_BN, OP_WGRAD_DEFERRED, OP_BN_FINALIZE, OP_BN_APPLY = 1, 2, 3, 5, 6, 7, 8, 9, 10
-OP_BN_STATS_LOCAL, OP_BN_FINALIZE_GLOBAL, OP_BN_BWD_SUMS_LOCAL, OP_BN_BWD_APPLY_GLOBAL = 11, 12, 13, 14
+OP_BN_STATS_LOCAL, OP_BN_FINALIZE_GLOBAL, OP_BN_BWD_SUMS_LOCAL, OP_BN_BWD_APPLY_GLOBAL, OP_BN_EVAL_COEF_BATCH = 11, 12, 13, 14, 15
 WORDS = 32
 
 
@@ -427,3 +438,172 @@ def run_chain(blocks, x):
         else:
             res.append(LazyTap(f, coefs.pop(0), b.relu, rb.out_indices, rb.out_shape, x.batch_size, x.grid, x.indice_dict))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- eval mode
+_residual_blocks = []
+
+
+def register_residual_block(cls):
+    """cls: a residual block class (SparseBasicBlock) whose OWN forward is relu(bn2(conv2(relu(bn1(conv1(x))))) + x) when its downsample is None;
+    flatten_eval takes instances whose forward is that very function (a subclass with a forward of its own is declined)."""
+    if cls not in _residual_blocks:
+        _residual_blocks.append(cls)
+    return cls
+
+
+class EvalEntry:
+    """One convolution of an eval list and what its epilogue applies: (conv, bn, relu, residual_from, tap).  residual_from: index of the entry whose
+    output is added before the ReLU (a residual block's identity), -1 for the chain's input, None for none; tap: the output is returned by the chain."""
+    __slots__ = ("conv", "bn", "relu", "residual_from", "tap", "K", "cin", "cout")
+
+    def __init__(self, conv, bn, relu, residual_from, tap):
+        self.conv, self.bn, self.relu, self.residual_from, self.tap = conv, bn, bool(relu), residual_from, tap
+        self.K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
+        self.cin, self.cout = conv.in_channels, conv.out_channels
+
+    def __iter__(self):
+        return iter((self.conv, self.bn, self.relu, self.residual_from, self.tap))
+
+
+def _is_residual_block(m):
+    from .conv import SparseConvolution
+    if not any(isinstance(m, cls) and type(m).forward is cls.forward for cls in _residual_blocks):
+        return False
+    c1, c2 = getattr(m, "conv1", None), getattr(m, "conv2", None)
+    return (isinstance(c1, SparseConvolution) and isinstance(c2, SparseConvolution) and c1.subm and c2.subm and c1.indice_key is not None
+            and c1.indice_key == c2.indice_key and c1.kernel_size == c2.kernel_size and c1.in_channels == c2.out_channels
+            and c1.out_channels == c2.in_channels and getattr(m, "downsample", 0) is None and type(getattr(m, "relu", None)) is torch.nn.ReLU
+            and type(getattr(m, "bn1", None)) in _EVAL_NORMS and type(getattr(m, "bn2", None)) in _EVAL_NORMS)
+
+
+_EVAL_NORMS = (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm)
+
+
+def flatten_eval(stages):
+    """stages: the backbone's stages in execution order (SparseSequential each).  -> BlockList of EvalEntry, one per convolution, or None when a stage is
+    anything but (SparseConvolution [with or without bias], BatchNorm1d | SyncBatchNorm, ReLU) triples and registered residual blocks without a
+    downsample.  The last entry of every stage is a tap."""
+    from .conv import SparseConvolution
+    from .modules import SparseSequential
+    entries = BlockList()
+    walked = []
+
+    def walk(m, out):
+        walked.append(m)
+        for child in m._modules.values():
+            if isinstance(child, SparseSequential):
+                walk(child, out)
+            else:
+                walked.append(child)
+                out.append(child)
+
+    for stage in stages:
+        if not isinstance(stage, SparseSequential):
+            return None
+        mods = []
+        walk(stage, mods)
+        j, n0 = 0, len(entries)
+        while j < len(mods):
+            m = mods[j]
+            if isinstance(m, SparseConvolution):
+                if j + 2 >= len(mods) or type(mods[j + 1]) not in _EVAL_NORMS or type(mods[j + 2]) is not torch.nn.ReLU:
+                    return None
+                entries.append(EvalEntry(m, mods[j + 1], True, None, False))
+                j += 3
+            elif _is_residual_block(m):
+                walked.extend(c for c in m._modules.values() if c is not None)      # a downsample set and cleared again stays registered as None
+                identity = len(entries) - 1                                         # -1: the block reads the chain's input
+                entries.append(EvalEntry(m.conv1, m.bn1, True, None, False))
+                entries.append(EvalEntry(m.conv2, m.bn2, True, identity, False))
+                j += 1
+            else:
+                return None
+        if len(entries) == n0:
+            return None
+        entries[-1].tap = True
+    entries.walked = tuple(walked)
+    return entries
+
+
+def eval_applicable(entries, x):
+    """The eval list takes these entries on x now: SEEVCN_CHAIN and SEEVCN_EVAL_CHAIN not 0, gradients disabled, fp32 CUDA features with at least one row,
+    no hooks on anything walked, every norm in eval mode with running statistics on a channel count the fused BatchNorm kernels take (what the module
+    path would run, so both give the same bits), every rulebook in x's indice_dict with the conv's kernel size and the row counts of a chain."""
+    if CHAIN_OFF or EVAL_CHAIN_OFF or entries is None or torch.is_grad_enabled():
+        return False
+    f = x.features
+    if not (f.is_cuda and f.dtype == torch.float32 and f.dim() == 2 and f.shape[0] >= 1 and f.shape[1] == entries[0].cin):
+        return False
+    if any(_has_hooks(m) for m in getattr(entries, 'walked', ())):
+        return False
+    rows = [f.shape[0]]                                                              # rows[k + 1]: rows of entry k's output; rows[0]: of the input
+    for e in entries:
+        bn, w = e.bn, e.conv.weight
+        if (type(bn) not in _EVAL_NORMS or bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None
+                or bn.num_features != e.cout or not norm.channels_fusable(e.cout) or bn.momentum is None or not bn.running_mean.is_cuda):
+            return False
+        if not (w.is_cuda and w.dtype == torch.float32) or e.conv.indice_key is None:
+            return False
+        rb = x.indice_dict.get(e.conv.indice_key)
+        if rb is None or rb.ksize != e.conv.kernel_size or rb.n_in != rows[-1] or rb.n_out < 1:
+            return False
+        if e.residual_from is not None and rows[e.residual_from + 1] != rb.n_out:
+            return False
+        rows.append(rb.n_out)
+    return True
+
+
+def run_eval_chain(entries, x):
+    """x: SparseConvTensor at the chain's input with every rulebook prebuilt (and the weight fragments refreshed).  -> list of SparseConvTensor, one per
+    tap, in order.  ONE sv_run_ops call: [all BatchNorm coefficients] + one convolution per entry; nothing is saved, parameters and buffers are only read.
+    Only the taps' features outlive the call."""
+    dev = x.features.device
+    features = x.features.contiguous()
+    rulebooks = [x.indice_dict[e.conv.indice_key] for e in entries]
+    L = len(entries)
+    # two allocations (all offsets multiples of 4 floats: 16-byte aligned pieces): the taps' outputs, which leave with the result, and everything that dies
+    # with this call -- every entry's (scale | shift) and the outputs nobody outside reads (freed to torch's allocator on the stream the list runs on)
+    t_total, w_total, c_offs, y_offs = 0, 0, [], []
+    for e in entries:
+        c_offs.append(w_total)
+        w_total += 2 * e.cout
+    for e, rb in zip(entries, rulebooks):
+        if e.tap:
+            y_offs.append(t_total)
+            t_total += rb.n_out * e.cout
+        else:
+            y_offs.append(w_total)
+            w_total += rb.n_out * e.cout
+    arena = torch.empty((t_total,), dtype=torch.float32, device=dev)
+    work = torch.empty((w_total,), dtype=torch.float32, device=dev)
+    y_addr = [(arena if e.tap else work).data_ptr() + 4 * y_offs[k] for k, e in enumerate(entries)]
+    base = work.data_ptr()
+    jobs = np.zeros((L, 8), dtype=np.int64)
+    rows = [_row(OP_BN_EVAL_COEF_BATCH, i=(L,), p=(jobs.ctypes.data,))]               # the table is host memory, read inside the call below
+    keep = []
+    x_ptr, n_src = features.data_ptr(), features.shape[0]
+    for k, (e, rb) in enumerate(zip(entries, rulebooks)):
+        bn, conv = e.bn, e.conv
+        o_coef, o_y = base + 4 * c_offs[k], y_addr[k]
+        jobs[k, :7] = (0 if bn.weight is None else bn.weight.data_ptr(), 0 if bn.bias is None else bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                       bn.running_var.data_ptr(), o_coef, e.cout, _bits(bn.eps))
+        bias = None if conv.bias is None else conv.bias.data_ptr()
+        res = None if e.residual_from is None else (features.data_ptr() if e.residual_from < 0 else y_addr[e.residual_from])
+        wk = conv.weight_kio_nograd()
+        plan = rb.plan_addrs("fwd", e.cin, e.cout)
+        if plan is not None:
+            a_rows, a_perm, a_masks_p, a_tiles, g, rev = plan
+            ff, _ = Fsp.fragment_cache.get(wk)
+            rows.append(_row(OP_CONV_PLANNED, i=(g, e.K, e.cin, e.cout, int(e.relu), int(bool(rev))), n=(n_src, rb.n_out),
+                             p=(x_ptr, a_rows, a_perm, a_masks_p, a_tiles, ff.data_ptr(), o_y, bias, o_coef, o_coef + 4 * e.cout, res, None)))
+        else:
+            wt = wk.detach().permute(0, 2, 1).contiguous()                           # (K, C_out, C_in): the 3/4/5-channel input layer only
+            keep.append(wt)
+            rows.append(_row(OP_CONV_PLAIN, i=(e.K, e.cin, e.cout, int(e.relu)), n=(n_src, rb.n_out),
+                             p=(x_ptr, rb.addr("nbr_out"), wt.data_ptr(), o_y, bias, o_coef, o_coef + 4 * e.cout, res)))
+        x_ptr, n_src = o_y, rb.n_out
+    _run(rows, "sv_run_ops (eval chain)")
+    return [SparseConvTensor(arena[y_offs[k]:y_offs[k] + rb.n_out * e.cout].view(rb.n_out, e.cout), rb.out_indices, rb.out_shape, x.batch_size, x.grid,
+                             x.indice_dict)
+            for k, (e, rb) in enumerate(zip(entries, rulebooks)) if e.tap]

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the sparse-conv layers of VoxelBackBone8x on the bench workload (16 KITTI-shaped scenes).
-Prints per-layer forward / backward-data / weight-grad times (HIP events) with pairs and achieved TFLOP/s."""
+Prints per-layer forward / backward-data / weight-grad times (HIP events) with pairs and achieved TFLOP/s.
+--epilogue: per planned layer the forward with scale+shift+relu and with all epilogue terms (bias, scale+shift, residual, relu) next to the bare
+conv -- the launches of an eval-mode forward; SEEVCN_RS3_EPI_ROWS=0 gives the per-accumulator store path of the same build, and two library
+builds are compared with tools/build_variant.sh + tools/ab_libs.sh."""
 import os
 import sys
 
@@ -46,6 +49,7 @@ def timeit(fn, reps=10):
 
 
 def main():
+    epilogue = "--epilogue" in sys.argv[1:]
     dev = torch.device("cuda:0")
     bs = int(os.environ.get("BS", "16"))
     pts, _ = synth.make_scene_batch(bs, seed=2000, n_az=int(os.environ.get("N_AZ", "384")))
@@ -60,6 +64,8 @@ def main():
     shape = [41, 1600, 1408]
     layers = [("subm1", 16, 16), ("spconv2", 16, 32), ("subm2", 32, 32), ("spconv3", 32, 64), ("subm3", 64, 64),
               ("spconv4", 64, 64), ("subm4", 64, 64), ("down", 64, 128)]
+    if epilogue:                                  # the 128 -> 128 residual layers of VoxelResBackBone8x run on a table of this level
+        layers.insert(7, ("subm4", 128, 128))
     c = coords
     tot = 0.0
     only = os.environ.get("LAYER")
@@ -103,6 +109,17 @@ def main():
             else:
                 ff = Fsp.fragment_cache.get(w)[0]
                 tf = timeit(with_in(lambda: Fsp.gather_gemm_planned(x, pf, ff, rb.n_out, K, cin, cout)))
+        if epilogue and pf is not None:
+            bias, shift = torch.randn(cout, device=dev), torch.randn(cout, device=dev)
+            scale, res = torch.rand(cout, device=dev) + 0.5, torch.randn(rb.n_out, cout, device=dev)
+            reps = int(os.environ.get("EPI_REPEATS", "3"))
+            ff = Fsp.fragment_cache.get(w)[0]
+            t_bare = [timeit(lambda: Fsp.gather_gemm_planned(x, pf, ff, rb.n_out, K, cin, cout)) for _ in range(reps)]
+            t_bn = [timeit(lambda: Fsp.gather_gemm_planned(x, pf, ff, rb.n_out, K, cin, cout, scale=scale, shift=shift, relu=True)) for _ in range(reps)]
+            t_all = [timeit(lambda: Fsp.gather_gemm_planned(x, pf, ff, rb.n_out, K, cin, cout, bias=bias, scale=scale, shift=shift, residual=res, relu=True))
+                     for _ in range(reps)]
+            fmt = lambda ts: " ".join(f"{t:7.1f}" for t in ts)
+            print(f"{name:8s} {cin:3d}->{cout:3d} N_out={rb.n_out:7d} epilogue us | bare {fmt(t_bare)} | scale+shift+relu {fmt(t_bn)} | all terms {fmt(t_all)}")
         if mode in ("all", "bwd"):
             if pb is None:
                 td = timeit(lambda: Fsp.gather_gemm(dy, rb.table_for_backward_data(), w, rb.n_in))
