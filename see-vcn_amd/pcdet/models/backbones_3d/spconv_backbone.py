@@ -56,7 +56,7 @@ class SparseBasicBlock(spconv.SparseModule):
         return out
 
 
-chain.register_residual_block(SparseBasicBlock)         # the eval list (chain.flatten_eval) takes blocks whose forward is the one above
+chain.register_residual_block(SparseBasicBlock)         # chain.flatten takes blocks whose forward is the one above (eval list)
 
 
 class _BackBone8xBase(nn.Module):
@@ -68,34 +68,19 @@ class _BackBone8xBase(nn.Module):
         return batch_dict
 
     def _chain_blocks(self):
-        """The stages as one list of conv -> norm -> ReLU blocks (taps after conv1..conv4 and conv_out), or None; cached until a module is registered
-        anywhere (the registration epoch of seevcn_amd.spconv.conv)."""
+        """The stages as one list of entries, one per convolution (chain.flatten: residual blocks and conv biases included; taps after conv1..conv4
+        and conv_out), or None; cached until a module is registered anywhere (the registration epoch of seevcn_amd.spconv.conv).  The training chain
+        and the eval list both read it."""
         from ....spconv import conv as sconv
         epoch = sconv._registration_epoch[0]
         hit = self.__dict__.get('_seevcn_chain')
         if hit is None or hit[0] != epoch:
-            stages = [self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out]
-            blocks = chain.flatten_blocks(stages)
-            if blocks is not None:
-                for b in blocks[:len(chain.flatten_blocks([self.conv_input]) or [])]:
-                    b.tap = False                                     # conv_input feeds conv1 only
-            hit = (epoch, blocks)
-            self.__dict__['_seevcn_chain'] = hit
-        return hit[1]
-
-    def _eval_entries(self):
-        """The stages as one list of eval entries, one per convolution (chain.flatten_eval: residual blocks and conv biases included), or None; the
-        same taps and the same cache key as _chain_blocks."""
-        from ....spconv import conv as sconv
-        epoch = sconv._registration_epoch[0]
-        hit = self.__dict__.get('_seevcn_eval_chain')
-        if hit is None or hit[0] != epoch:
-            entries = chain.flatten_eval([self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out])
+            entries = chain.flatten([self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out])
             if entries is not None:
-                for e in entries[:len(chain.flatten_eval([self.conv_input]) or [])]:
+                for e in entries[:len(chain.flatten([self.conv_input]) or [])]:
                     e.tap = False                                     # conv_input feeds conv1 only
             hit = (epoch, entries)
-            self.__dict__['_seevcn_eval_chain'] = hit
+            self.__dict__['_seevcn_chain'] = hit
         return hit[1]
 
     def forward_stages(self, batch_dict):
@@ -109,16 +94,15 @@ class _BackBone8xBase(nn.Module):
         spconv.prebuild_rulebooks(self, input_sp_tensor, with_backward=self.training and torch.is_grad_enabled())
         # the MFMA fragment copies of all layer weights in one launch (they follow the weights every forward; spconv/functional.py)
         spconv.refresh_weight_fragments(self)
-        # training, every stage a plain run of conv -> BatchNorm1d -> ReLU blocks (VoxelBackBone8x): the whole chain and its backward as two launch
-        # lists inside one autograd node (seevcn_amd/spconv/chain.py) instead of ~100 calls from the module tree
-        blocks = self._chain_blocks()
-        if self.training and chain.applicable(blocks, input_sp_tensor):
-            x_conv1, x_conv2, x_conv3, x_conv4, out = chain.run_chain(blocks, input_sp_tensor)
-            return self._finish(batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out)
-        # eval without gradients (both backbones, residual blocks included): one launch list, every BatchNorm folded into its conv's epilogue
-        elif not self.training and chain.eval_applicable(self._eval_entries(), input_sp_tensor):
-            x_conv1, x_conv2, x_conv3, x_conv4, out = chain.run_eval_chain(self._eval_entries(), input_sp_tensor)
-            return self._finish(batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out)
+        # one description of the stages for both launch-list routes (seevcn_amd/spconv/chain.py) instead of ~100 calls from the module tree.  Training,
+        # every stage a plain run of conv -> BatchNorm1d | SyncBatchNorm -> ReLU blocks (VoxelBackBone8x): the whole chain and its backward as two lists
+        # inside one autograd node.  Eval without gradients (both backbones, residual blocks included): one list, every BatchNorm folded into its
+        # conv's epilogue.  Whatever neither takes walks the module tree below.
+        entries = self._chain_blocks()
+        if self.training and chain.applicable(entries, input_sp_tensor):
+            return self._finish(batch_dict, *chain.run_chain(entries, input_sp_tensor))
+        if not self.training and chain.eval_applicable(entries, input_sp_tensor):
+            return self._finish(batch_dict, *chain.run_eval_chain(entries, input_sp_tensor))
         x = self.conv_input(input_sp_tensor)
         x_conv1 = self.conv1(x)
         yield

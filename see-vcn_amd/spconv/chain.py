@@ -9,12 +9,18 @@ enqueued with one call; the backward (BatchNorm backward, weight gradient, data 
 same arithmetic, same parameters and running statistics as the per-module path (SparseSequential), which stays the fallback for anything
 this does not take (hooks, a conv bias or residual blocks in training mode, a layer without a plan for its data gradient).
 
-Eval mode (flatten_eval / eval_applicable / run_eval_chain; tools/test.py of the reference, the post_processing + recall path): the list is one
+Eval mode (eval_applicable / run_eval_chain; tools/test.py of the reference, the post_processing + recall path): the list is one
 launch that makes every BatchNorm's (scale, shift) from its running statistics (SV_OP_BN_EVAL_COEF_BATCH) and one convolution per layer whose
 epilogue applies conv bias, folded BatchNorm, the identity of a residual block (SparseBasicBlock, spconv_backbone.py:30-66) and the ReLU -- every
 activation is written once, normalised.  It stands down (module tree) when gradients are enabled, a norm is in training mode or keeps no running
 statistics, the input is empty, anything walked carries a hook, a residual block has a downsample module or a forward of its own, or SEEVCN_CHAIN=0 /
-SEEVCN_EVAL_CHAIN=0."""
+SEEVCN_EVAL_CHAIN=0.
+
+Both routes read ONE description of the network: flatten() -> BlockList of Entry, one per convolution (applicable() declines for training what only
+the eval list carries: a residual identity, a conv bias).  Every row of a list is made by the constructor of its operation code (CONV_PLANNED ...
+BN_EVAL_COEF_BATCH below): the only place that knows which word of the row a field of include/seevcn_hip.h is."""
+from collections import namedtuple
+from functools import partial
 import os
 import struct
 
@@ -71,6 +77,77 @@ def _row(code, i=(), n=(), f=(), p=()):
     return r
 
 
+# One constructor per operation code: keyword arguments named like the fields of the executor's header comment (include/seevcn_hip.h), pointers as device
+# addresses (None = null).  `plan` is the tuple of Rulebook.plan_addrs: (table_rows, perm, masks_p, tile_of, tiles_per_wave, table_k_reversed); mom_eps
+# the bit patterns of (momentum, eps) (Entry.mom_eps).  in_coef / in_relu: the input transform (X is the raw conv output of the layer below).
+def CONV_PLANNED(plan, *, X, n_src, wfrag, Y, n_rows, K, Kd, Nc, relu=0, bias=None, scale=None, shift=None, residual=None, bn_partial=None, in_coef=None,
+                 in_relu=0):
+    table_rows, perm, masks_p, tile_of, tiles_per_wave, table_k_reversed = plan
+    return _row(OP_CONV_PLANNED, i=(tiles_per_wave, K, Kd, Nc, relu, bool(table_k_reversed), in_relu), n=(n_src, n_rows),
+                p=(X, table_rows, perm, masks_p, tile_of, wfrag, Y, bias, scale, shift, residual, bn_partial, in_coef))
+
+
+def CONV_PLAIN(*, X, n_src, nbr, Wt, Y, n_rows, K, Kd, Nc, relu=0, bias=None, scale=None, shift=None, residual=None):
+    return _row(OP_CONV_PLAIN, i=(K, Kd, Nc, relu), n=(n_src, n_rows), p=(X, nbr, Wt, Y, bias, scale, shift, residual))
+
+
+def DGRAD_PLANNED_BN(plan, *, dZ, n_src, wfrag, dY, n_rows, K, Kd, Nc, bn_x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_partial, bn_relu):
+    table_rows, perm, masks_p, tile_of, tiles_per_wave, table_k_reversed = plan
+    return _row(OP_DGRAD_PLANNED_BN, i=(tiles_per_wave, K, Kd, Nc, bool(table_k_reversed), bn_relu), n=(n_src, n_rows),
+                p=(dZ, table_rows, perm, masks_p, tile_of, wfrag, dY, bn_x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_partial))
+
+
+def WGRAD(*, X, n_src, nbr, dY, n_rows, dW, scratch, K, Cin, Cout, stride_k, stride_cin, stride_cout, plan=None, in_coef=None, in_relu=0, code=OP_WGRAD):
+    return _row(code, i=(K, Cin, Cout, n_src, in_relu), n=(n_rows, stride_k, stride_cin, stride_cout), p=(X, nbr, dY, dW, scratch, plan, in_coef))
+
+
+WGRAD_DEFERRED = partial(WGRAD, code=OP_WGRAD_DEFERRED)          # the same fields; `scratch` is the layer's OWN partial region
+
+
+def BN_FWD(*, x, rows, channels, gamma, beta, running_mean, running_var, mom_eps, scratch, y, save_mean, save_invstd, num_batches_tracked, training, relu,
+           n_partials=0):
+    return _row(OP_BN_FWD, i=(channels, training, relu, n_partials), n=(rows,), f=mom_eps,
+                p=(x, gamma, beta, running_mean, running_var, scratch, y, save_mean, save_invstd, num_batches_tracked))
+
+
+def BN_FINALIZE(*, x, rows, channels, gamma, beta, running_mean, running_var, mom_eps, scratch, coef, save_mean, save_invstd, num_batches_tracked,
+                n_partials=0):
+    return _row(OP_BN_FINALIZE, i=(channels, n_partials), n=(rows,), f=mom_eps,
+                p=(gamma, beta, running_mean, running_var, scratch, coef, save_mean, save_invstd, num_batches_tracked, x))
+
+
+def BN_APPLY(*, x, rows, channels, coef, relu, y):
+    return _row(OP_BN_APPLY, i=(channels, relu), n=(rows,), p=(x, coef, y))
+
+
+def BN_STATS_LOCAL(*, x, rows, channels, scratch, sums, n_partials=0):
+    return _row(OP_BN_STATS_LOCAL, i=(channels, n_partials), n=(rows,), p=(x, scratch, sums))
+
+
+def BN_FINALIZE_GLOBAL(*, gathered, world, channels, gamma, beta, running_mean, running_var, mom_eps, coef, save_mean, save_invstd, num_batches_tracked,
+                       total_rows):
+    return _row(OP_BN_FINALIZE_GLOBAL, i=(channels, world), f=mom_eps,
+                p=(gathered, gamma, beta, running_mean, running_var, coef, save_mean, save_invstd, num_batches_tracked, total_rows))
+
+
+def BN_BWD(*, x, dy, rows, channels, gamma, beta, save_mean, save_invstd, relu, scratch, dx, dgamma, dbeta, n_partials=0):
+    return _row(OP_BN_BWD, i=(channels, relu, n_partials), n=(rows,), p=(x, dy, gamma, beta, save_mean, save_invstd, scratch, dx, dgamma, dbeta))
+
+
+def BN_BWD_SUMS_LOCAL(*, x, dy, rows, channels, gamma, beta, save_mean, save_invstd, relu, scratch, dgamma, dbeta, sums, n_partials=0):
+    return _row(OP_BN_BWD_SUMS_LOCAL, i=(channels, relu, n_partials), n=(rows,),
+                p=(x, dy, gamma, beta, save_mean, save_invstd, scratch, dgamma, dbeta, sums))
+
+
+def BN_BWD_APPLY_GLOBAL(*, x, dy, rows, channels, gamma, beta, save_mean, save_invstd, relu, scratch, gathered, world, total_rows, dx):
+    return _row(OP_BN_BWD_APPLY_GLOBAL, i=(channels, relu, world), n=(rows,),
+                p=(x, dy, gamma, beta, save_mean, save_invstd, scratch, gathered, total_rows, dx))
+
+
+def BN_EVAL_COEF_BATCH(*, jobs_host, n_jobs):
+    return _row(OP_BN_EVAL_COEF_BATCH, i=(n_jobs,), p=(jobs_host,))                  # the job table is HOST memory, read before the list's call returns
+
+
 def _run(rows, what):
     arr = np.array(rows, dtype=np.int64)
     _lib.check(_lib.load().sv_run_ops(arr.ctypes.data, len(rows), _lib.stream()), what)
@@ -95,7 +172,7 @@ class Cut:
 
 
 def _run_cut(rows, run):
-    """run(segment) for every run of rows between the Cuts of `rows`, the exchange of each Cut in between.  A list without a Cut is one call, as it is."""
+    """run(segment) for every run of rows between the Cuts of `rows`, the exchange of each Cut in between.  A list without a Cut is one call with all its rows."""
     seg = []
     for r in rows:
         if isinstance(r, Cut):
@@ -108,23 +185,29 @@ def _run_cut(rows, run):
         run(seg)
 
 
-class Block:
-    """One conv -> norm (-> ReLU) block of a chain: the modules (parameters and running statistics stay theirs) and what is fixed about them."""
+class Entry:
+    """One convolution of a chain and what follows it: (conv, bn, relu, residual_from, tap); the modules keep their parameters and running statistics.
+    residual_from: index of the entry whose output is added before the ReLU (a residual block's identity), -1 for the chain's input, None for none;
+    tap: the output is returned by the chain."""
+    __slots__ = ("conv", "bn", "relu", "residual_from", "tap", "K", "cin", "cout")
 
-    def __init__(self, conv, bn, relu, tap):
-        self.conv, self.bn, self.relu, self.tap = conv, bn, bool(relu), tap          # tap: this block's output is returned by the chain
+    def __init__(self, conv, bn, relu, residual_from, tap):
+        self.conv, self.bn, self.relu, self.residual_from, self.tap = conv, bn, bool(relu), residual_from, tap
         self.K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
         self.cin, self.cout = conv.in_channels, conv.out_channels
 
+    def __iter__(self):
+        return iter((self.conv, self.bn, self.relu, self.residual_from, self.tap))
+
     @property
     def mom_eps(self):
-        # read when the launch list is made, i.e. after applicable() -> fusable_with() has rejected momentum=None (cumulative average)
+        # read when a training list is made, i.e. after applicable() -> fusable_with() has rejected momentum=None (cumulative average)
         return (_bits(self.bn.momentum), _bits(self.bn.eps))
 
 
 class BlockList(list):
-    """The blocks of a chain + every module the flattening walked over (stage containers, nested SparseSequentials, convs, norms, ReLUs): the chain
-    bypasses __call__ of ALL of them, so a hook on any of them must send the forward back to the module tree."""
+    """The entries of a chain + every module the flattening walked over (stage containers, nested SparseSequentials, residual blocks, convs, norms,
+    ReLUs): the chain bypasses __call__ of ALL of them, so a hook on any of them must send the forward back to the module tree."""
     walked = ()
 
 
@@ -132,45 +215,82 @@ def _has_hooks(m):
     return bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None))
 
 
-def flatten_blocks(groups):
-    """groups: the backbone's stages in execution order (SparseSequential each).  -> list of Block, or None when a stage is not a plain sequence of
-    (SparseConvolution, BatchNorm1d | SyncBatchNorm, ReLU) triples.  The last block of every stage is a tap."""
+_residual_blocks = []
+
+
+def register_residual_block(cls):
+    """cls: a residual block class (SparseBasicBlock) whose OWN forward is relu(bn2(conv2(relu(bn1(conv1(x))))) + x) when its downsample is None;
+    flatten takes instances whose forward is that very function (a subclass with a forward of its own is declined)."""
+    if cls not in _residual_blocks:
+        _residual_blocks.append(cls)
+    return cls
+
+
+def _is_residual_block(m):
+    from .conv import SparseConvolution
+    if not any(isinstance(m, cls) and type(m).forward is cls.forward for cls in _residual_blocks):
+        return False
+    c1, c2 = getattr(m, "conv1", None), getattr(m, "conv2", None)
+    return (isinstance(c1, SparseConvolution) and isinstance(c2, SparseConvolution) and c1.subm and c2.subm and c1.indice_key is not None
+            and c1.indice_key == c2.indice_key and c1.kernel_size == c2.kernel_size and c1.in_channels == c2.out_channels
+            and c1.out_channels == c2.in_channels and getattr(m, "downsample", 0) is None and type(getattr(m, "relu", None)) is torch.nn.ReLU
+            and norm.route(getattr(m, "bn1", None)) is not None and norm.route(getattr(m, "bn2", None)) is not None)
+
+
+def flatten(stages):
+    """stages: the backbone's stages in execution order (SparseSequential each).  -> BlockList of Entry, one per convolution, or None when a stage is
+    anything but (SparseConvolution [with or without bias], BatchNorm1d | SyncBatchNorm, ReLU) triples and registered residual blocks without a
+    downsample.  The last entry of every stage is a tap."""
     from .conv import SparseConvolution
     from .modules import SparseSequential
-    blocks = BlockList()
+    entries = BlockList()
     walked = []
 
     def walk(m, out):
         walked.append(m)
         for child in m._modules.values():
             if isinstance(child, SparseSequential):
-                if not walk(child, out):
-                    return False
+                walk(child, out)
             else:
                 walked.append(child)
                 out.append(child)
-        return True
 
-    for stage in groups:
-        mods = []
-        if not isinstance(stage, SparseSequential) or not walk(stage, mods) or len(mods) % 3 != 0 or not mods:
+    for stage in stages:
+        if not isinstance(stage, SparseSequential):
             return None
-        for j in range(0, len(mods), 3):
-            conv, bn, relu = mods[j:j + 3]
-            if not (isinstance(conv, SparseConvolution) and norm.route(bn) is not None and type(relu) is torch.nn.ReLU):
+        mods = []
+        walk(stage, mods)
+        j, n0 = 0, len(entries)
+        while j < len(mods):
+            m = mods[j]
+            if isinstance(m, SparseConvolution):
+                if j + 2 >= len(mods) or norm.route(mods[j + 1]) is None or type(mods[j + 2]) is not torch.nn.ReLU:
+                    return None
+                entries.append(Entry(m, mods[j + 1], True, None, False))
+                j += 3
+            elif _is_residual_block(m):
+                walked.extend(c for c in m._modules.values() if c is not None)      # a downsample set and cleared again stays registered as None
+                identity = len(entries) - 1                                         # -1: the block reads the chain's input
+                entries.append(Entry(m.conv1, m.bn1, True, None, False))
+                entries.append(Entry(m.conv2, m.bn2, True, identity, False))
+                j += 1
+            else:
                 return None
-            blocks.append(Block(conv, bn, True, False))
-        blocks[-1].tap = True
-    blocks.walked = tuple(walked)
-    return blocks
+        if len(entries) == n0:
+            return None
+        entries[-1].tap = True
+    entries.walked = tuple(walked)
+    return entries
 
 
 def applicable(blocks, x):
-    """The chain takes these blocks on x now: training with gradients on, fp32 CUDA features, every block what fusable_with() accepts, no hooks,
-    every rulebook in x's indice_dict (prebuild_rulebooks ran) with at least two output rows, and a planned data-gradient kernel for every block
-    behind the first (the first one's is needed only when the input features want a gradient, which the backbone's never do)."""
+    """The chain takes these blocks on x now: training with gradients on, fp32 CUDA features, no residual identity, every block what fusable_with()
+    accepts, no hooks, every rulebook in x's indice_dict (prebuild_rulebooks ran) with at least two output rows, and a planned data-gradient kernel
+    for every block behind the first (the first one's is needed only when the input features want a gradient, which the backbone's never do)."""
     if CHAIN_OFF or blocks is None or not torch.is_grad_enabled() or x.features.requires_grad or x.indices.shape[0] < 2:
         return False
+    if any(b.residual_from is not None for b in blocks):
+        return False               # a residual block's identity: only the eval list adds it (a conv bias is declined by fusable_with below)
     if any(_has_hooks(m) for m in getattr(blocks, 'walked', ())):
         return False               # a forward / pre-forward / backward hook on a stage, a nested sequential, a conv, a norm or a ReLU: module path
     for k, b in enumerate(blocks):
@@ -214,6 +334,70 @@ def fold_plan(blocks, rulebooks):
     return fold_in, materialize
 
 
+# where a block's pieces lie in the chain's allocations (offsets in floats; _addresses(): the same record as device addresses).  Forward arena per block:
+# [conv output | block output (when it is written at all) | batch mean | batch invstd | scale | shift]; backward work buffer per block: [gradient of the
+# conv output | gradient of the block's input (blocks >= 1) | dgamma | dbeta]
+_Forward = namedtuple("_Forward", "conv y mean istd coef")
+_Backward = namedtuple("_Backward", "dconv dx dgamma dbeta")
+
+
+def _addresses(base, offs):
+    return offs._make(base + 4 * v for v in offs)
+
+
+def _conv_row(e, rb, keep, X, n_src, Y, bn_partial=None, in_coef=None, in_relu=0, **epilogue):
+    """-> (row, backward fragments, planned) of entry e's forward convolution X (n_src rows) -> Y on rulebook rb: on the table's plan with the weights in
+    fragment order when the MFMA kernel takes the layer (planned), else (backward fragments None) the plain kernel on a (K, C_out, C_in) copy of the weights that `keep`
+    holds until the list has run: the 3/4/5-channel input layer only.  epilogue: relu, bias, scale, shift, residual.  Only the planned kernel writes
+    bn_partial and reads its input through in_coef."""
+    wk = e.conv.weight_kio_nograd()
+    plan = rb.plan_addrs("fwd", e.cin, e.cout)
+    if plan is not None:
+        wfrag, frag_bwd = Fsp.fragment_cache.get(wk)
+        return CONV_PLANNED(plan, X=X, n_src=n_src, wfrag=wfrag.data_ptr(), Y=Y, n_rows=rb.n_out, K=e.K, Kd=e.cin, Nc=e.cout, bn_partial=bn_partial,
+                            in_coef=in_coef, in_relu=in_relu, **epilogue), frag_bwd, True
+    assert in_coef is None
+    wt = wk.detach().permute(0, 2, 1).contiguous()
+    keep.append(wt)
+    return CONV_PLAIN(X=X, n_src=n_src, nbr=rb.addr("nbr_out"), Wt=wt.data_ptr(), Y=Y, n_rows=rb.n_out, K=e.K, Kd=e.cin, Nc=e.cout, **epilogue), None, False
+
+
+def _bn_forward_rows(e, a, rows, gamma, beta, n_partials, materialize, total_rows):
+    """The rows of a block's BatchNorm in the training forward.  a: the block's arena addresses; n_partials: the conv in front left that many partial sums
+    in the norm's scratch (norm.partial_address; 0: the statistics read a.conv); total_rows: where a SYNCED norm (norm.route) keeps the row count of all ranks -- its list is
+    cut behind this rank's sums, the ranks exchange them, the next list starts with the combine over all ranks."""
+    bn, dev = e.bn, gamma.device
+    x = None if n_partials else a.conv
+    scratch = norm._scratch(e.cout, dev).data_ptr()
+    stats = dict(channels=e.cout, gamma=gamma.data_ptr(), beta=beta.data_ptr(), running_mean=bn.running_mean.data_ptr(), running_var=bn.running_var.data_ptr(),
+                 mom_eps=e.mom_eps, save_mean=a.mean, save_invstd=a.istd, num_batches_tracked=bn.num_batches_tracked.data_ptr())
+    if total_rows is not None:
+        local, gathered, group = norm.sync_buffers(bn, e.cout, dev)
+        out = [BN_STATS_LOCAL(x=x, rows=rows, channels=e.cout, scratch=scratch, sums=local.data_ptr(), n_partials=n_partials), Cut(local, gathered, group),
+               BN_FINALIZE_GLOBAL(gathered=gathered.data_ptr(), world=gathered.shape[0], coef=a.coef, total_rows=total_rows, **stats)]
+    elif BN_FOLD:
+        out = [BN_FINALIZE(x=x, rows=rows, scratch=scratch, coef=a.coef, n_partials=n_partials, **stats)]
+    else:                                                                             # statistics, normalisation and ReLU in one operation
+        return [BN_FWD(x=a.conv, rows=rows, scratch=scratch, y=a.y, training=1, relu=e.relu, n_partials=n_partials, **stats)]
+    if materialize:
+        out.append(BN_APPLY(x=a.conv, rows=rows, channels=e.cout, coef=a.coef, relu=e.relu, y=a.y))
+    return out
+
+
+def _bn_backward_rows(e, a, w, rows, dy, gamma, beta, n_partials, total_rows):
+    """The rows of a block's BatchNorm in the backward.  a / w: the block's addresses in the forward arena / the backward work buffer; n_partials: the
+    data-gradient launch above left that many partial sums (0: the reduce pass over x, dy runs first); total_rows: as in the forward (SYNCED: this rank's
+    two sums | exchange | the elementwise pass with everybody's)."""
+    dev = gamma.device
+    common = dict(x=a.conv, dy=dy, rows=rows, channels=e.cout, gamma=gamma.data_ptr(), beta=beta.data_ptr(), save_mean=a.mean, save_invstd=a.istd,
+                  relu=e.relu, scratch=norm._scratch(e.cout, dev).data_ptr())
+    if total_rows is None:
+        return [BN_BWD(dx=w.dconv, dgamma=w.dgamma, dbeta=w.dbeta, n_partials=n_partials, **common)]
+    local, gathered, group = norm.sync_buffers(e.bn, e.cout, dev, backward=True)
+    return [BN_BWD_SUMS_LOCAL(dgamma=w.dgamma, dbeta=w.dbeta, sums=local.data_ptr(), n_partials=n_partials, **common), Cut(local, gathered, group),
+            BN_BWD_APPLY_GLOBAL(gathered=gathered.data_ptr(), world=gathered.shape[0], total_rows=total_rows, dx=w.dconv, **common)]
+
+
 class SparseChainFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, blocks, rulebooks, *params):
@@ -222,84 +406,46 @@ class SparseChainFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)                                              # a tap nobody differentiates arrives as None, not as zeros
         features = features.contiguous().float()
         fold_in, materialize = fold_plan(blocks, rulebooks)
-        # one allocation for every activation: per block [conv output | block output (when it is written at all) | batch mean | batch invstd | scale | shift]
-        offs, total = [], 0
+        offs, total = [], 0                                                           # one allocation for every activation
         for k, (b, rb) in enumerate(zip(blocks, rulebooks)):
             n = rb.n_out * b.cout
             ny = n if materialize[k] else 0
-            offs.append((total, total + n, total + n + ny, total + n + ny + b.cout, total + n + ny + 2 * b.cout))
+            offs.append(_Forward(total, total + n, total + n + ny, total + n + ny + b.cout, total + n + ny + 2 * b.cout))
             total += n + ny + 4 * b.cout
         arena = torch.empty((total,), dtype=torch.float32, device=dev)
         base = arena.data_ptr()
         n_part = lib.sv_conv_planned_partials()
         rows, x_ptr, n_src, keep = [], features.data_ptr(), features.shape[0], []
         frags = []
-        # a SyncBatchNorm over several ranks (norm.route): the list is cut behind the block's own sums, the ranks exchange them, the next list starts with
-        # the combine over all ranks.  Every rank keeps the total row count of each synced block on the device for the backward.
+        # every rank keeps the total row count of each synced block (norm.route) on the device for the backward
         synced = [norm.route(b.bn) == norm.SYNCED for b in blocks]
         totals = torch.empty((len(blocks),), dtype=torch.float64, device=dev) if any(synced) else None
-        in_coef = None                                                                # (address, relu) of the transform the next conv applies on load
+        in_coef, in_relu = None, 0                                                    # the transform this block's conv applies on load
         for k, (b, rb) in enumerate(zip(blocks, rulebooks)):
             w, gamma, beta = params[3 * k:3 * k + 3]
-            o_conv, o_y, o_mean, o_istd, o_coef = (base + 4 * v for v in offs[k])
-            wk = b.conv.weight_kio_nograd()
-            plan = rb.plan_addrs("fwd", b.cin, b.cout)
-            scratch = norm._scratch(b.cout, dev).data_ptr()
-            partial = 0
-            if plan is not None:
-                a_rows, a_perm, a_masks_p, a_tiles, g, rev = plan
-                ff, fb = Fsp.fragment_cache.get(wk)
-                frags.append(fb)
-                partial = scratch + 16 * b.cout if norm.STATS_IN_CONV else 0
-                rows.append(_row(OP_CONV_PLANNED, i=(g, b.K, b.cin, b.cout, 0, int(bool(rev)), in_coef[1] if in_coef else 0), n=(n_src, rb.n_out),
-                                 p=(x_ptr, a_rows, a_perm, a_masks_p, a_tiles, ff.data_ptr(), o_conv, None, None, None, None, partial or None,
-                                    in_coef[0] if in_coef else None)))
-            else:
-                assert in_coef is None
-                frags.append(None)
-                wt = wk.detach().permute(0, 2, 1).contiguous()                       # (K, C_out, C_in): the 3-channel input layer only
-                keep.append(wt)
-                rows.append(_row(OP_CONV_PLAIN, i=(b.K, b.cin, b.cout, 0), n=(n_src, rb.n_out), p=(x_ptr, rb.addr("nbr_out"), wt.data_ptr(), o_conv)))
-            if synced[k]:
-                local, gathered, group = norm.sync_buffers(b.bn, b.cout, dev)
-                rows.append(_row(OP_BN_STATS_LOCAL, i=(b.cout, n_part if partial else 0), n=(rb.n_out,), p=(None if partial else o_conv, scratch, local.data_ptr())))
-                rows.append(Cut(local, gathered, group))
-                rows.append(_row(OP_BN_FINALIZE_GLOBAL, i=(b.cout, gathered.shape[0]), f=b.mom_eps,
-                                 p=(gathered.data_ptr(), gamma.data_ptr(), beta.data_ptr(), b.bn.running_mean.data_ptr(), b.bn.running_var.data_ptr(), o_coef, o_mean,
-                                    o_istd, b.bn.num_batches_tracked.data_ptr(), totals.data_ptr() + 8 * k)))
-                if materialize[k]:
-                    rows.append(_row(OP_BN_APPLY, i=(b.cout, int(b.relu)), n=(rb.n_out,), p=(o_conv, o_coef, o_y)))
-            elif BN_FOLD:
-                rows.append(_row(OP_BN_FINALIZE, i=(b.cout, n_part if partial else 0), n=(rb.n_out,), f=b.mom_eps,
-                                 p=(gamma.data_ptr(), beta.data_ptr(), b.bn.running_mean.data_ptr(), b.bn.running_var.data_ptr(), scratch, o_coef, o_mean, o_istd,
-                                    b.bn.num_batches_tracked.data_ptr(), None if partial else o_conv)))
-                if materialize[k]:
-                    rows.append(_row(OP_BN_APPLY, i=(b.cout, int(b.relu)), n=(rb.n_out,), p=(o_conv, o_coef, o_y)))
-            else:
-                rows.append(_row(OP_BN_FWD, i=(b.cout, 1, int(b.relu), n_part if partial else 0), n=(rb.n_out,), f=b.mom_eps,
-                                 p=(o_conv, gamma.data_ptr(), beta.data_ptr(), b.bn.running_mean.data_ptr(), b.bn.running_var.data_ptr(), scratch, o_y, o_mean,
-                                    o_istd, b.bn.num_batches_tracked.data_ptr())))
+            a = _addresses(base, offs[k])
+            row, frag_bwd, planned = _conv_row(b, rb, keep, x_ptr, n_src, a.conv, bn_partial=norm.partial_address(b.cout, dev) if norm.STATS_IN_CONV else None,
+                                               in_coef=in_coef, in_relu=in_relu)
+            rows.append(row)
+            frags.append(frag_bwd)
+            n_partials = n_part if norm.STATS_IN_CONV and planned else 0              # only the planned kernel's epilogue makes the sums
+            rows += _bn_forward_rows(b, a, rb.n_out, gamma, beta, n_partials, materialize[k], totals.data_ptr() + 8 * k if synced[k] else None)
             if k + 1 < len(blocks) and fold_in[k + 1]:
-                x_ptr, in_coef = o_conv, (o_coef, int(b.relu))
+                x_ptr, in_coef, in_relu = a.conv, a.coef, int(b.relu)
             else:
-                x_ptr, in_coef = o_y, None
+                x_ptr, in_coef, in_relu = a.y, None, 0
             n_src = rb.n_out
-        if totals is None:
-            _run(rows, "sv_run_ops (chain forward)")
-        else:
-            _run_cut(rows, lambda seg: _run(seg, "sv_run_ops (chain forward)"))
+        _run_cut(rows, lambda seg: _run(seg, "sv_run_ops (chain forward)"))
         ctx.blocks, ctx.rulebooks, ctx.offs, ctx.frags, ctx.fold_in, ctx.synced = blocks, rulebooks, offs, frags, fold_in, synced
         ctx.save_for_backward(features, arena, totals, *params)
         # a tap whose normalised output is written in the list is that tensor; the others hand out [raw conv output, coefficients] (see run_chain)
-        outs = []
+        outs, coefs = [], []
         for k, b in enumerate(blocks):
             if b.tap:
-                n, c = rulebooks[k].n_out, b.cout
-                if materialize[k]:
-                    outs.append(arena[offs[k][1]:offs[k][2]].view(n, c))
-                else:
-                    outs.append(arena[offs[k][0]:offs[k][1]].view(n, c))
-        coefs = [arena[offs[k][4]:offs[k][4] + 2 * b.cout] for k, b in enumerate(blocks) if b.tap and not materialize[k]]
+                o = offs[k]
+                outs.append((arena[o.y:o.mean] if materialize[k] else arena[o.conv:o.y]).view(rulebooks[k].n_out, b.cout))
+                if not materialize[k]:
+                    coefs.append(arena[o.coef:o.coef + 2 * b.cout])
         ctx.mark_non_differentiable(*coefs)
         return tuple(outs) + tuple(coefs)
 
@@ -317,17 +463,16 @@ class SparseChainFunction(torch.autograd.Function):
                 gi += 1
         if ext[L - 1] is None:
             ext[L - 1] = torch.zeros((rulebooks[-1].n_out, blocks[-1].cout), dtype=torch.float32, device=dev)
-        # one allocation for the work buffers: per block [gradient of the conv output | gradient of the block's input (blocks >= 1) | dgamma | dbeta],
-        # one for the weight gradients (in the parameters' own layout)
+        # one allocation for the work buffers, one for the weight gradients (in the parameters' own layout)
         boffs, total, woffs, wtotal, wbytes, poffs, wplans = [], 0, [], 0, 0, [], []
         for k, (b, rb) in enumerate(zip(blocks, rulebooks)):
             n, nin = rb.n_out * b.cout, (rb.n_in * b.cin if k > 0 else 0)
-            boffs.append((total, total + n, total + n + nin, total + n + nin + b.cout))
+            boffs.append(_Backward(total, total + n, total + n + nin, total + n + nin + b.cout))
             total += n + nin + 2 * b.cout
             woffs.append(wtotal)
             wtotal += b.K * b.cin * b.cout
             wp = rb.wgrad_plan(b.cin, b.cout)                        # equal-pieces plan of the table (built with the index; here only if it was not)
-            wplans.append(0 if wp is None else wp.data_ptr())
+            wplans.append(None if wp is None else wp.data_ptr())
             if DEFER_WGRAD_REDUCE:                                   # every layer keeps its own partial slabs until the one reduction at the end of the list
                 poffs.append(wbytes)
                 wbytes += lib.sv_sparse_conv_wgrad_partial_bytes(rb.n_out, b.K, b.cin, b.cout) if wp is None else lib.sv_sparse_conv_wgrad_planned_bytes(b.K, b.cin, b.cout)
@@ -338,64 +483,44 @@ class SparseChainFunction(torch.autograd.Function):
         work = torch.empty((total,), dtype=torch.float32, device=dev)
         wgrads = torch.empty((wtotal,), dtype=torch.float32, device=dev)
         wscratch = _lib.workspace.scratch("wgrad_layers" if DEFER_WGRAD_REDUCE else "wgrad", wbytes, dev)
-        base, abase, wbase = work.data_ptr(), arena.data_ptr(), wgrads.data_ptr()
+        base, abase, wbase = work.data_ptr(), arena.data_ptr(), wgrads.data_ptr()       # abase: of the SAVED arena (autograd may hand back another tensor)
         rows = []
         n_part, n_part_bwd = lib.sv_conv_planned_partials(), 0          # n_part_bwd: partials the data-gradient launch above left for this BatchNorm
+        wgrad_row = WGRAD_DEFERRED if DEFER_WGRAD_REDUCE else WGRAD
         dy_ptr = ext[L - 1].data_ptr()
         for k in range(L - 1, -1, -1):
             b, rb = blocks[k], rulebooks[k]
             w, gamma, beta = params[3 * k:3 * k + 3]
-            o_dconv, o_dx, o_dg, o_db = (base + 4 * v for v in boffs[k])
-            a_conv, a_y, a_mean, a_istd, _ = (abase + 4 * v for v in offs[k])
-            # the layer's input: the features, the block below's normalised output, or (folded) its raw conv output + the coefficients of its BatchNorm
-            x_in = features.data_ptr() if k == 0 else abase + 4 * offs[k - 1][0 if fold_in[k] else 1]
-            x_coef = (abase + 4 * offs[k - 1][4], int(blocks[k - 1].relu)) if fold_in[k] else (None, 0)
-            scratch = norm._scratch(b.cout, dev)
-            if synced[k]:                                                              # this rank's two sums | exchange | the elementwise pass with everybody's
-                local, gathered, group = norm.sync_buffers(b.bn, b.cout, dev, backward=True)
-                rows.append(_row(OP_BN_BWD_SUMS_LOCAL, i=(b.cout, int(b.relu), n_part_bwd), n=(rb.n_out,),
-                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), o_dg, o_db, local.data_ptr())))
-                rows.append(Cut(local, gathered, group))
-                rows.append(_row(OP_BN_BWD_APPLY_GLOBAL, i=(b.cout, int(b.relu), gathered.shape[0]), n=(rb.n_out,),
-                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), gathered.data_ptr(),
-                                    totals.data_ptr() + 8 * k, o_dconv)))
-            else:
-                rows.append(_row(OP_BN_BWD, i=(b.cout, int(b.relu), n_part_bwd), n=(rb.n_out,),
-                                 p=(a_conv, dy_ptr, gamma.data_ptr(), beta.data_ptr(), a_mean, a_istd, scratch.data_ptr(), o_dconv, o_dg, o_db)))
+            a, o = _addresses(abase, offs[k]), _addresses(base, boffs[k])
+            lo = _addresses(abase, offs[k - 1]) if k > 0 else None                    # the block below, whose output is this layer's input
+            rows += _bn_backward_rows(b, a, o, rb.n_out, dy_ptr, gamma, beta, n_part_bwd, totals.data_ptr() + 8 * k if synced[k] else None)
             n_part_bwd = 0
-            rows.append(_row(OP_WGRAD_DEFERRED if DEFER_WGRAD_REDUCE else OP_WGRAD, i=(b.K, b.cin, b.cout, rb.n_in, x_coef[1]), n=(rb.n_out, b.cin, 1, b.K * b.cin),
-                             p=(x_in, rb.addr("nbr_out"), o_dconv, wbase + 4 * woffs[k], wscratch.data_ptr() + poffs[k], wplans[k] or None, x_coef[0])))
+            # the layer's input: the features, the block below's normalised output, or (folded) its raw conv output + the coefficients of its BatchNorm
+            x_in = features.data_ptr() if k == 0 else lo.conv if fold_in[k] else lo.y
+            rows.append(wgrad_row(X=x_in, n_src=rb.n_in, nbr=rb.addr("nbr_out"), dY=o.dconv, n_rows=rb.n_out, dW=wbase + 4 * woffs[k],
+                                  scratch=wscratch.data_ptr() + poffs[k], K=b.K, Cin=b.cin, Cout=b.cout, stride_k=b.cin, stride_cin=1, stride_cout=b.K * b.cin,
+                                  plan=wplans[k], in_coef=lo.coef if fold_in[k] else None, in_relu=int(blocks[k - 1].relu) if fold_in[k] else 0))
             if k > 0:
-                a_rows, a_perm, a_masks_p, a_tiles, g, rev = rb.plan_addrs("bwd", b.cout, b.cin)
+                dgrad = dict(n_src=rb.n_out, wfrag=frags[k].data_ptr(), n_rows=rb.n_in, K=b.K, Kd=b.cout, Nc=b.cin)
+                plan = rb.plan_addrs("bwd", b.cout, b.cin)
                 res = ext[k - 1]
                 if res is None and norm.STATS_IN_CONV and BWD_SUMS_IN_CONV:
                     # the gradient this launch writes is the whole gradient of block k-1's output: its epilogue also makes the two sums of that
                     # block's BatchNorm backward (the rows' x comes from the arena), and the BatchNorm op below starts at the combine
-                    lo = blocks[k - 1]
-                    p_conv, _, p_mean, p_istd, _ = (abase + 4 * v for v in offs[k - 1])
-                    g_lo, b_lo = params[3 * (k - 1) + 1], params[3 * (k - 1) + 2]
-                    partial = norm._scratch(lo.cout, dev).data_ptr() + 16 * lo.cout
-                    rows.append(_row(OP_DGRAD_PLANNED_BN, i=(g, b.K, b.cout, b.cin, int(bool(rev)), int(lo.relu)), n=(rb.n_out, rb.n_in),
-                                     p=(o_dconv, a_rows, a_perm, a_masks_p, a_tiles, frags[k].data_ptr(), o_dx,
-                                        p_conv, p_mean, p_istd, g_lo.data_ptr(), b_lo.data_ptr(), partial)))
+                    below = blocks[k - 1]
+                    rows.append(DGRAD_PLANNED_BN(plan, dZ=o.dconv, dY=o.dx, bn_x=lo.conv, bn_mean=lo.mean, bn_invstd=lo.istd,
+                                                 bn_gamma=params[3 * (k - 1) + 1].data_ptr(), bn_beta=params[3 * (k - 1) + 2].data_ptr(),
+                                                 bn_partial=norm.partial_address(below.cout, dev), bn_relu=int(below.relu), **dgrad))
                     n_part_bwd = n_part
                 else:
-                    rows.append(_row(OP_CONV_PLANNED, i=(g, b.K, b.cout, b.cin, 0, int(bool(rev))), n=(rb.n_out, rb.n_in),
-                                     p=(o_dconv, a_rows, a_perm, a_masks_p, a_tiles, frags[k].data_ptr(), o_dx, None,
-                                        None, None, None if res is None else res.data_ptr(), None)))
-                dy_ptr = o_dx
+                    rows.append(CONV_PLANNED(plan, X=o.dconv, Y=o.dx, residual=None if res is None else res.data_ptr(), **dgrad))
+                dy_ptr = o.dx
         # cut lists (synced norms): every segment is a call of its own, so a weight gradient joins -- and a deferred reduction runs -- at the end of its segment
-        if totals is not None:
-            _run_cut(rows, (lambda seg: _run_two_streams(seg, dev)) if WGRAD_STREAM else (lambda seg: _run(seg, "sv_run_ops (chain backward)")))
-        elif WGRAD_STREAM:
-            _run_two_streams(rows, dev)
-        else:
-            _run(rows, "sv_run_ops (chain backward)")
+        _run_cut(rows, (lambda seg: _run_two_streams(seg, dev)) if WGRAD_STREAM else (lambda seg: _run(seg, "sv_run_ops (chain backward)")))
         out = [None, None, None]
         for k, b in enumerate(blocks):
-            w = params[3 * k]
             o = boffs[k]
-            out += [wgrads[woffs[k]:woffs[k] + b.K * b.cin * b.cout].view(w.shape), work[o[2]:o[3]], work[o[3]:o[3] + b.cout]]
+            out += [wgrads[woffs[k]:woffs[k] + b.K * b.cin * b.cout].view(params[3 * k].shape), work[o.dgamma:o.dbeta], work[o.dbeta:o.dbeta + b.cout]]
         return tuple(out)
 
 
@@ -441,91 +566,6 @@ def run_chain(blocks, x):
 
 
 # ---------------------------------------------------------------------------------------------------------------- eval mode
-_residual_blocks = []
-
-
-def register_residual_block(cls):
-    """cls: a residual block class (SparseBasicBlock) whose OWN forward is relu(bn2(conv2(relu(bn1(conv1(x))))) + x) when its downsample is None;
-    flatten_eval takes instances whose forward is that very function (a subclass with a forward of its own is declined)."""
-    if cls not in _residual_blocks:
-        _residual_blocks.append(cls)
-    return cls
-
-
-class EvalEntry:
-    """One convolution of an eval list and what its epilogue applies: (conv, bn, relu, residual_from, tap).  residual_from: index of the entry whose
-    output is added before the ReLU (a residual block's identity), -1 for the chain's input, None for none; tap: the output is returned by the chain."""
-    __slots__ = ("conv", "bn", "relu", "residual_from", "tap", "K", "cin", "cout")
-
-    def __init__(self, conv, bn, relu, residual_from, tap):
-        self.conv, self.bn, self.relu, self.residual_from, self.tap = conv, bn, bool(relu), residual_from, tap
-        self.K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
-        self.cin, self.cout = conv.in_channels, conv.out_channels
-
-    def __iter__(self):
-        return iter((self.conv, self.bn, self.relu, self.residual_from, self.tap))
-
-
-def _is_residual_block(m):
-    from .conv import SparseConvolution
-    if not any(isinstance(m, cls) and type(m).forward is cls.forward for cls in _residual_blocks):
-        return False
-    c1, c2 = getattr(m, "conv1", None), getattr(m, "conv2", None)
-    return (isinstance(c1, SparseConvolution) and isinstance(c2, SparseConvolution) and c1.subm and c2.subm and c1.indice_key is not None
-            and c1.indice_key == c2.indice_key and c1.kernel_size == c2.kernel_size and c1.in_channels == c2.out_channels
-            and c1.out_channels == c2.in_channels and getattr(m, "downsample", 0) is None and type(getattr(m, "relu", None)) is torch.nn.ReLU
-            and type(getattr(m, "bn1", None)) in _EVAL_NORMS and type(getattr(m, "bn2", None)) in _EVAL_NORMS)
-
-
-_EVAL_NORMS = (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm)
-
-
-def flatten_eval(stages):
-    """stages: the backbone's stages in execution order (SparseSequential each).  -> BlockList of EvalEntry, one per convolution, or None when a stage is
-    anything but (SparseConvolution [with or without bias], BatchNorm1d | SyncBatchNorm, ReLU) triples and registered residual blocks without a
-    downsample.  The last entry of every stage is a tap."""
-    from .conv import SparseConvolution
-    from .modules import SparseSequential
-    entries = BlockList()
-    walked = []
-
-    def walk(m, out):
-        walked.append(m)
-        for child in m._modules.values():
-            if isinstance(child, SparseSequential):
-                walk(child, out)
-            else:
-                walked.append(child)
-                out.append(child)
-
-    for stage in stages:
-        if not isinstance(stage, SparseSequential):
-            return None
-        mods = []
-        walk(stage, mods)
-        j, n0 = 0, len(entries)
-        while j < len(mods):
-            m = mods[j]
-            if isinstance(m, SparseConvolution):
-                if j + 2 >= len(mods) or type(mods[j + 1]) not in _EVAL_NORMS or type(mods[j + 2]) is not torch.nn.ReLU:
-                    return None
-                entries.append(EvalEntry(m, mods[j + 1], True, None, False))
-                j += 3
-            elif _is_residual_block(m):
-                walked.extend(c for c in m._modules.values() if c is not None)      # a downsample set and cleared again stays registered as None
-                identity = len(entries) - 1                                         # -1: the block reads the chain's input
-                entries.append(EvalEntry(m.conv1, m.bn1, True, None, False))
-                entries.append(EvalEntry(m.conv2, m.bn2, True, identity, False))
-                j += 1
-            else:
-                return None
-        if len(entries) == n0:
-            return None
-        entries[-1].tap = True
-    entries.walked = tuple(walked)
-    return entries
-
-
 def eval_applicable(entries, x):
     """The eval list takes these entries on x now: SEEVCN_CHAIN and SEEVCN_EVAL_CHAIN not 0, gradients disabled, fp32 CUDA features with at least one row,
     no hooks on anything walked, every norm in eval mode with running statistics on a channel count the fused BatchNorm kernels take (what the module
@@ -540,7 +580,7 @@ def eval_applicable(entries, x):
     rows = [f.shape[0]]                                                              # rows[k + 1]: rows of entry k's output; rows[0]: of the input
     for e in entries:
         bn, w = e.bn, e.conv.weight
-        if (type(bn) not in _EVAL_NORMS or bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None
+        if (norm.route(bn) is None or bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None
                 or bn.num_features != e.cout or not norm.channels_fusable(e.cout) or bn.momentum is None or not bn.running_mean.is_cuda):
             return False
         if not (w.is_cuda and w.dtype == torch.float32) or e.conv.indice_key is None:
@@ -580,7 +620,7 @@ def run_eval_chain(entries, x):
     y_addr = [(arena if e.tap else work).data_ptr() + 4 * y_offs[k] for k, e in enumerate(entries)]
     base = work.data_ptr()
     jobs = np.zeros((L, 8), dtype=np.int64)
-    rows = [_row(OP_BN_EVAL_COEF_BATCH, i=(L,), p=(jobs.ctypes.data,))]               # the table is host memory, read inside the call below
+    rows = [BN_EVAL_COEF_BATCH(jobs_host=jobs.ctypes.data, n_jobs=L)]
     keep = []
     x_ptr, n_src = features.data_ptr(), features.shape[0]
     for k, (e, rb) in enumerate(zip(entries, rulebooks)):
@@ -590,18 +630,7 @@ def run_eval_chain(entries, x):
                        bn.running_var.data_ptr(), o_coef, e.cout, _bits(bn.eps))
         bias = None if conv.bias is None else conv.bias.data_ptr()
         res = None if e.residual_from is None else (features.data_ptr() if e.residual_from < 0 else y_addr[e.residual_from])
-        wk = conv.weight_kio_nograd()
-        plan = rb.plan_addrs("fwd", e.cin, e.cout)
-        if plan is not None:
-            a_rows, a_perm, a_masks_p, a_tiles, g, rev = plan
-            ff, _ = Fsp.fragment_cache.get(wk)
-            rows.append(_row(OP_CONV_PLANNED, i=(g, e.K, e.cin, e.cout, int(e.relu), int(bool(rev))), n=(n_src, rb.n_out),
-                             p=(x_ptr, a_rows, a_perm, a_masks_p, a_tiles, ff.data_ptr(), o_y, bias, o_coef, o_coef + 4 * e.cout, res, None)))
-        else:
-            wt = wk.detach().permute(0, 2, 1).contiguous()                           # (K, C_out, C_in): the 3/4/5-channel input layer only
-            keep.append(wt)
-            rows.append(_row(OP_CONV_PLAIN, i=(e.K, e.cin, e.cout, int(e.relu)), n=(n_src, rb.n_out),
-                             p=(x_ptr, rb.addr("nbr_out"), wt.data_ptr(), o_y, bias, o_coef, o_coef + 4 * e.cout, res)))
+        rows.append(_conv_row(e, rb, keep, x_ptr, n_src, o_y, relu=int(e.relu), bias=bias, scale=o_coef, shift=o_coef + 4 * e.cout, residual=res)[0])
         x_ptr, n_src = o_y, rb.n_out
     _run(rows, "sv_run_ops (eval chain)")
     return [SparseConvTensor(arena[y_offs[k]:y_offs[k] + rb.n_out * e.cout].view(rb.n_out, e.cout), rb.out_indices, rb.out_shape, x.batch_size, x.grid,

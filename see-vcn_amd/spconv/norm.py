@@ -182,9 +182,8 @@ def channels_fusable(c):
 
 
 def fusable(bn, x):
-    c = x.shape[1] if x.dim() == 2 else 0
     return (route(bn, subclasses=True) is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0
-            and c >= 4 and c <= 512 and c % 4 == 0 and 256 % (c // 4) == 0 and bn.momentum is not None
+            and channels_fusable(x.shape[1]) and bn.momentum is not None
             and (bn.training or bn.track_running_stats) and (not x.requires_grad or bn.training))
 
 

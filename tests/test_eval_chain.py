@@ -1,4 +1,4 @@
-"""Eval-mode sparse backbones as one launch list with folded BatchNorm (seevcn_amd/spconv/chain.py: flatten_eval / eval_applicable / run_eval_chain),
+"""Eval-mode sparse backbones as one launch list with folded BatchNorm (seevcn_amd/spconv/chain.py: flatten / eval_applicable / run_eval_chain),
 the one-launch eval coefficients (sv_batchnorm_eval_coef_batch) and the whole-row store path of the planned conv kernel's epilogue.  The module path
 (SEEVCN_EVAL_CHAIN=0) is the bitwise reference of the chain, the float64 oracle (oracle/spconv.py) the reference of both."""
 import re
@@ -38,23 +38,29 @@ def test_eval_coef_batch_is_declared_exported_and_bound(hip_lib):
     assert hip_lib.sv_batchnorm_eval_coef_batch(None, 0, None) == 0                 # no jobs: nothing is launched, no device is touched
 
 
-def test_flatten_eval_of_both_backbones():
+def test_flatten_of_both_backbones():
     """12 / 21 entries, every one with a ReLU; the identity of a residual block is the entry in front of the block; taps behind conv1..conv4 and conv_out."""
     from seevcn_amd.spconv import chain
     from seevcn_amd.spconv.conv import SparseConvolution
     m = _backbone("VoxelBackBone8x")
-    e = m._eval_entries()
+    e = m._chain_blocks()
     assert len(e) == 12 and all(x.relu for x in e) and all(x.residual_from is None for x in e)
     assert [k for k, x in enumerate(e) if x.tap] == [1, 4, 7, 10, 11]
     assert [x.conv for x in e] == [mod for mod in m.modules() if isinstance(mod, SparseConvolution)]          # execution order = definition order
     conv, bn, relu, residual_from, tap = e[0]                                       # an entry unpacks as the five fields
     assert conv is m.conv_input[0] and bn is m.conv_input[1] and relu is True and residual_from is None and tap is False
-    # flatten_eval itself: the last entry of EVERY stage is a tap (the backbone clears conv_input's)
-    raw = chain.flatten_eval([getattr(m, s) for s in STAGES])
+    # flatten itself: the last entry of EVERY stage is a tap (the backbone clears conv_input's)
+    raw = chain.flatten([getattr(m, s) for s in STAGES])
     assert [k for k, x in enumerate(raw) if x.tap] == [0, 1, 4, 7, 10, 11]
+    # the training chain reads the same list: no residual identity in it, plain or after convert_sync_batchnorm (chain.applicable declines one that has)
+    s = torch.nn.SyncBatchNorm.convert_sync_batchnorm(_backbone("VoxelBackBone8x"))
+    es = s._chain_blocks()
+    assert len(es) == 12 and all(x.residual_from is None for x in es) and all(type(x.bn) is torch.nn.SyncBatchNorm for x in es)
+    assert [k for k, x in enumerate(es) if x.tap] == [1, 4, 7, 10, 11] and len(es.walked) == len(e.walked)
+    assert isinstance(e[0].mom_eps, tuple) and e[0].mom_eps == (chain._bits(0.01), chain._bits(1e-3))
 
     r = _backbone("VoxelResBackBone8x", 5, [1440, 1440, 40])
-    e = r._eval_entries()
+    e = r._chain_blocks()
     assert len(e) == 21 and all(x.relu for x in e)
     want_res = {2: 0, 4: 2, 7: 5, 9: 7, 12: 10, 14: 12, 17: 15, 19: 17}              # conv2 of every block <- the entry in front of its conv1
     assert {k: x.residual_from for k, x in enumerate(e) if x.residual_from is not None} == want_res
@@ -65,17 +71,17 @@ def test_flatten_eval_of_both_backbones():
         assert x.cin == x.conv.in_channels and x.cout == x.conv.out_channels and x.bn.num_features == x.cout
     assert set(e.walked) >= {r.conv1, blk, blk.conv1, blk.bn1, blk.relu, blk.conv2, blk.bn2, r.conv_out[0]}
     # a chain whose first module is a residual block reads the chain's input as the identity
-    first = chain.flatten_eval([r.conv1])
+    first = chain.flatten([r.conv1])
     assert [x.residual_from for x in first] == [None, -1, None, 1] and first[-1].tap
 
 
-def test_flatten_eval_declines_what_it_cannot_fold():
+def test_flatten_declines_what_it_cannot_fold():
     import seevcn_amd.spconv as spconv
     from seevcn_amd.pcdet.models.backbones_3d.spconv_backbone import SparseBasicBlock
     from seevcn_amd.spconv import chain
     norm_fn = partial(torch.nn.BatchNorm1d, eps=1e-3, momentum=0.01)
     down = spconv.SparseSequential(spconv.SubMConv3d(16, 16, 1, bias=False, indice_key="d"), norm_fn(16))
-    assert chain.flatten_eval([spconv.SparseSequential(SparseBasicBlock(16, 16, norm_fn=norm_fn, downsample=down, indice_key="r"))]) is None
+    assert chain.flatten([spconv.SparseSequential(SparseBasicBlock(16, 16, norm_fn=norm_fn, downsample=down, indice_key="r"))]) is None
 
     class OwnForward(SparseBasicBlock):
         def forward(self, x):
@@ -84,26 +90,26 @@ def test_flatten_eval_declines_what_it_cannot_fold():
     class SameForward(SparseBasicBlock):
         pass
 
-    assert chain.flatten_eval([spconv.SparseSequential(OwnForward(16, 16, norm_fn=norm_fn, indice_key="r"))]) is None
-    assert len(chain.flatten_eval([spconv.SparseSequential(SameForward(16, 16, norm_fn=norm_fn, indice_key="r"))])) == 2
+    assert chain.flatten([spconv.SparseSequential(OwnForward(16, 16, norm_fn=norm_fn, indice_key="r"))]) is None
+    assert len(chain.flatten([spconv.SparseSequential(SameForward(16, 16, norm_fn=norm_fn, indice_key="r"))])) == 2
     # conv -> norm without the ReLU, a GroupNorm, a bare ReLU, something that is no SparseSequential
     conv = lambda: spconv.SubMConv3d(16, 16, 3, bias=True, indice_key="s")
-    assert chain.flatten_eval([spconv.SparseSequential(conv(), norm_fn(16))]) is None
-    assert chain.flatten_eval([spconv.SparseSequential(conv(), torch.nn.GroupNorm(4, 16), torch.nn.ReLU())]) is None
-    assert chain.flatten_eval([spconv.SparseSequential(torch.nn.ReLU())]) is None
-    assert chain.flatten_eval([torch.nn.Sequential()]) is None and chain.flatten_eval([spconv.SparseSequential()]) is None
-    ok = chain.flatten_eval([spconv.SparseSequential(conv(), norm_fn(16), torch.nn.ReLU())])              # a conv bias is taken
+    assert chain.flatten([spconv.SparseSequential(conv(), norm_fn(16))]) is None
+    assert chain.flatten([spconv.SparseSequential(conv(), torch.nn.GroupNorm(4, 16), torch.nn.ReLU())]) is None
+    assert chain.flatten([spconv.SparseSequential(torch.nn.ReLU())]) is None
+    assert chain.flatten([torch.nn.Sequential()]) is None and chain.flatten([spconv.SparseSequential()]) is None
+    ok = chain.flatten([spconv.SparseSequential(conv(), norm_fn(16), torch.nn.ReLU())])              # a conv bias is taken
     assert len(ok) == 1 and ok[0].conv.bias is not None and ok[0].tap
     # the backbone re-flattens when a module is assigned (registration epoch): a downsample set later sends it to the module tree
     r = _backbone("VoxelResBackBone8x")
-    assert len(r._eval_entries()) == 21
+    assert len(r._chain_blocks()) == 21
     r.conv3[1].downsample = down
-    assert r._eval_entries() is None
+    assert r._chain_blocks() is None
     r.conv3[1].downsample = None
-    assert len(r._eval_entries()) == 21
+    assert len(r._chain_blocks()) == 21
     # ... and the cleared slot stays registered as None in the block's _modules: it is not among the modules whose hooks are looked at
-    assert "downsample" in r.conv3[1]._modules and None not in r._eval_entries().walked
-    assert not any(chain._has_hooks(mod) for mod in r._eval_entries().walked)
+    assert "downsample" in r.conv3[1]._modules and None not in r._chain_blocks().walked
+    assert not any(chain._has_hooks(mod) for mod in r._chain_blocks().walked)
 
 
 # ---------------------------------------------------------------------------------- 2. coefficients
@@ -251,7 +257,7 @@ def test_hip_eval_chain_vs_module_path_vs_float64(cuda, hip_lib, monkeypatch, na
     m.load_state_dict(sd)
     m = m.to(cuda).eval()
     before = _state_snapshot(m)
-    assert sum(1 for _ in m._eval_entries()) == n_convs
+    assert sum(1 for _ in m._chain_blocks()) == n_convs
     chain_taps, calls = _run_backbone(m, bd, monkeypatch, on=True)
     assert calls == [n_convs + 1], calls                                            # the test that fails without the feature
     module_taps, calls_off = _run_backbone(m, bd, monkeypatch, on=False)
@@ -374,7 +380,7 @@ def test_hip_eval_chain_stands_down(cuda, hip_lib, monkeypatch):
     m4.conv3[1].downsample = down
     got, calls = _run_backbone(m4, bd, monkeypatch, on=True)
     ref, _ = _run_backbone(m4, bd, monkeypatch, on=False)
-    assert calls == [] and m4._eval_entries() is None
+    assert calls == [] and m4._chain_blocks() is None
     _assert_same_taps(got, ref, "downsample")
     assert not torch.equal(got["x_conv3"].features, want["x_conv3"].features)       # the downsample branch took part
 
@@ -390,7 +396,7 @@ def test_hip_eval_chain_stands_down(cuda, hip_lib, monkeypatch):
     m5.conv3.add_module("2", blk.to(cuda).eval())
     got, calls = _run_backbone(m5, bd, monkeypatch, on=True)
     ref, _ = _run_backbone(m5, bd, monkeypatch, on=False)
-    assert calls == [] and m5._eval_entries() is None
+    assert calls == [] and m5._chain_blocks() is None
     _assert_same_taps(got, ref, "own forward")
     assert torch.equal(got["x_conv3"].features, want["x_conv3"].features * 2.0)
 
@@ -399,7 +405,7 @@ def test_hip_eval_chain_stands_down(cuda, hip_lib, monkeypatch):
     m6 = build()
     m6.conv3[1].downsample = down
     m6.conv3[1].downsample = None
-    assert "downsample" in m6.conv3[1]._modules and len(m6._eval_entries()) == 21
+    assert "downsample" in m6.conv3[1]._modules and len(m6._chain_blocks()) == 21
     got, calls = _run_backbone(m6, bd, monkeypatch, on=True)
     ref, calls_off = _run_backbone(m6, bd, monkeypatch, on=False)
     assert calls == [22] and calls_off == []

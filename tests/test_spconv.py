@@ -1075,6 +1075,91 @@ def test_hip_launch_list_executor_runs_in_order_and_reports_errors(cuda, hip_lib
         chain._run([chain._row(chain.OP_BN_FWD, i=(c, 1, 1, 0), n=(n,), f=me)], "null pointers")
 
 
+def test_launch_row_layout():
+    """Every row constructor of spconv/chain.py puts each field at the word csrc/sequencer.hip reads it from (include/seevcn_hip.h, "launch-list executor":
+    [0] code, [1..8] i0..i7, [9..12] n0..n3, [13..16] f0..f3, [17..31] p0..p14), the words bench.py reads by number included.  No device, no library."""
+    from seevcn_amd.spconv import chain
+    I, N, F, P = 1, 9, 13, 17
+    plan = {"table_rows": P + 1, "perm": P + 2, "masks_p": P + 3, "tile_of": P + 4, "tiles_per_wave": I + 0}           # + table_k_reversed, a flag
+    bn = {"gamma": P + 1, "beta": P + 2, "running_mean": P + 3, "running_var": P + 4}
+    bwd = {"x": P + 0, "dy": P + 1, "gamma": P + 2, "beta": P + 3, "save_mean": P + 4, "save_invstd": P + 5, "scratch": P + 6, "rows": N + 0, "channels": I + 0,
+           "relu": I + 1}
+    wgrad = {"X": P + 0, "nbr": P + 1, "dY": P + 2, "dW": P + 3, "scratch": P + 4, "plan": P + 5, "in_coef": P + 6, "n_rows": N + 0, "stride_k": N + 1,
+             "stride_cin": N + 2, "stride_cout": N + 3, "K": I + 0, "Cin": I + 1, "Cout": I + 2, "n_src": I + 3, "in_relu": I + 4}
+    layout = {          # constructor: (code, word of the plan's table_k_reversed flag or None, {field: word})
+        chain.CONV_PLANNED: (1, I + 5, {**plan, "X": P + 0, "wfrag": P + 5, "Y": P + 6, "bias": P + 7, "scale": P + 8, "shift": P + 9, "residual": P + 10,
+                                        "bn_partial": P + 11, "in_coef": P + 12, "n_src": N + 0, "n_rows": N + 1, "K": I + 1, "Kd": I + 2, "Nc": I + 3,
+                                        "relu": I + 4, "in_relu": I + 6}),
+        chain.CONV_PLAIN: (2, None, {"X": P + 0, "nbr": P + 1, "Wt": P + 2, "Y": P + 3, "bias": P + 4, "scale": P + 5, "shift": P + 6, "residual": P + 7,
+                                     "n_src": N + 0, "n_rows": N + 1, "K": I + 0, "Kd": I + 1, "Nc": I + 2, "relu": I + 3}),
+        chain.BN_FWD: (3, None, {**bn, "x": P + 0, "scratch": P + 5, "y": P + 6, "save_mean": P + 7, "save_invstd": P + 8, "num_batches_tracked": P + 9,
+                                 "rows": N + 0, "channels": I + 0, "training": I + 1, "relu": I + 2, "n_partials": I + 3}),
+        chain.BN_BWD: (5, None, {**bwd, "dx": P + 7, "dgamma": P + 8, "dbeta": P + 9, "n_partials": I + 2}),
+        chain.WGRAD: (6, None, wgrad),
+        chain.DGRAD_PLANNED_BN: (7, I + 4, {**plan, "dZ": P + 0, "wfrag": P + 5, "dY": P + 6, "bn_x": P + 7, "bn_mean": P + 8, "bn_invstd": P + 9,
+                                            "bn_gamma": P + 10, "bn_beta": P + 11, "bn_partial": P + 12, "n_src": N + 0, "n_rows": N + 1, "K": I + 1,
+                                            "Kd": I + 2, "Nc": I + 3, "bn_relu": I + 5}),
+        chain.WGRAD_DEFERRED: (8, None, wgrad),
+        chain.BN_FINALIZE: (9, None, {"gamma": P + 0, "beta": P + 1, "running_mean": P + 2, "running_var": P + 3, "scratch": P + 4, "coef": P + 5,
+                                      "save_mean": P + 6, "save_invstd": P + 7, "num_batches_tracked": P + 8, "x": P + 9, "rows": N + 0, "channels": I + 0,
+                                      "n_partials": I + 1}),
+        chain.BN_APPLY: (10, None, {"x": P + 0, "coef": P + 1, "y": P + 2, "rows": N + 0, "channels": I + 0, "relu": I + 1}),
+        chain.BN_STATS_LOCAL: (11, None, {"x": P + 0, "scratch": P + 1, "sums": P + 2, "rows": N + 0, "channels": I + 0, "n_partials": I + 1}),
+        chain.BN_FINALIZE_GLOBAL: (12, None, {**bn, "gathered": P + 0, "coef": P + 5, "save_mean": P + 6, "save_invstd": P + 7, "num_batches_tracked": P + 8,
+                                              "total_rows": P + 9, "channels": I + 0, "world": I + 1}),
+        chain.BN_BWD_SUMS_LOCAL: (13, None, {**bwd, "dgamma": P + 7, "dbeta": P + 8, "sums": P + 9, "n_partials": I + 2}),
+        chain.BN_BWD_APPLY_GLOBAL: (14, None, {**bwd, "gathered": P + 7, "total_rows": P + 8, "dx": P + 9, "world": I + 2}),
+        chain.BN_EVAL_COEF_BATCH: (15, None, {"jobs_host": P + 0, "n_jobs": I + 0}),
+    }
+    codes = [getattr(chain, "OP_" + name) for name in ("CONV_PLANNED CONV_PLAIN BN_FWD BN_BWD WGRAD DGRAD_PLANNED_BN WGRAD_DEFERRED BN_FINALIZE BN_APPLY "
+                                                      "BN_STATS_LOCAL BN_FINALIZE_GLOBAL BN_BWD_SUMS_LOCAL BN_BWD_APPLY_GLOBAL BN_EVAL_COEF_BATCH").split()]
+    assert codes == [code for code, _, _ in layout.values()]                      # the values of include/seevcn_hip.h's #defines, in this order
+    with_mom_eps = (chain.BN_FWD, chain.BN_FINALIZE, chain.BN_FINALIZE_GLOBAL)
+    rows = {}
+    for make, (code, flag_word, words) in layout.items():
+        assert len(set(words.values())) == len(words), code                         # one word per field
+        for reversed_flag in (False, True):
+            value = {name: 1000 + 7 * q for q, name in enumerate(sorted(words))}    # a distinct sentinel per field
+            kwargs = {name: v for name, v in value.items() if name not in plan or flag_word is None}
+            args = ()
+            if flag_word is not None:
+                args = ((value["table_rows"], value["perm"], value["masks_p"], value["tile_of"], value["tiles_per_wave"], reversed_flag),)
+            if make in with_mom_eps:
+                kwargs["mom_eps"] = (chain._bits(0.01), chain._bits(1e-3))
+            row = make(*args, **kwargs)
+            want = [0] * chain.WORDS
+            want[0] = code
+            for name, w in words.items():
+                want[w] = value[name]
+            if flag_word is not None:
+                want[flag_word] = int(reversed_flag)
+            if make in with_mom_eps:
+                want[F:F + 2] = kwargs["mom_eps"]
+            assert list(row) == want and len(row) == chain.WORDS == 32 and all(type(v) is int for v in row), (code, row, want)
+            np.array([row], dtype=np.int64)
+        rows[code], rows[code, "value"] = row, value
+    # optional fields are null / 0 when they are not given
+    row = chain.CONV_PLANNED((1, 2, 3, 4, 5, False), X=6, n_src=7, wfrag=8, Y=9, n_rows=10, K=27, Kd=16, Nc=32)
+    assert row[I + 4] == row[I + 6] == 0 and row[P + 7:P + 13] == [0] * 6 and row[P + 13:] == [0, 0]
+    row = chain.CONV_PLAIN(X=6, n_src=7, nbr=1, Wt=8, Y=9, n_rows=10, K=27, Kd=3, Nc=16)
+    assert row[I + 3] == 0 and row[P + 4:] == [0] * 11
+    row = chain.WGRAD(X=6, n_src=7, nbr=1, dY=2, n_rows=3, dW=4, scratch=5, K=27, Cin=16, Cout=16, stride_k=16, stride_cin=1, stride_cout=432)
+    assert row[0] == 6 and row[I + 4] == 0 and row[P + 5:] == [0] * 10
+    # the words bench.py (measure_spconv_kernel) reads by number
+    for code in (chain.OP_CONV_PLANNED, chain.OP_DGRAD_PLANNED_BN):
+        r, v = rows[code], rows[code, "value"]
+        assert (r[2], r[3], r[4], r[9], r[10], r[18]) == (v["K"], v["Kd"], v["Nc"], v["n_src"], v["n_rows"], v["table_rows"])
+    for code in (chain.OP_WGRAD, chain.OP_WGRAD_DEFERRED):
+        r, v = rows[code], rows[code, "value"]
+        assert (r[1], r[2], r[3], r[4], r[9], r[18], r[22]) == (v["K"], v["Cin"], v["Cout"], v["n_src"], v["n_rows"], v["nbr"], v["plan"])
+    # the input transform: p12 / i6 of a planned conv, p6 / i4 of a weight gradient
+    r, v = rows[chain.OP_CONV_PLANNED], rows[chain.OP_CONV_PLANNED, "value"]
+    assert (r[17 + 12], r[1 + 6]) == (v["in_coef"], v["in_relu"])
+    for code in (chain.OP_WGRAD, chain.OP_WGRAD_DEFERRED):
+        r, v = rows[code], rows[code, "value"]
+        assert (r[17 + 6], r[1 + 4]) == (v["in_coef"], v["in_relu"])
+
+
 def _same_rulebook(a, b, tag):
     assert a.subm == b.subm and a.n_in == b.n_in and a.n_out == b.n_out and list(a.out_shape) == list(b.out_shape) and a.ksize == b.ksize, tag
     for name in ("out_indices", "nbr_in", "nbr_out", "rows_in", "rows_out", "masks_in", "masks_out"):
@@ -1238,6 +1323,51 @@ def test_hip_chain_stands_down_for_hooks_on_any_walked_module(cuda, hip_lib):
     net.conv3[1][1].momentum = None
     out = run()['encoded_spconv_tensor'].features                  # no TypeError: module path, torch's cumulative moving average
     assert type(out.grad_fn).__name__ != "SparseChainFunctionBackward" and torch.isfinite(out).all()
+
+
+@pytest.mark.gpu
+def test_hip_residual_backbone_trains_on_the_module_tree(cuda, hip_lib):
+    """The training chain and the eval list read one flattened list, and only the eval list carries a residual block's identity: a training step of
+    VoxelResBackBone8x asks chain.applicable about its list (21 entries, 8 identities), is declined and walks the module tree -- chain.run_chain is not
+    called; the same step of VoxelBackBone8x is one run_chain call.  With every conv bias taken away (fusable_with declines a bias on its own) the
+    residual identities alone decline: the same list on the same input is taken once they are cleared."""
+    import seevcn_amd.synth as synth
+    from seevcn_amd.pcdet.models import backbones_3d
+    from seevcn_amd.pcdet.ops import voxel_ops
+    from seevcn_amd.spconv import chain
+    from seevcn_amd.spconv.conv import SparseConvolution
+    pts, _ = synth.make_scene_batch(2, seed=2006, n_az=96)
+    g = dict(point_cloud_range=[0, -40, -3, 70.4, 40, 1], voxel_size=[0.05, 0.05, 0.1], grid_size=[1408, 1600, 40])
+    f, c, _ = voxel_ops.voxelize_dynamic(torch.from_numpy(pts).to(cuda), g["point_cloud_range"], g["voxel_size"], g["grid_size"], 2)
+    calls, asked = [], []
+    run_chain, applicable = chain.run_chain, chain.applicable
+    chain.run_chain = lambda *a: calls.append(1) or run_chain(*a)
+    chain.applicable = lambda blocks, x: asked.append((blocks, x, applicable(blocks, x))) or asked[-1][2]
+    saved, chain.CHAIN_OFF = chain.CHAIN_OFF, False
+    try:
+        for name, no_bias, want_calls in (("VoxelResBackBone8x", False, 0), ("VoxelResBackBone8x", True, 0), ("VoxelBackBone8x", False, 1)):
+            torch.manual_seed(0)
+            net = backbones_3d.__all__[name]({}, 3, g['grid_size']).to(cuda).train()
+            if no_bias:
+                for m in net.modules():
+                    if isinstance(m, SparseConvolution):
+                        m.bias = None
+            del calls[:], asked[:]
+            out = net({'batch_size': 2, 'voxel_features': f.clone(), 'voxel_coords': c.clone()})['encoded_spconv_tensor'].features
+            out.square().sum().backward()
+            (blocks, x, took), = asked
+            assert blocks is net._chain_blocks() and blocks is not None and took == bool(want_calls) and len(calls) == want_calls, (name, no_bias)
+            assert (type(out.grad_fn).__name__ == "SparseChainFunctionBackward") == bool(want_calls)
+            assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
+            if name == "VoxelResBackBone8x":
+                assert len(blocks) == 21 and sum(e.residual_from is not None for e in blocks) == 8
+                assert applicable(blocks, x) is False
+                if no_bias:
+                    for e in blocks:
+                        e.residual_from = None
+                    assert applicable(blocks, x) is True
+    finally:
+        chain.run_chain, chain.applicable, chain.CHAIN_OFF = run_chain, applicable, saved
 
 
 @pytest.mark.gpu
