@@ -34,6 +34,10 @@ extern "C" {
 
 int sv_abi_version(void);
 const char* sv_last_error(void);
+/* 1 when the library is the measurement build (`make measure`, libseevcn_hip_measure.so): only that build has the debug / trace kernel
+ * instances, sv_debug_conv_trace / sv_debug_wgrad_trace and the environment switches that change results or skip launches (INTEGRATION.md,
+ * "measurement build").  0: the production build, which answers to none of them. */
+int sv_measure_build(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Coordinate index (persistent workspace shared by voxelisation and rulebook builds)
@@ -296,11 +300,12 @@ int sv_sparse_conv_dgrad_planned_bn(const float* dZ, int64_t n_src, const int32_
 int sv_conv_planned_partials(void);
 /* Measurement aid (tools/conv_trace.py): while buf is non-null every wave of sv_sparse_conv_gather_gemm_planned writes 8 uint64 to it
  * (s_memtime at start / after the prologue / after the main loop / at the end, HW_ID, XCC_ID, tile-offset steps, block << 8 | wave);
- * buf holds grid.x * grid.y * 4 slots of 64 bytes (size it as 8 * (n_tiles + 64) * columns / 64 slots).  Not for production use. */
+ * buf holds grid.x * grid.y * 4 slots of 64 bytes (size it as 8 * (n_tiles + 64) * columns / 64 slots).  Measurement build only
+ * (sv_measure_build() == 1); the production library returns SV_ERR_ARG. */
 int sv_debug_conv_trace(void* buf);
 /* The same for the MFMA weight gradient (tools/wgrad_trace.py; the 64 -> 64 channel instance only): per wave s_memtime at start, ticks spent in the
  * pass prologues (table read + compaction), ticks in the MFMA loops, s_memtime at the end, XCC_ID << 32 | HW_ID, s_memtime after the last pass,
- * passes << 32 | pairs, offset << 32 | chunk; buf holds 4 x workgroups slots of 64 bytes.  Not for production use. */
+ * passes << 32 | pairs, offset << 32 | chunk; buf holds 4 x workgroups slots of 64 bytes.  Measurement build only, like sv_debug_conv_trace. */
 int sv_debug_wgrad_trace(void* buf);
 /* dW (K, C_in, C_out) = sum_o X[nbr[k][o]]^T dY[o]; deterministic two-stage reduction.  n_src = rows of X (every table entry is < n_src): when
  * n_src * C_in * 4 < 2^32 the operand rows are addressed with 32-bit byte offsets from uniform bases; n_src <= 0 = unknown (64-bit addresses). */

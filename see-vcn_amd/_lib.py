@@ -23,6 +23,7 @@ c_sz = ctypes.c_size_t
 SIGNATURES = {
     "sv_abi_version": (c_i, []),
     "sv_last_error": (ctypes.c_char_p, []),
+    "sv_measure_build": (c_i, []),
     "sv_index_persistent_bytes": (c_sz, [c_i64]),
     "sv_index_scratch_bytes": (c_sz, [c_i64]),
     "sv_voxelize_dynamic_scratch_bytes": (c_sz, [c_i64, c_i64, c_i64]),
@@ -216,6 +217,17 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+# switches and entry points that only the measurement build of the library has (csrc/Makefile, target `measure`)
+MEASURE_SWITCHES = ("SEEVCN_RS3_DEBUG", "SEEVCN_PLAN_DEBUG", "SEEVCN_WGRAD_DEBUG", "SEEVCN_WGRAD_SKIP", "SEEVCN_DEBUG_SKIP_FINALIZE")
+
+
+def require_measure_build(who):
+    """For measurement tools: exit with one line unless the loaded library is the measurement build."""
+    if not load().sv_measure_build():
+        raise SystemExit(f"{who}: needs the measurement build of the library (make -C see-vcn_amd/csrc measure, then "
+                         f"SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so); {LIB_PATH} is a production build")
 
 
 def check(rc, what):

@@ -16,6 +16,14 @@ void sv_set_error(const char* fmt, ...) {
 
 extern "C" const char* sv_last_error(void) { return g_err; }
 extern "C" int sv_abi_version(void) { return SV_ABI_VERSION; }
+// 1: the measurement build (make measure, -DSEEVCN_MEASURE=1), the only one with the debug / trace kernel instances and the switches that skip work
+extern "C" int sv_measure_build(void) {
+#if SEEVCN_MEASURE
+  return 1;
+#else
+  return 0;
+#endif
+}
 
 extern "C" size_t sv_index_persistent_bytes(int64_t ncells) {
   const int64_t nchunks = sv_index_nchunks(ncells);

@@ -872,8 +872,7 @@ extern "C" int sv_rulebook_chain_count(const int32_t* coords0, int64_t n0, const
     const int blocks = (int)((nchunks + CH_BLOCK - 1) / CH_BLOCK);
     int4* s4 = reinterpret_cast<int4*>(sites[l]);
     hipLaunchKernelGGL(k_chain_count, dim3(blocks), dim3(RB_THREADS), 0, st, ix[l], nchunks, sums);
-    static const int emit_split = getenv("SEEVCN_EMIT_SPLIT") ? atoi(getenv("SEEVCN_EMIT_SPLIT")) : CH_EMIT_SPLIT;       // A/B: 1 = one workgroup per block
-    hipLaunchKernelGGL(k_chain_emit, dim3(blocks, emit_split < 1 ? 1 : emit_split), dim3(RB_THREADS), 0, st, ix[l], nchunks, sums, s4, caps[l], num_out + l, g[l]);
+    hipLaunchKernelGGL(k_chain_emit, dim3(blocks, CH_EMIT_SPLIT), dim3(RB_THREADS), 0, st, ix[l], nchunks, sums, s4, caps[l], num_out + l, g[l]);
     if (l + 1 < n_levels) {
       // the next level's marks from the sites just written; their number is num_out[l] on the device, the grid is sized for the capacity
       const dim3 grid(sv_grid_1d(caps[l], RB_THREADS, 2048));

@@ -140,11 +140,13 @@ static int run_ops(const int64_t* ops, int n_ops, void* stream, void* side_strea
                                         ptr_of<float>(p[7]), ptr_of<float>(p[8]), ptr_of<float>(p[9]), stream);
         break;
       case SV_OP_BN_FINALIZE: {
-        // MEASUREMENT ONLY (results are stale after the first calls): SEEVCN_DEBUG_SKIP_FINALIZE=n skips the launch from the n-th call on -- what the step would
-        // gain if the statistics' combine cost the chain nothing
+#if SEEVCN_MEASURE
+        // measurement build (results are stale after the first calls): SEEVCN_DEBUG_SKIP_FINALIZE=n skips the launch from the n-th call on -- what the step
+        // would gain if the statistics' combine cost the chain nothing
         static const int skip_after = getenv("SEEVCN_DEBUG_SKIP_FINALIZE") ? atoi(getenv("SEEVCN_DEBUG_SKIP_FINALIZE")) : 0;
         static int calls = 0;
         if (skip_after > 0 && ++calls > skip_after && !p[9]) break;
+#endif
         rc = sv_batchnorm_finalize_forward(ptr_of<const float>(p[9]), n[0], (int)i[0], ptr_of<const float>(p[0]), ptr_of<const float>(p[1]), ptr_of<float>(p[2]), ptr_of<float>(p[3]),
                                            (float)as_double(f[0]), (float)as_double(f[1]), ptr_of<void>(p[4]), (int)i[1], ptr_of<float>(p[5]), ptr_of<float>(p[6]),
                                            ptr_of<float>(p[7]), ptr_of<int64_t>(p[8]), stream);

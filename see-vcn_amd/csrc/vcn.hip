@@ -448,15 +448,13 @@ static int gemm_launch(const float* A, int lda, const float* W, int ldw, const f
   SV_CHECK_ARG(act >= 0 && act <= 2, "gemm_bias_act: unknown activation %d", act);
   GemmArgs g{A, lda, W, ldw, bias, group_bias, rows_per_group, row_group, C, ldc, group_max, M, N, K, act, slope, m_dev, 0, 0, 0};
   // tile shape: from M when the host knows it; with the row count on the device the kernel chooses (mode -1) and the 1-D grid covers the finest
-  // tiling of the capacity.  SEEVCN_GEMM_TILES=0: 128 x 128 always (A/B runs)
-  static const bool big_only = getenv("SEEVCN_GEMM_TILES") && atoi(getenv("SEEVCN_GEMM_TILES")) == 0;
-  g.tile_mode = big_only ? 0 : (m_dev ? -1 : gemm_tile_mode(M, N));
+  // tiling of the capacity
+  g.tile_mode = m_dev ? -1 : gemm_tile_mode(M, N);
   const int wgs = g.tile_mode < 0 ? std::max(std::max(gemm_tiles(M, N, 0), gemm_tiles(M, N, 1)), gemm_tiles(M, N, 2)) : gemm_tiles(M, N, g.tile_mode);
   dim3 grid(wgs);
   hipStream_t st = sv_stream(stream);
   if (M <= 64 && C && !group_max && !group_bias && !row_group && !m_dev) {
-    static const int small_waves = getenv("SEEVCN_GEMM_SMALL_WAVES") ? atoi(getenv("SEEVCN_GEMM_SMALL_WAVES")) : 0;      // 4 / 16: A/B runs
-    if (small_waves == 16 || (small_waves != 4 && K >= 512)) hipLaunchKernelGGL(k_gemm_small_m<16>, dim3(sv_div_up(N, 16)), dim3(1024), 0, st, g);
+    if (K >= 512) hipLaunchKernelGGL(k_gemm_small_m<16>, dim3(sv_div_up(N, 16)), dim3(1024), 0, st, g);
     else hipLaunchKernelGGL(k_gemm_small_m<4>, dim3(sv_div_up(N, 16)), dim3(256), 0, st, g);
     SV_LAUNCH_CHECK();
     return SV_OK;

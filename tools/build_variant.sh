@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <name> "<extra hipcc flags>" [source, default sparse_conv]   e.g.  tools/build_variant.sh ra4 "-DSEEVCN_RS3_RA=4"
+# usage: tools/build_variant.sh <name> "<extra hipcc flags>" [source: sparse_conv (default), conv_plan, sparse_wgrad, ...]   e.g.  tools/build_variant.sh fbstats "-DFB_STATS" fps_bucket
 # Builds see-vcn_amd/lib/variants/libseevcn_hip_<name>.so: <source>.hip recompiled with the flags, every other object as built by `make`.
 # A/B runs on one box: SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_<name>.so python bench.py ...
 set -e

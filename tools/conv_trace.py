@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-wave timeline of one planned sparse-conv launch (sv_debug_conv_trace): where the launch's time goes -- prologue, main loop, epilogue,
-idle tail -- and how evenly the SIMDs are loaded.  LAYER=subm3 (default) | subm4 | subm2 ...; prints a summary."""
+idle tail -- and how evenly the SIMDs are loaded.  LAYER=subm3 (default) | subm4 | subm2 ...; prints a summary.
+Needs the measurement build: run with SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so (make -C see-vcn_amd/csrc measure)."""
 import os
 import sys
 
@@ -15,6 +16,7 @@ from seevcn_amd.spconv import functional as Fsp
 
 
 def main():
+    _lib.require_measure_build("tools/conv_trace.py")
     dev = torch.device("cuda:0")
     bs = 16
     pts, _ = synth.make_scene_batch(bs, seed=2000, n_az=384)

@@ -43,8 +43,11 @@ timeout 300 python3 tools/vcn_gemm_micro.py > gpurun_out/${TAG}_vcn_gemm_micro.t
 timeout 300 python3 tools/host_time.py > gpurun_out/${TAG}_host_time.txt 2>&1
 for c in main pvrcnn centerpoint second; do timeout 300 python3 tools/sync_trace.py $c > gpurun_out/${TAG}_sync_trace_$c.txt 2>&1; done
 tools/timeline.sh ${TAG} > /dev/null 2>&1
+# the debug instances live in the measurement build only (make -C see-vcn_amd/csrc measure); against a production library the tools exit with one line
+CALLER_LIB=$SEEVCN_LIB; export SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so
 timeout 120 python3 tools/wgrad_uniform.py > gpurun_out/${TAG}_wgrad_uniform.txt 2>&1
 for d in 1 2 4 5 8 12; do echo "SEEVCN_WGRAD_DEBUG=$d" >> gpurun_out/${TAG}_wgrad_debug.txt; SEEVCN_WGRAD_PLANNED=0 SEEVCN_WGRAD_DEBUG=$d MODE=wgrad LAYER=subm3 timeout 120 python3 tools/spconv_micro.py 2>&1 | grep subm3 >> gpurun_out/${TAG}_wgrad_debug.txt; done
+if [ -n "$CALLER_LIB" ]; then export SEEVCN_LIB=$CALLER_LIB; else unset SEEVCN_LIB; fi
 (cd tools/ubench && /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -o /tmp/mfma_rate mfma_rate.hip 2>/dev/null && /tmp/mfma_rate | tail -4) > gpurun_out/${TAG}_mfma_rate.txt 2>&1
 tools/wgrad_ab.sh ${TAG} > /dev/null 2>&1
 timeout 300 python3 tools/launch_sites.py pvrcnn 40 > gpurun_out/${TAG}_launch_sites_pvrcnn.txt 2>&1

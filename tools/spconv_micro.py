@@ -3,7 +3,9 @@
 Prints per-layer forward / backward-data / weight-grad times (HIP events) with pairs and achieved TFLOP/s.
 --epilogue: per planned layer the forward with scale+shift+relu and with all epilogue terms (bias, scale+shift, residual, relu) next to the bare
 conv -- the launches of an eval-mode forward; SEEVCN_RS3_EPI_ROWS=0 gives the per-accumulator store path of the same build, and two library
-builds are compared with tools/build_variant.sh + tools/ab_libs.sh."""
+builds are compared with tools/build_variant.sh + tools/ab_libs.sh.
+Debug modes (SEEVCN_RS3_DEBUG, SEEVCN_WGRAD_DEBUG, SEEVCN_WGRAD_SKIP, SEEVCN_PLAN_DEBUG: instances without loads / MFMAs / passes) need the measurement
+build: run them with SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so (make -C see-vcn_amd/csrc measure)."""
 import os
 import sys
 
@@ -12,6 +14,7 @@ import numpy as np
 import torch
 
 import seevcn_amd.synth as synth
+from seevcn_amd import _lib
 from seevcn_amd.pcdet.ops import voxel_ops
 from seevcn_amd.spconv import functional as Fsp
 
@@ -50,6 +53,8 @@ def timeit(fn, reps=10):
 
 def main():
     epilogue = "--epilogue" in sys.argv[1:]
+    if any(os.environ.get(v) for v in _lib.MEASURE_SWITCHES):      # a production library would ignore the switch and time the production kernel
+        _lib.require_measure_build("tools/spconv_micro.py with " + ", ".join(v for v in _lib.MEASURE_SWITCHES if os.environ.get(v)))
     dev = torch.device("cuda:0")
     bs = int(os.environ.get("BS", "16"))
     pts, _ = synth.make_scene_batch(bs, seed=2000, n_az=int(os.environ.get("N_AZ", "384")))

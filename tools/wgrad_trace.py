@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-wave timeline of one MFMA weight-gradient launch (sv_debug_wgrad_trace, the 64 -> 64 instance): how long a wave spends in its pass prologues
 (table read + compaction + first operand loads) and in its MFMA loops, how long workgroups live, how many are resident, and how evenly the SIMDs are
-loaded.  LAYER=subm3 (default) | subm4 | spconv4."""
+loaded.  LAYER=subm3 (default) | subm4 | spconv4.
+Needs the measurement build: run with SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so (make -C see-vcn_amd/csrc measure)."""
 import os
 import sys
 
@@ -16,6 +17,7 @@ from seevcn_amd.spconv import functional as Fsp
 
 
 def main():
+    _lib.require_measure_build("tools/wgrad_trace.py")
     dev = torch.device("cuda:0")
     bs = 16
     pts, _ = synth.make_scene_batch(bs, seed=2000, n_az=384)

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Weight-gradient kernel on SYNTHETIC tables of uniform density (every offset has a pair for the same fraction of rows): separates the kernel's
-own efficiency from the imbalance between the 27 offsets of a real rulebook (centre offset: every row; corners: one row in thirty)."""
+own efficiency from the imbalance between the 27 offsets of a real rulebook (centre offset: every row; corners: one row in thirty).  Read next to the SEEVCN_WGRAD_DEBUG instances (no loads / no MFMAs), which only the
+measurement build has: run with SEEVCN_LIB=see-vcn_amd/lib/variants/libseevcn_hip_measure.so (make -C see-vcn_amd/csrc measure)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+from seevcn_amd import _lib
 from seevcn_amd.spconv import functional as Fsp
 
 
@@ -23,6 +25,7 @@ def timeit(fn, reps=10):
 
 
 def main():
+    _lib.require_measure_build("tools/wgrad_uniform.py")
     dev = torch.device("cuda:0")
     n, K, c = 139554, 27, 64
     g = torch.Generator(device=dev).manual_seed(0)
