@@ -98,7 +98,8 @@ int sv_scale_by_device_scalar(float* x, int64_t n, const float* g, void* stream)
  * (v_mfma_f32_32x32x2_f32: exact fp32).  Replaces the Conv1d(k=1)(+BN folded)(+ReLU/LeakyReLU) layers of
  * pose_encoder / FeatureEncoder (VCN_VC.py:81-106,116-123) and the Linear layers (:124-131).
  * C may be NULL (no store); group_max (M/rows_per_group, N), pre-filled with -inf, receives the max over each
- * group of rows (torch.max(feature, dim=2), VCN_VC.py:100,104 and AdaptiveMaxPool1d :122).  K % 32 == 0. */
+ * group of rows (torch.max(feature, dim=2), VCN_VC.py:100,104 and AdaptiveMaxPool1d :122).  K must be a positive multiple of 16 (the K tile of the
+ * kernel); lda, ldw >= K and multiples of 4, A and W 16-byte aligned; ldc >= N. */
 int sv_gemm_bias_act(const float* A, int lda, const float* W, int ldw, const float* bias,
                      const float* group_bias, int rows_per_group, float* C, int ldc, float* group_max,
                      int M, int N, int K, int act, float slope, void* stream);

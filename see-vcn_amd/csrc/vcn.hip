@@ -48,7 +48,7 @@ __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
 #ifndef SEEVCN_GEMM_WGS
 #define SEEVCN_GEMM_WGS 4
 #endif
-constexpr int BM = 128, BN = 128, BK = SEEVCN_GEMM_BK, LDP = BK + 4;     // K tile of the LDS stages (callers keep K % 32 == 0)
+constexpr int BM = 128, BN = 128, BK = SEEVCN_GEMM_BK, LDP = BK + 4;     // K tile of the LDS stages (the launcher takes K % BK == 0)
 constexpr int GEMM_ROW_THREADS = BK / 4, GEMM_ROWS_PER_PASS = 256 / GEMM_ROW_THREADS;
 
 struct GemmArgs {
