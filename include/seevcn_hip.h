@@ -295,6 +295,34 @@ int sv_sparse_conv_dgrad_planned_bn(const float* dZ, int64_t n_src, const int32_
                                     const int32_t* tile_of, int tiles_per_wave, const float* wfrag, float* dY, int64_t n_rows, int K, int Kd, int Nc,
                                     int table_k_reversed, const float* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                     const float* bn_beta, int bn_relu, float* bn_partial, void* stream);
+/* ---- half-precision inference (csrc/sparse_conv_half.hip): fp16 activations and weights, fp32 accumulation and epilogue.  Replaces the fp16 kernels
+ * of spconv 2.x behind SubMConv3d / SparseConv3d in eval mode (detector3d/pcdet/models/backbones_3d/spconv_backbone.py:8-27,77-117).
+ * 1 iff k_spconv_h16 is built for the layer: K <= 27 offsets, C_in and C_out in {16, 32, 64, 128}, and X (n_src rows of C_in fp16 values) is
+ * addressable with 32-bit byte offsets. */
+int sv_conv_h16_applies(int K, int Kd, int Nc, int64_t n_src);
+/* fp16 fragment copy of one layer's weights for the FORWARD direction (the eval list has no other), from any (K, C_in, C_out) fp32 view given by its
+ * element strides like sv_conv_weight_fragments; round to nearest even (the bits of torch.Tensor.half()).  frag16: K * C_in * C_out fp16 values,
+ * 16-byte aligned, caller-owned.  Order: one unit = one lane's MFMA operand, E = 8 values (C_in >= 32) or 4 (C_in = 16):
+ * frag16[(((k * KQ + q) * NT + t) * 64 + lane) * E + j] = W[k][q * 4 E + (lane >> 4) * E + j][t * 16 + (lane & 15)], KQ = C_in / (4 E), NT = C_out / 16. */
+int sv_conv_weight_fragments_h16(const float* W, int64_t stride_k, int64_t stride_cin, int64_t stride_cout, int K, int Cin, int Cout, void* frag16,
+                                 void* stream);
+/* The same for n_layers weights in one launch.  descs_device: (n_layers, 10) int64 ON THE DEVICE, laid out like sv_conv_weight_fragments_batch's: per
+ * layer {W pointer, stride_k, stride_cin, stride_cout, K, C_in, C_out, frag16 pointer, 0, first unit}; a layer has K * C_in * C_out / E units. */
+int sv_conv_weight_fragments_h16_batch(const void* descs_device, int n_layers, int64_t total_units, void* stream);
+/* Y (n_rows, Nc) = store(epilogue(sum_k X16[nbr[k]] @ W16[k])) on the plan of a table (table_rows, perm, masks_p as sv_conv_plan_build* leave them;
+ * tile_of is not used: a wave takes 16 consecutive perm positions at a time, in perm order, inside the region of its XCD).  X16 (n_src, Kd) and
+ * residual16 (n_rows, Nc) are fp16, bias / scale / shift (Nc) fp32, wfrag16 from sv_conv_weight_fragments_h16.  Products and sums in fp32 (offsets
+ * ascending, channel blocks ascending: reproducible bit for bit); epilogue in fp32 in sv_sparse_conv_gather_gemm_planned's order (add bias, ONE fused
+ * multiply-add, add residual, max with 0).  y_is_f32 = 0: Y is fp16, stored round-to-nearest-even; a finite result beyond 65504 is stored as +-inf
+ * (not clamped).  y_is_f32 = 1: Y is fp32 (the last layer of a list).  Whole rows are stored when Y and every term given are 16-byte aligned, single
+ * elements otherwise; the values are the same.  Rows the plan pads with (-1) are neither read nor written.  Shapes: sv_conv_h16_applies. */
+int sv_sparse_conv_gather_gemm_planned_h16(const void* X16, int64_t n_src, const int32_t* table_rows, const int32_t* perm, const int32_t* masks_p,
+                                           const void* wfrag16, void* Y, int y_is_f32, int64_t n_rows, int K, int Kd, int Nc, const float* bias,
+                                           const float* scale, const float* shift, const void* residual16, int relu, void* stream);
+/* y_f16[i] = half(x_f32[i]), round to nearest even (subnormals kept, +-inf beyond 65504): the fp16 copy of the fp32 input layer's output that the
+ * second layer of a half-precision list gathers (the reference casts with features.half() in front of the backbone instead, which rounds raw
+ * point coordinates). */
+int sv_narrow_h16(const float* x_f32, int64_t n_elems, void* y_f16, void* stream);
 /* bn_partial (null or sv_conv_planned_partials() x 2 x Nc floats; plain epilogue only: no bias / scale / residual / relu): per-workgroup column
  * sums and sums of squares of Y, the first pass of the training-mode BatchNorm behind the convolution (post_act_block, spconv_backbone.py:9-27)
  * made in the epilogue that holds the values in registers anyway; consumed by sv_batchnorm_relu_forward_partial. */
@@ -612,12 +640,16 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
  *                       (SyncBatchNorm: a list is CUT behind a *_LOCAL operation, the caller all-gathers `sums` between the ranks, and the next list
  *                       starts with the matching *_GLOBAL operation)
  *   SV_OP_BN_EVAL_COEF_BATCH   sv_batchnorm_eval_coef_batch: p0 = HOST address of the job table (read before sv_run_ops returns); i = n_jobs
+ *   SV_OP_CONV_PLANNED_H16     sv_sparse_conv_gather_gemm_planned_h16: p = X16, table_rows, perm, masks_p, wfrag16, Y, bias, scale, shift, residual16;
+ *                       n = n_src, n_rows; i = K, Kd, Nc, relu, y_is_f32
+ *   SV_OP_NARROW_H16    sv_narrow_h16: p = x_f32, y_f16; n = n_elems
  * Input transform: SV_OP_CONV_PLANNED with p12 = coef (2, Kd) and i6 = relu, SV_OP_WGRAD[_DEFERRED] with p6 = coef (2, Cin) and i4 = relu read their
  * X through sv_conv_next_input_norm(coef, relu): X is then the RAW output of the convolution below, its BatchNorm (+ReLU) is applied as the rows are
  * gathered, and the normalised activation tensor is never written.
  * Used by seevcn_amd/spconv/chain.py: the forward and the backward of a conv -> BatchNorm -> ReLU chain (VoxelBackBone8x, spconv_backbone.py:128-180)
  * as two calls inside one autograd node; and the eval-mode forward of both 3-D backbones as one call (SV_OP_BN_EVAL_COEF_BATCH + one conv per layer,
- * BatchNorm, conv bias, identity and ReLU in the convs' epilogues). */
+ * BatchNorm, conv bias, identity and ReLU in the convs' epilogues), in fp32 or -- SV_OP_NARROW_H16 behind the fp32 input layer, SV_OP_CONV_PLANNED_H16
+ * for every layer behind it -- with fp16 activations. */
 #define SV_OP_WORDS 32
 #define SV_OP_CONV_PLANNED 1
 #define SV_OP_CONV_PLAIN 2
@@ -633,6 +665,8 @@ int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float*
 #define SV_OP_BN_BWD_SUMS_LOCAL 13
 #define SV_OP_BN_BWD_APPLY_GLOBAL 14
 #define SV_OP_BN_EVAL_COEF_BATCH 15
+#define SV_OP_CONV_PLANNED_H16 16
+#define SV_OP_NARROW_H16 17
 int sv_run_ops(const int64_t* ops, int n_ops, void* stream);
 /* measurement form: events around every operation on `stream`, the call waits for the stream and writes each operation's elapsed milliseconds to
  * ms[0 .. n_ops) (bench.py's roofline block times the conv launches of the step's own launch lists with it) */

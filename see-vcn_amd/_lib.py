@@ -73,6 +73,11 @@ SIGNATURES = {
     "sv_sparse_conv_gather_gemm_planned": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     "sv_sparse_conv_dgrad_planned_bn": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "sv_conv_planned_partials": (c_i, []),
+    "sv_conv_h16_applies": (c_i, [c_i, c_i, c_i, c_i64]),
+    "sv_conv_weight_fragments_h16": (c_i, [c_p, c_i64, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "sv_conv_weight_fragments_h16_batch": (c_i, [c_p, c_i, c_i64, c_p]),
+    "sv_sparse_conv_gather_gemm_planned_h16": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p]),
+    "sv_narrow_h16": (c_i, [c_p, c_i64, c_p, c_p]),
     "sv_batchnorm_relu_forward_partial": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_debug_conv_trace": (c_i, [c_p]),
     "sv_debug_wgrad_trace": (c_i, [c_p]),

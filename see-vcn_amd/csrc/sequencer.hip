@@ -176,6 +176,15 @@ static int run_ops(const int64_t* ops, int n_ops, void* stream, void* side_strea
       case SV_OP_BN_EVAL_COEF_BATCH:
         rc = sv_batchnorm_eval_coef_batch(ptr_of<const int64_t>(p[0]), (int)i[0], stream);      // p0: the HOST job table
         break;
+      case SV_OP_CONV_PLANNED_H16:
+        rc = sv_sparse_conv_gather_gemm_planned_h16(ptr_of<const void>(p[0]), n[0], ptr_of<const int32_t>(p[1]), ptr_of<const int32_t>(p[2]),
+                                                    ptr_of<const int32_t>(p[3]), ptr_of<const void>(p[4]), ptr_of<void>(p[5]), (int)i[4], n[1], (int)i[0],
+                                                    (int)i[1], (int)i[2], ptr_of<const float>(p[6]), ptr_of<const float>(p[7]), ptr_of<const float>(p[8]),
+                                                    ptr_of<const void>(p[9]), (int)i[3], stream);
+        break;
+      case SV_OP_NARROW_H16:
+        rc = sv_narrow_h16(ptr_of<const float>(p[0]), n[0], ptr_of<void>(p[1]), stream);
+        break;
       case SV_OP_WGRAD:
         if (st_side && (rc = fork_side()) != SV_OK) break;
         if (p[6]) sv_conv_next_input_norm(ptr_of<const float>(p[6]), (int)i[4]);

@@ -59,7 +59,33 @@ class SparseBasicBlock(spconv.SparseModule):
 chain.register_residual_block(SparseBasicBlock)         # chain.flatten takes blocks whose forward is the one above (eval list)
 
 
+_EVAL_DTYPES = {'float32': torch.float32, 'float16': torch.float16, torch.float32: torch.float32, torch.float16: torch.float16}
+
+
 class _BackBone8xBase(nn.Module):
+    # the route the last forward took: 'half' (fp16 eval launch list), 'chain' (fp32 launch list, training or eval) or 'modules' (the module tree);
+    # None before the first forward.  A stand-down of the half route shows here instead of having to be guessed from timings.
+    last_eval_route = None
+    _eval_dtype = torch.float32
+
+    def set_eval_dtype(self, dtype):
+        """torch.float32 / 'float32' (default) or torch.float16 / 'float16': the activation format of the eval-mode launch list (model_cfg key
+        EVAL_DTYPE).  float16 is a property of the ROUTE: parameters, buffers and the state_dict stay fp32, nothing is cast on the module; the layers
+        behind the input layer read fp16 rows and fp16 weight fragments and compute in fp32 (seevcn_amd/spconv/chain.py).  Training, enabled gradients, hooks
+        and whatever else sends the fp32 list to the module tree do the same here; a layer shape the fp16 kernel is not built for sends the forward to
+        the fp32 list."""
+        try:
+            known = dtype in _EVAL_DTYPES
+        except TypeError:
+            known = False
+        if not known:
+            raise ValueError(f"EVAL_DTYPE must be 'float32' or 'float16' (torch.float32 / torch.float16), got {dtype!r}")
+        self._eval_dtype = _EVAL_DTYPES[dtype]
+        return self
+
+    def _init_eval_dtype(self, model_cfg):
+        self.set_eval_dtype(model_cfg.get('EVAL_DTYPE', 'float32') if hasattr(model_cfg, 'get') else 'float32')
+
     def _finish(self, batch_dict, x_conv1, x_conv2, x_conv3, x_conv4, out):
         # same keys as the reference (spconv_backbone.py:159-178)
         batch_dict.update({'encoded_spconv_tensor': out, 'encoded_spconv_tensor_stride': 8})
@@ -92,17 +118,26 @@ class _BackBone8xBase(nn.Module):
                                                   indice_dict=batch_dict.get('spconv_indice_dict'))      # seevcn: rulebooks built ahead (pipeline.front)
         # all rulebooks + conv plans first: their host syncs then wait for index kernels only, and the layer loop below is enqueued without one
         spconv.prebuild_rulebooks(self, input_sp_tensor, with_backward=self.training and torch.is_grad_enabled())
+        entries = self._chain_blocks()
+        # half-precision eval list (opt-in, set_eval_dtype): its fp16 fragment copies are the ones re-laid, in one launch, and the layers behind the fp32
+        # input layer run on them
+        if not self.training and self._eval_dtype == torch.float16 and chain.eval_half_applicable(entries, input_sp_tensor):
+            spconv.refresh_weight_fragments(self, half=True)
+            self.last_eval_route = 'half'
+            return self._finish(batch_dict, *chain.run_eval_chain(entries, input_sp_tensor, dtype=torch.float16))
         # the MFMA fragment copies of all layer weights in one launch (they follow the weights every forward; spconv/functional.py)
         spconv.refresh_weight_fragments(self)
         # one description of the stages for both launch-list routes (seevcn_amd/spconv/chain.py) instead of ~100 calls from the module tree.  Training,
         # every stage a plain run of conv -> BatchNorm1d | SyncBatchNorm -> ReLU blocks (VoxelBackBone8x): the whole chain and its backward as two lists
         # inside one autograd node.  Eval without gradients (both backbones, residual blocks included): one list, every BatchNorm folded into its
         # conv's epilogue.  Whatever neither takes walks the module tree below.
-        entries = self._chain_blocks()
         if self.training and chain.applicable(entries, input_sp_tensor):
+            self.last_eval_route = 'chain'
             return self._finish(batch_dict, *chain.run_chain(entries, input_sp_tensor))
         if not self.training and chain.eval_applicable(entries, input_sp_tensor):
+            self.last_eval_route = 'chain'
             return self._finish(batch_dict, *chain.run_eval_chain(entries, input_sp_tensor))
+        self.last_eval_route = 'modules'
         x = self.conv_input(input_sp_tensor)
         x_conv1 = self.conv1(x)
         yield
@@ -131,6 +166,7 @@ class VoxelBackBone8x(_BackBone8xBase):
     def __init__(self, model_cfg, input_channels, grid_size, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
+        self._init_eval_dtype(model_cfg)
         norm_fn = partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01)
         self.sparse_shape = [int(g) for g in list(grid_size)[::-1]]
         self.sparse_shape[0] += 1                     # grid_size[::-1] + [1, 0, 0]  (spconv_backbone.py:75)
@@ -164,6 +200,7 @@ class VoxelResBackBone8x(_BackBone8xBase):
     def __init__(self, model_cfg, input_channels, grid_size, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
+        self._init_eval_dtype(model_cfg)
         norm_fn = partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01)
         self.sparse_shape = [int(g) for g in list(grid_size)[::-1]]
         self.sparse_shape[0] += 1

@@ -15,6 +15,8 @@ epilogue applies conv bias, folded BatchNorm, the identity of a residual block (
 activation is written once, normalised.  It stands down (module tree) when gradients are enabled, a norm is in training mode or keeps no running
 statistics, the input is empty, anything walked carries a hook, a residual block has a downsample module or a forward of its own, or SEEVCN_CHAIN=0 /
 SEEVCN_EVAL_CHAIN=0.
+A second form of the same list runs the layers behind the input layer on fp16 activations and fp16 weight fragments with fp32 arithmetic
+(eval_half_applicable / run_eval_chain(dtype=torch.float16), csrc/sparse_conv_half.hip); a backbone takes it only when asked (EVAL_DTYPE / set_eval_dtype).
 
 Both routes read ONE description of the network: flatten() -> BlockList of Entry, one per convolution (applicable() declines for training what only
 the eval list carries: a residual identity, a conv bias).  Every row of a list is made by the constructor of its operation code (CONV_PLANNED ...
@@ -60,6 +62,7 @@ BN_FOLD = os.environ.get("SEEVCN_BN_FOLD", "1") != "0"
 EVAL_CHAIN_OFF = os.environ.get("SEEVCN_EVAL_CHAIN", "1") == "0"
 OP_CONV_PLANNED, OP_CONV_PLAIN, OP_BN_FWD, OP_BN_BWD, OP_WGRAD, OP_DGRAD_PLANNED_BN, OP_WGRAD_DEFERRED, OP_BN_FINALIZE, OP_BN_APPLY = 1, 2, 3, 5, 6, 7, 8, 9, 10
 OP_BN_STATS_LOCAL, OP_BN_FINALIZE_GLOBAL, OP_BN_BWD_SUMS_LOCAL, OP_BN_BWD_APPLY_GLOBAL, OP_BN_EVAL_COEF_BATCH = 11, 12, 13, 14, 15
+OP_CONV_PLANNED_H16, OP_NARROW_H16 = 16, 17
 WORDS = 32
 
 
@@ -146,6 +149,16 @@ def BN_BWD_APPLY_GLOBAL(*, x, dy, rows, channels, gamma, beta, save_mean, save_i
 
 def BN_EVAL_COEF_BATCH(*, jobs_host, n_jobs):
     return _row(OP_BN_EVAL_COEF_BATCH, i=(n_jobs,), p=(jobs_host,))                  # the job table is HOST memory, read before the list's call returns
+
+
+def CONV_PLANNED_H16(plan, *, X16, n_src, wfrag16, Y, y_is_f32, n_rows, K, Kd, Nc, relu=0, bias=None, scale=None, shift=None, residual16=None):
+    table_rows, perm, masks_p = plan[:3]                                             # the fp16 kernel walks perm itself: no tile_of, no tiles_per_wave
+    return _row(OP_CONV_PLANNED_H16, i=(K, Kd, Nc, relu, bool(y_is_f32)), n=(n_src, n_rows),
+                p=(X16, table_rows, perm, masks_p, wfrag16, Y, bias, scale, shift, residual16))
+
+
+def NARROW_H16(*, x_f32, n_elems, y_f16):
+    return _row(OP_NARROW_H16, n=(n_elems,), p=(x_f32, y_f16))
 
 
 def _run(rows, what):
@@ -594,10 +607,121 @@ def eval_applicable(entries, x):
     return True
 
 
-def run_eval_chain(entries, x):
-    """x: SparseConvTensor at the chain's input with every rulebook prebuilt (and the weight fragments refreshed).  -> list of SparseConvTensor, one per
+def eval_half_applicable(entries, x):
+    """The half-precision form of the eval list takes these entries on x now: everything eval_applicable asks, at least two entries, and behind the
+    first one (the fp32 input layer) every convolution on a planned table with a shape the fp16 kernel is built for (sv_conv_h16_applies), no identity
+    read from the chain's fp32 input."""
+    if not eval_applicable(entries, x) or len(entries) < 2:
+        return False
+    lib = _lib.load()
+    for k, e in enumerate(entries):
+        if e.residual_from is not None and e.residual_from < 0:
+            return False
+        if k == 0:
+            continue
+        rb = x.indice_dict[e.conv.indice_key]
+        if not lib.sv_conv_h16_applies(int(e.K), int(e.cin), int(e.cout), int(rb.n_in)) or rb.plan_addrs("fwd", e.cin, e.cout) is None:
+            return False
+    return True
+
+
+class HalfTap(SparseConvTensor):
+    """A tap of the half-precision eval list: the rows stay fp16 until somebody reads `.features`, which widens them to fp32 once (exact) and keeps the
+    result -- SECOND and CenterPoint read none of x_conv1..4, PV-RCNN pays one elementwise pass per scale it reads.  `features_half` is the stored tensor."""
+
+    def __init__(self, half, indices, spatial_shape, batch_size, grid=None, indice_dict=None):
+        super().__init__(None, indices, spatial_shape, batch_size, grid, indice_dict)
+        self.features_half = half
+
+    @property
+    def features(self):
+        if self._features is None:
+            self._features = self.features_half.float()
+        return self._features
+
+    @features.setter
+    def features(self, value):
+        self._features = value
+
+
+def _align16(nbytes):
+    return (int(nbytes) + 15) & ~15
+
+
+def _run_eval_chain_half(entries, x, keep_all=False):
+    """run_eval_chain's half-precision form.  The list: [all BatchNorm coefficients, fp32] + [entry 0 on the fp32 conv row: raw point features (coordinates
+    of up to 70 m) are never rounded to fp16] + [SV_OP_NARROW_H16: its fp16 copy] + one SV_OP_CONV_PLANNED_H16 per further entry, each reading and
+    writing fp16 rows, the last one storing fp32.  Offsets are BYTES, every piece 16-byte aligned.  keep_all: every entry's output leaves with the result
+    (-> list of (n_out, cout) tensors, one per entry: tests hold each layer to its own bound)."""
+    dev = x.features.device
+    features = x.features.contiguous()
+    rulebooks = [x.indice_dict[e.conv.indice_key] for e in entries]
+    L = len(entries)
+    leaves = [keep_all or e.tap for e in entries]
+    size = [rb.n_out * e.cout * (4 if k == L - 1 else 2) for k, (e, rb) in enumerate(zip(entries, rulebooks))]
+    t_total, w_total, c_offs, y_offs = 0, 0, [], []
+    for e in entries:
+        c_offs.append(w_total)
+        w_total += _align16(8 * e.cout)
+    y0_f32 = w_total                                                                 # entry 0's fp32 output: dies with the call
+    w_total += _align16(4 * rulebooks[0].n_out * entries[0].cout)
+    for k in range(L):
+        if leaves[k]:
+            y_offs.append(t_total)
+            t_total += _align16(size[k])
+        else:
+            y_offs.append(w_total)
+            w_total += _align16(size[k])
+    arena = torch.empty((t_total,), dtype=torch.uint8, device=dev)
+    work = torch.empty((w_total,), dtype=torch.uint8, device=dev)
+    assert arena.data_ptr() % 16 == 0 and work.data_ptr() % 16 == 0
+    base = work.data_ptr()
+    y_addr = [(arena.data_ptr() if leaves[k] else base) + y_offs[k] for k in range(L)]
+    jobs = np.zeros((L, 8), dtype=np.int64)
+    rows = [BN_EVAL_COEF_BATCH(jobs_host=jobs.ctypes.data, n_jobs=L)]
+    keep = []
+    x_ptr, n_src = features.data_ptr(), features.shape[0]
+    for k, (e, rb) in enumerate(zip(entries, rulebooks)):
+        bn, conv = e.bn, e.conv
+        o_coef = base + c_offs[k]
+        jobs[k, :7] = (0 if bn.weight is None else bn.weight.data_ptr(), 0 if bn.bias is None else bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                       bn.running_var.data_ptr(), o_coef, e.cout, _bits(bn.eps))
+        bias = None if conv.bias is None else conv.bias.data_ptr()
+        epilogue = dict(relu=int(e.relu), bias=bias, scale=o_coef, shift=o_coef + 4 * e.cout)
+        if k == 0:
+            assert e.residual_from is None
+            rows.append(_conv_row(e, rb, keep, x_ptr, n_src, base + y0_f32, residual=None, **epilogue)[0])
+            rows.append(NARROW_H16(x_f32=base + y0_f32, n_elems=rb.n_out * e.cout, y_f16=y_addr[0]))
+        else:
+            res = None if e.residual_from is None else y_addr[e.residual_from]
+            rows.append(CONV_PLANNED_H16(rb.plan_addrs("fwd", e.cin, e.cout), X16=x_ptr, n_src=n_src, wfrag16=Fsp.fragment_cache.get_half(conv.weight_kio_nograd()).data_ptr(),
+                                         Y=y_addr[k], y_is_f32=k == L - 1, n_rows=rb.n_out, K=e.K, Kd=e.cin, Nc=e.cout, residual16=res, **epilogue))
+        x_ptr, n_src = y_addr[k], rb.n_out
+    _run(rows, "sv_run_ops (eval chain, fp16)")
+
+    def view(k):
+        e, rb = entries[k], rulebooks[k]
+        return arena[y_offs[k]:y_offs[k] + size[k]].view(torch.float32 if k == L - 1 else torch.float16).view(rb.n_out, e.cout)
+
+    if keep_all:
+        return [view(k) for k in range(L)]
+    out = []
+    for k, (e, rb) in enumerate(zip(entries, rulebooks)):
+        if e.tap:
+            meta = (rb.out_indices, rb.out_shape, x.batch_size, x.grid, x.indice_dict)
+            out.append(SparseConvTensor(view(k), *meta) if k == L - 1 else HalfTap(view(k), *meta))
+    return out
+
+
+def run_eval_chain(entries, x, dtype=torch.float32):
+    """dtype torch.float16: the half-precision form (_run_eval_chain_half; ask eval_half_applicable first) -- fp16 activations and weight fragments, fp32
+    arithmetic, the last entry's output and every tap's `.features` fp32.  Default: the fp32 list, unchanged.
+    x: SparseConvTensor at the chain's input with every rulebook prebuilt (and the weight fragments refreshed).  -> list of SparseConvTensor, one per
     tap, in order.  ONE sv_run_ops call: [all BatchNorm coefficients] + one convolution per entry; nothing is saved, parameters and buffers are only read.
     Only the taps' features outlive the call."""
+    if dtype == torch.float16:
+        return _run_eval_chain_half(entries, x)
+    assert dtype == torch.float32, dtype
     dev = x.features.device
     features = x.features.contiguous()
     rulebooks = [x.indice_dict[e.conv.indice_key] for e in entries]

@@ -255,10 +255,14 @@ def _prebuild_layer_by_layer(root, x, with_backward):
             rb.wgrad_plan(m.in_channels, m.out_channels)
 
 
-def refresh_weight_fragments(root):
-    """One launch that re-lays the MFMA fragment copies of every planned-kernel convolution under `root` (Fsp.fragment_cache.refresh_all)."""
+def refresh_weight_fragments(root, half=False):
+    """One launch that re-lays the MFMA fragment copies of every planned-kernel convolution under `root` (Fsp.fragment_cache.refresh_all); half: the fp16
+    copies of the half-precision eval list instead (refresh_all_half)."""
     if not Fsp.USE_PLAN:
         return
     ws = [m.weight_kio_nograd() for m in _sparse_convs(root) if m.weight.is_cuda]
     with torch.no_grad():
-        Fsp.fragment_cache.refresh_all(ws)
+        if half:
+            Fsp.fragment_cache.refresh_all_half(ws)
+        else:
+            Fsp.fragment_cache.refresh_all(ws)

@@ -546,6 +546,8 @@ class _FragmentCache:
         self._d = {}
         self._fresh = set()          # entries re-laid by refresh_all and not yet taken by their layer's forward
         self._tables = {}            # descriptor tables of refresh_all, by the identity of the weight set
+        self._h = {}                 # the half side: fp16 forward fragments, laid out only when a half-precision route asks
+        self._fresh_h = set()
 
     def _entry(self, weight_kio):
         base = weight_kio._base if weight_kio._base is not None else weight_kio
@@ -599,10 +601,68 @@ class _FragmentCache:
                    "sv_conv_weight_fragments")
         return fwd, bwd
 
+    # ---- the half side: fp16 fragment copies for the half-precision eval list (sv_conv_weight_fragments_h16, forward direction only).  Keyed and dropped
+    # like the fp32 pair (identity of the base tensor, weak reference) and re-laid by the forward that uses them; nothing is allocated or launched until
+    # a half route first asks.
+    def _entry_half(self, weight_kio):
+        base = weight_kio._base if weight_kio._base is not None else weight_kio
+        K, cin, cout = weight_kio.shape
+        key = id(base)
+        hit = self._h.get(key)
+        if hit is not None and hit[0]() is base and hit[1].numel() == K * cin * cout and hit[1].device == weight_kio.device:
+            return key, hit[1], True
+        frag = torch.empty((K * cin * cout,), dtype=torch.float16, device=weight_kio.device)
+        h = self._h
+        self._h[key] = (weakref.ref(base, lambda _r, k=key: (h.pop(k, None), self._fresh_h.discard(k))), frag)
+        return key, frag, False
+
+    @staticmethod
+    def half_layout_applies(w):
+        return w.is_cuda and w.dtype == torch.float32 and w.shape[1] in (16, 32, 64, 128) and w.shape[2] % 16 == 0
+
+    def refresh_all_half(self, weights):
+        """refresh_all for the fp16 copies: ONE launch (sv_conv_weight_fragments_h16_batch) re-lays every (K, C_in, C_out) view in `weights` that the
+        fp16 kernel's layout takes; get_half() of this forward then finds its copy fresh."""
+        lib = _lib.load()
+        self._fresh_h.clear()
+        weights = [w for w in weights if self.half_layout_applies(w)]
+        if not weights:
+            return
+        rows, keys, unit0 = [], [], 0
+        for w in weights:
+            key, frag, _ = self._entry_half(w)
+            K, cin, cout = w.shape
+            sk, si, so = w.stride()
+            rows.append([w.data_ptr(), sk, si, so, K, cin, cout, frag.data_ptr(), 0, unit0])
+            unit0 += K * cin * cout // (8 if cin >= 32 else 4)
+            keys.append(key)
+        sig = ("h16",) + tuple(tuple(r) for r in rows)
+        table = self._tables.get(sig)
+        if table is None:
+            if len(self._tables) > 16:
+                self._tables.clear()
+            table = torch.tensor(rows, dtype=torch.int64).to(weights[0].device)
+            self._tables[sig] = table
+        _lib.check(lib.sv_conv_weight_fragments_h16_batch(_lib.ptr(table), len(rows), unit0, _lib.stream()), "sv_conv_weight_fragments_h16_batch")
+        self._fresh_h.update(keys)
+
+    def get_half(self, weight_kio):
+        K, cin, cout = weight_kio.shape
+        key, frag, hit = self._entry_half(weight_kio)
+        if hit and key in self._fresh_h:
+            self._fresh_h.discard(key)
+            return frag
+        sk, si, so = weight_kio.stride()
+        _lib.check(_lib.load().sv_conv_weight_fragments_h16(ctypes.c_void_p(weight_kio.data_ptr()), sk, si, so, K, cin, cout, _lib.ptr(frag), _lib.stream()),
+                   "sv_conv_weight_fragments_h16")
+        return frag
+
     def clear(self):
         self._d.clear()
         self._fresh.clear()
         self._tables.clear()
+        self._h.clear()
+        self._fresh_h.clear()
 
 
 fragment_cache = _FragmentCache()
@@ -621,6 +681,34 @@ def gather_gemm_planned(x, plan, wfrag, n_rows, K, kd, nc, bias=None, scale=None
                                                 _lib.ptr(y) if n_rows else None, n_rows, int(K), int(kd), int(nc), _lib.ptr(bias), _lib.ptr(scale),
                                                 _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)), int(bool(rev)), bn_partial, _lib.stream())
     _lib.check(rc, "sv_sparse_conv_gather_gemm_planned")
+    return y
+
+
+def gather_gemm_planned_h16(x16, plan, wfrag16, n_rows, K, kd, nc, bias=None, scale=None, shift=None, residual16=None, relu=False, out_dtype=torch.float16,
+                            out=None):
+    """Y (n_rows, nc) = store(epi(sum_k X16[nbr[k]] @ W16[k])) on a table plan (Rulebook.plan; its deal is not used) with fp16 rows, fp16 weight fragments
+    (fragment_cache.get_half), fp32 accumulation and epilogue; Y is fp16 (round to nearest even) or fp32.  out: a (n_rows, nc) tensor of out_dtype to
+    write (it need not be 16-byte aligned)."""
+    lib = _lib.load()
+    tp = plan[0]
+    assert x16.shape[1] == kd and x16.dtype == torch.float16 and out_dtype in (torch.float16, torch.float32)
+    assert residual16 is None or residual16.dtype == torch.float16
+    x16 = x16.contiguous()
+    y = torch.empty((n_rows, nc), dtype=out_dtype, device=x16.device) if out is None else out
+    assert y.dtype == out_dtype and tuple(y.shape) == (n_rows, nc)
+    rc = lib.sv_sparse_conv_gather_gemm_planned_h16(_lib.ptr(x16) if x16.numel() else None, x16.shape[0], _lib.ptr(tp.rows), _lib.ptr(tp.perm), _lib.ptr(tp.masks_p),
+                                                    _lib.ptr(wfrag16), _lib.ptr(y) if n_rows else None, int(out_dtype == torch.float32), n_rows, int(K), int(kd),
+                                                    int(nc), _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual16), int(bool(relu)), _lib.stream())
+    _lib.check(rc, "sv_sparse_conv_gather_gemm_planned_h16")
+    return y
+
+
+def narrow_h16(x):
+    """fp32 tensor -> its fp16 copy (sv_narrow_h16: round to nearest even, the bits of x.half())."""
+    assert x.dtype == torch.float32
+    x = x.contiguous()
+    y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    _lib.check(_lib.load().sv_narrow_h16(_lib.ptr(x) if x.numel() else None, x.numel(), _lib.ptr(y) if x.numel() else None, _lib.stream()), "sv_narrow_h16")
     return y
 
 
