@@ -564,6 +564,20 @@ int sv_bev_interpolate(const float* keypoints, int64_t num_keypoints, const floa
 size_t sv_bev_interpolate_grad_scratch_bytes(int batch, int C, int H, int W);
 int sv_bev_interpolate_grad(const float* keypoints, int64_t num_keypoints, const float* grad_out, int batch, int C, int H, int W,
                             float x_min, float y_min, float voxel_x, float voxel_y, float bev_stride, void* scratch, float* grad_bev, void* stream);
+/* The same pair on a channel-last map: bev and grad_bev are (B,H,W,C), the storage of a channels_last (B,C,H,W) tensor; out and grad_out stay
+ * (M,C).  Forward: per element the expression of sv_bev_interpolate, so the bits equal its result on the permuted map; rows with a batch index
+ * outside [0, B) give zeros.  16-byte accesses along C when C % 4 == 0 and the pointers are 16-byte aligned, else one float a lane.
+ * Gradient: no float atomics and a fixed order.  grad_bev[pixel, c] = +0.0f + grad_out[m, c] * w_t summed in ascending key 4 * m + t over the
+ * taps that land on the pixel (t = 0..3: the taps y0x0, y1x0, y0x1, y1x1 of keypoint m; two taps of one keypoint clamped onto one pixel are two
+ * terms), every product and every sum rounded to fp32; a pixel without taps is +0.0f.  Every element is written exactly once, the map is never
+ * cleared or copied.  scratch (sv_bev_interpolate_grad_nhwc_scratch_bytes bytes, uninitialised): int32 tap counts and key-list segments per
+ * pixel and the 4 * M keys; needs B*H*W < 2^31 and M < 2^29.  M == 0 writes the zero map and reads no scratch. */
+int sv_bev_interpolate_nhwc(const float* keypoints, int64_t num_keypoints, const float* bev, int batch, int C, int H, int W, float x_min,
+                            float y_min, float voxel_x, float voxel_y, float bev_stride, float* out, void* stream);
+size_t sv_bev_interpolate_grad_nhwc_scratch_bytes(int64_t num_keypoints, int batch, int H, int W);
+int sv_bev_interpolate_grad_nhwc(const float* keypoints, int64_t num_keypoints, const float* grad_out, int batch, int C, int H, int W,
+                                 float x_min, float y_min, float voxel_x, float voxel_y, float bev_stride, void* scratch, float* grad_bev,
+                                 void* stream);
 
 /* SigmoidFocalClassificationLoss.forward (detector3d/pcdet/utils/loss_utils.py:9-72: alpha-balanced sigmoid focal loss, un-reduced) and its
  * derivative w.r.t. the logits, one launch each instead of ~20 / ~30 elementwise ones.  input, target (n_rows, num_class), weights (n_rows) or

@@ -144,6 +144,9 @@ SIGNATURES = {
     "sv_sigmoid_focal_loss": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_f, c_f, c_p, c_p, c_p]),
     "sv_weighted_smooth_l1_loss": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_f, c_p, c_p, c_p]),
     "sv_bev_interpolate_grad": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p]),
+    "sv_bev_interpolate_nhwc": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
+    "sv_bev_interpolate_grad_nhwc_scratch_bytes": (c_sz, [c_i64, c_i, c_i, c_i]),
+    "sv_bev_interpolate_grad_nhwc": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p]),
     "sv_center_assign_targets": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_p, c_p, c_p,
                                        c_p, c_p]),
     "sv_vcn_surface_select_scratch_bytes": (c_sz, [c_i]),

@@ -320,6 +320,239 @@ extern "C" int sv_bev_interpolate_grad(const float* keypoints, int64_t num_keypo
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same interpolation on a channel-last map (B, H, W, C) -- the storage of a channels_last (B, C, H, W) tensor, which HeightCompression
+// writes from 8 scenes on.  A tap is one contiguous run of C floats, so the lanes run along C: 16 bytes a lane where C % 4 == 0 and the
+// pointers allow it.  Per element the expression and its operand order are k_bev_interp's, so the bits are too (-ffp-contract=off).
+// ------------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ __launch_bounds__(256) void k_bev_interp_cl(const float* __restrict__ kps, int64_t M, const float* __restrict__ bev, BevGeom g,
+                                                       float* __restrict__ out) {
+  const int cv = g.C / VEC;                                        // VEC == 4 only when C % 4 == 0
+  const int64_t total = M * cv;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = e / cv;
+    const int c = (int)(e - m * cv) * VEC;
+    int b, x0, x1, y0, y1; float wa, wb, wc, wd;
+    bev_taps(kps + m * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
+    float* o = out + m * g.C + c;
+    if (b < 0 || b >= g.B) {
+      if constexpr (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(0.f, 0.f, 0.f, 0.f);
+      else *o = 0.f;
+      continue;
+    }
+    const float* p = bev + (int64_t)b * g.H * g.W * g.C + c;
+    const float* pa = p + ((int64_t)y0 * g.W + x0) * g.C;
+    const float* pb = p + ((int64_t)y1 * g.W + x0) * g.C;
+    const float* pc = p + ((int64_t)y0 * g.W + x1) * g.C;
+    const float* pd = p + ((int64_t)y1 * g.W + x1) * g.C;
+    if constexpr (VEC == 4) {
+      const float4 a = *reinterpret_cast<const float4*>(pa), bb = *reinterpret_cast<const float4*>(pb);
+      const float4 cc = *reinterpret_cast<const float4*>(pc), d = *reinterpret_cast<const float4*>(pd);
+      float4 v;
+      v.x = a.x * wa + bb.x * wb + cc.x * wc + d.x * wd;
+      v.y = a.y * wa + bb.y * wb + cc.y * wc + d.y * wd;
+      v.z = a.z * wa + bb.z * wb + cc.z * wc + d.z * wd;
+      v.w = a.w * wa + bb.w * wb + cc.w * wc + d.w * wd;
+      *reinterpret_cast<float4*>(o) = v;
+    } else {
+      *o = *pa * wa + *pb * wb + *pc * wc + *pd * wd;
+    }
+  }
+}
+
+// Gradient on the channel-last map with a fixed summation order and no float atomics: every pixel's C floats are written once, as
+//   +0.0f + gout[m, :] * w_t   over the pixel's taps in ascending key 4 * m + t   (t = 0..3: wa, wb, wc, wd; each product and sum rounded to fp32).
+// The taps of a pixel are found through per-pixel key lists built with integer atomics: count the taps of every pixel, give every pixel a
+// segment of the key buffer, fill the segments (in arrival order -- the gather orders them), then one wave per pixel gathers.
+struct BevLists {
+  int32_t* total;   // 1 word (+3 of padding): the segment allocator
+  int32_t* cnt;     // (B * H * W) taps per pixel
+  int32_t* seg;     // (B * H * W) segment start; the fill advances it to the segment's end
+  int32_t* keys;    // (4 * M)
+};
+
+__device__ __forceinline__ void bev_tap_pixels(const BevGeom& g, int b, int x0, int x1, int y0, int y1, int64_t pix[4]) {
+  const int64_t base = (int64_t)b * g.H * g.W;
+  pix[0] = base + (int64_t)y0 * g.W + x0;       // wa
+  pix[1] = base + (int64_t)y1 * g.W + x0;       // wb
+  pix[2] = base + (int64_t)y0 * g.W + x1;       // wc
+  pix[3] = base + (int64_t)y1 * g.W + x1;       // wd
+}
+
+// FILL == 0: cnt[pixel] += 1 per tap.  FILL == 1: keys[seg[pixel]++] = 4 * m + t.
+template <int FILL>
+__global__ __launch_bounds__(256) void k_bev_tap_lists(const float* __restrict__ kps, int64_t M, BevGeom g, BevLists L) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M * 4; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = e >> 2;
+    const int t = (int)(e & 3);
+    int b, x0, x1, y0, y1; float wa, wb, wc, wd;
+    bev_taps(kps + m * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
+    if (b < 0 || b >= g.B) continue;
+    int64_t pix[4];
+    bev_tap_pixels(g, b, x0, x1, y0, y1, pix);
+    const int64_t p = t == 0 ? pix[0] : t == 1 ? pix[1] : t == 2 ? pix[2] : pix[3];
+    if (FILL) L.keys[atomicAdd(&L.seg[p], 1)] = (int32_t)e;
+    else atomicAdd(&L.cnt[p], 1);
+  }
+}
+
+// seg[pixel] = start of a segment of cnt[pixel] keys.  The segments need not lie in pixel order (nothing reads across them), so a workgroup
+// sums its 1024 pixels and takes its range with ONE integer atomic instead of a device-wide scan.
+__global__ __launch_bounds__(256) void k_bev_tap_segments(int64_t npix, BevLists L) {
+  __shared__ int32_t wave_sum[4];
+  __shared__ int32_t block_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  int32_t c[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c[j] = p0 + j < npix ? L.cnt[p0 + j] : 0;
+  const int32_t mine = c[0] + c[1] + c[2] + c[3];
+  int32_t incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int32_t up = __shfl_up(incl, d);
+    if (lane >= d) incl += up;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int32_t all = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+    block_base = all ? atomicAdd(L.total, all) : 0;
+  }
+  __syncthreads();
+  int32_t at = block_base + incl - mine;
+  for (int w = 0; w < wave; ++w) at += wave_sum[w];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (p0 + j < npix) L.seg[p0 + j] = at;
+    at += c[j];
+  }
+}
+
+__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
+  return v;
+}
+
+// One wave per pixel.  The next term is the smallest key above the last one taken: lists of up to 64 keys sit in one register a lane, longer ones
+// (clustered keypoints) are read again for every term -- correct at any length, quadratic in it.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_bev_interp_grad_gather(const float* __restrict__ kps, const float* __restrict__ gout, BevGeom g,
+                                                                int64_t npix, BevLists L, float* __restrict__ gbev) {
+  constexpr int MAXV = 2;                                          // channel groups of 64 lanes held in registers at once: C <= 128 * VEC
+  const int lane = threadIdx.x & 63;
+  const int cv = g.C / VEC;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < npix; p += nwaves) {
+    const int32_t n = L.cnt[p];
+    const int32_t* keys = L.keys + (L.seg[p] - n);
+    const int32_t k0 = lane < n ? keys[lane] : INT32_MAX;
+    for (int cb = 0; cb < cv; cb += 64 * MAXV) {                  // one trip for C <= 128 * VEC
+      float acc[MAXV][VEC];
+#pragma unroll
+      for (int u = 0; u < MAXV; ++u)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[u][v] = 0.f;
+      int32_t last = -1;
+      for (int32_t i = 0; i < n; ++i) {
+        int32_t best = k0 > last ? k0 : INT32_MAX;
+        for (int32_t j = 64 + lane; j < n; j += 64) {
+          const int32_t k = keys[j];
+          if (k > last && k < best) best = k;
+        }
+        best = __builtin_amdgcn_readfirstlane(wave_min_i32(best));
+        last = best;
+        const int64_t m = best >> 2;
+        int b, x0, x1, y0, y1; float wa, wb, wc, wd;
+        bev_taps(kps + m * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
+        const int t = best & 3;
+        const float w = t == 0 ? wa : t == 1 ? wb : t == 2 ? wc : wd;
+        const float* go = gout + m * g.C;
+#pragma unroll
+        for (int u = 0; u < MAXV; ++u) {
+          const int c = cb + u * 64 + lane;
+          if (c < cv) {
+            if constexpr (VEC == 4) {
+              const float4 x = *reinterpret_cast<const float4*>(go + (int64_t)c * 4);
+              acc[u][0] = acc[u][0] + x.x * w; acc[u][1] = acc[u][1] + x.y * w;
+              acc[u][2] = acc[u][2] + x.z * w; acc[u][3] = acc[u][3] + x.w * w;
+            } else {
+              acc[u][0] = acc[u][0] + go[c] * w;
+            }
+          }
+        }
+      }
+      float* o = gbev + p * g.C;
+#pragma unroll
+      for (int u = 0; u < MAXV; ++u) {
+        const int c = cb + u * 64 + lane;
+        if (c < cv) {
+          if constexpr (VEC == 4) *reinterpret_cast<float4*>(o + (int64_t)c * 4) = make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+          else o[c] = acc[u][0];
+        }
+      }
+    }
+  }
+}
+
+static inline bool sv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int sv_bev_interpolate_nhwc(const float* keypoints, int64_t num_keypoints, const float* bev, int batch, int C, int H, int W, float x_min,
+                                       float y_min, float voxel_x, float voxel_y, float bev_stride, float* out, void* stream) {
+  SV_CHECK_ARG(num_keypoints >= 0 && batch > 0 && C > 0 && H > 0 && W > 0, "bev_interpolate_nhwc: bad arguments");
+  if (num_keypoints == 0) return SV_OK;
+  SV_CHECK_ARG(keypoints && bev && out, "bev_interpolate_nhwc: null pointer");
+  BevGeom g{x_min, y_min, voxel_x, voxel_y, bev_stride, batch, C, H, W};
+  if (C % 4 == 0 && sv_aligned16(bev) && sv_aligned16(out))
+    hipLaunchKernelGGL(k_bev_interp_cl<4>, dim3(sv_grid_1d(num_keypoints * (C / 4), 256, 256 * 16)), dim3(256), 0, sv_stream(stream), keypoints,
+                       num_keypoints, bev, g, out);
+  else
+    hipLaunchKernelGGL(k_bev_interp_cl<1>, dim3(sv_grid_1d(num_keypoints * C, 256, 256 * 16)), dim3(256), 0, sv_stream(stream), keypoints,
+                       num_keypoints, bev, g, out);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// layout: total (16 bytes) | cnt (B*H*W int32) | seg (B*H*W int32) | keys (4*M int32)
+extern "C" size_t sv_bev_interpolate_grad_nhwc_scratch_bytes(int64_t num_keypoints, int batch, int H, int W) {
+  if (num_keypoints < 0 || batch <= 0 || H <= 0 || W <= 0) return 0;
+  return 16 + ((size_t)batch * H * W * 2 + (size_t)num_keypoints * 4) * sizeof(int32_t);
+}
+
+extern "C" int sv_bev_interpolate_grad_nhwc(const float* keypoints, int64_t num_keypoints, const float* grad_out, int batch, int C, int H, int W,
+                                            float x_min, float y_min, float voxel_x, float voxel_y, float bev_stride, void* scratch,
+                                            float* grad_bev, void* stream) {
+  SV_CHECK_ARG(num_keypoints >= 0 && batch > 0 && C > 0 && H > 0 && W > 0 && grad_bev, "bev_interpolate_grad_nhwc: bad arguments");
+  const int64_t npix = (int64_t)batch * H * W;
+  SV_CHECK_ARG(npix < (int64_t)1 << 31 && num_keypoints < (int64_t)1 << 29, "bev_interpolate_grad_nhwc: pixel index or tap key exceeds int32");
+  hipStream_t st = sv_stream(stream);
+  if (num_keypoints == 0) {
+    SV_HIP(hipMemsetAsync(grad_bev, 0, (size_t)npix * C * 4, st));
+    return SV_OK;
+  }
+  SV_CHECK_ARG(keypoints && grad_out && scratch, "bev_interpolate_grad_nhwc: null pointer");
+  BevLists L;
+  L.total = reinterpret_cast<int32_t*>(scratch);
+  L.cnt = L.total + 4;
+  L.seg = L.cnt + npix;
+  L.keys = L.seg + npix;
+  SV_HIP(hipMemsetAsync(L.total, 0, 16 + (size_t)npix * 4, st));     // the allocator and the counts; the gradient map itself is never cleared
+  BevGeom g{x_min, y_min, voxel_x, voxel_y, bev_stride, batch, C, H, W};
+  const dim3 tap_grid(sv_grid_1d(num_keypoints * 4, 256));
+  hipLaunchKernelGGL(k_bev_tap_lists<0>, tap_grid, dim3(256), 0, st, keypoints, num_keypoints, g, L);
+  hipLaunchKernelGGL(k_bev_tap_segments, dim3((unsigned)((npix + 1023) / 1024)), dim3(256), 0, st, npix, L);
+  hipLaunchKernelGGL(k_bev_tap_lists<1>, tap_grid, dim3(256), 0, st, keypoints, num_keypoints, g, L);
+  const dim3 gather_grid(sv_grid_1d(npix * 64, 256, 256 * 16));
+  if (C % 4 == 0 && sv_aligned16(grad_out) && sv_aligned16(grad_bev))
+    hipLaunchKernelGGL(k_bev_interp_grad_gather<4>, gather_grid, dim3(256), 0, st, keypoints, grad_out, g, npix, L, grad_bev);
+  else
+    hipLaunchKernelGGL(k_bev_interp_grad_gather<1>, gather_grid, dim3(256), 0, st, keypoints, grad_out, g, npix, L, grad_bev);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // CenterHead target assignment (CenterHead.assign_targets / assign_target_of_single_head,
 // detector3d/pcdet/models/dense_heads/center_head.py:103-213 with gaussian_radius / draw_gaussian_to_heatmap,
 // models/model_utils/centernet_utils.py:9-69).  The reference loops over heads x scenes x boxes in python on CPU tensors

@@ -1,3 +1,5 @@
+import os
+
 import torch
 import torch.nn as nn
 
@@ -7,18 +9,34 @@ from ....ops.pointnet2.pointnet2_stack import pointnet2_utils as pointnet2_stack
 from ....utils import common_utils
 from ....utils.common_utils import cfg_get
 
+# 1: a channels_last fp32 map is read, and its gradient written, in place by the channel-last entries.  Opt-in until the route has been run and timed on
+# a GPU ("BEV keypoint features on the channels_last map"); 0 / unset: the map is copied to NCHW and back around the NCHW entries.
+BEV_INTERP_NHWC = os.environ.get("SEEVCN_BEV_INTERP_NHWC", "0") == "1"
+
 
 class _BevInterp(torch.autograd.Function):
+    """Bilinear BEV features at the keypoints.  With BEV_INTERP_NHWC a channels_last fp32 map (what HeightCompression hands a BaseBEVBackbone from 8
+    scenes on) is read and its gradient written in that layout by the library's channel-last entries: no copy of the map either way, and a gradient
+    whose summation order is fixed.  Every other map takes the NCHW entries."""
+
     @staticmethod
     def forward(ctx, bev, keypoints, x0, y0, vx, vy, stride):
         lib = _lib.load()
         _lib.require_cuda(bev, keypoints)
-        bev = bev.contiguous().float()
         kp = keypoints.contiguous().float()
         B, C, H, W = bev.shape
+        ctx.nhwc = (BEV_INTERP_NHWC and bev.dtype == torch.float32 and bev.is_contiguous(memory_format=torch.channels_last)
+                    and not bev.is_contiguous())
+        VoxelSetAbstraction.last_bev_layout = 'nhwc' if ctx.nhwc else 'nchw'
         out = torch.empty((kp.shape[0], C), dtype=torch.float32, device=bev.device)
-        rc = lib.sv_bev_interpolate(_lib.ptr(kp), kp.shape[0], _lib.ptr(bev), B, C, H, W, x0, y0, vx, vy, float(stride), _lib.ptr(out), _lib.stream())
-        _lib.check(rc, "sv_bev_interpolate")
+        if ctx.nhwc:
+            rc = lib.sv_bev_interpolate_nhwc(_lib.ptr(kp), kp.shape[0], _lib.ptr(bev.permute(0, 2, 3, 1)), B, C, H, W, x0, y0, vx, vy, float(stride),
+                                             _lib.ptr(out), _lib.stream())
+            _lib.check(rc, "sv_bev_interpolate_nhwc")
+        else:
+            bev = bev.contiguous().float()
+            rc = lib.sv_bev_interpolate(_lib.ptr(kp), kp.shape[0], _lib.ptr(bev), B, C, H, W, x0, y0, vx, vy, float(stride), _lib.ptr(out), _lib.stream())
+            _lib.check(rc, "sv_bev_interpolate")
         ctx.save_for_backward(kp)
         ctx.meta = (B, C, H, W, x0, y0, vx, vy, float(stride))
         return out
@@ -29,6 +47,13 @@ class _BevInterp(torch.autograd.Function):
         (kp,) = ctx.saved_tensors
         B, C, H, W, x0, y0, vx, vy, stride = ctx.meta
         g = grad_out.contiguous().float()
+        if ctx.nhwc:
+            gbev = torch.empty((B, H, W, C), dtype=torch.float32, device=g.device)
+            scratch = _lib.workspace.scratch("bev_interp_grad_nhwc", lib.sv_bev_interpolate_grad_nhwc_scratch_bytes(kp.shape[0], B, H, W), g.device)
+            rc = lib.sv_bev_interpolate_grad_nhwc(_lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch),
+                                                  _lib.ptr(gbev), _lib.stream())
+            _lib.check(rc, "sv_bev_interpolate_grad_nhwc")
+            return gbev.permute(0, 3, 1, 2), None, None, None, None, None, None      # (B, C, H, W) with channels_last strides
         gbev = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device)
         scratch = _lib.workspace.scratch("bev_interp_grad", lib.sv_bev_interpolate_grad_scratch_bytes(B, C, H, W), g.device)
         rc = lib.sv_bev_interpolate_grad(_lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch), _lib.ptr(gbev),
@@ -40,7 +65,10 @@ class _BevInterp(torch.autograd.Function):
 class VoxelSetAbstraction(nn.Module):
     """Drop-in for the reference VoxelSetAbstraction (backbones_3d/pfe/voxel_set_abstraction.py:122-411), FPS keypoints
     (POINT_SOURCE raw_points | voxel_centers, SAMPLE_METHOD FPS): all scenes are sampled in ONE stacked FPS launch, BEV
-    features are interpolated in place from the NCHW map, every SA source runs the HIP ball query / grouping."""
+    features are interpolated in place from the NCHW or the channels_last map (last_bev_layout says which entries the most recent interpolation
+    took), every SA source runs the HIP ball query / grouping."""
+
+    last_bev_layout = None      # 'nhwc' | 'nchw': written by _BevInterp.forward, so it is one value for the process
 
     def __init__(self, model_cfg, voxel_size, point_cloud_range, num_bev_features=None, num_rawpoint_features=None, **kwargs):
         super().__init__()
@@ -175,8 +203,9 @@ class VoxelSetAbstraction(nn.Module):
             feats.append(self.aggregate_keypoint_features_from_one_source(batch_size, self.SA_layers[k], xyz.contiguous(), t.features.contiguous(),
                                                                           t.indices[:, 0], new_xyz, new_xyz_batch_cnt))
         point_features = torch.cat(feats, dim=-1)
-        batch_dict['point_features_before_fusion'] = point_features.view(-1, point_features.shape[-1])
+        point_features = point_features.view(-1, point_features.shape[-1])
+        batch_dict['point_features_before_fusion'] = point_features     # the tensor the fusion reads: its gradient is the fusion's input gradient
         from .....dense_ops import run_sequential                       # Linear + BatchNorm1d + ReLU on the library's own GEMM / BatchNorm kernels
-        batch_dict['point_features'] = run_sequential(self.vsa_point_feature_fusion, point_features.view(-1, point_features.shape[-1]))
+        batch_dict['point_features'] = run_sequential(self.vsa_point_feature_fusion, point_features)
         batch_dict['point_coords'] = keypoints
         return batch_dict
