@@ -487,6 +487,24 @@ int sv_sa_train_backward(const float* xyz, const float* features, const float* n
                          const float* save_invstd1, const float* save_mean2, const float* save_invstd2, const float* sel, const uint8_t* arg,
                          const float* out, const float* grad_out, void* scratch, float* dy1, float* aux, float* scatter, float* grad_features,
                          float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* stream);
+/* sv_sa_train_backward with an order-fixed scatter (opt-in; replaces the atomicAdd scatter of group_points_grad_kernel_stack,
+ * group_points_gpu.cu:38-41, inside the autograd chain behind pointnet2_modules.py:96-110).  Same arguments and the same launches, except:
+ * the layer-1 launch scatters nothing, and scatter (N, C1) is then written once per element, without float atomics and without a zero-fill, as
+ *   scatter[n][c] = +0.0f + dz1[q * nsample + slot][c]   summed in ascending key q * nsample + slot
+ * over the slots of non-empty balls (idx[q][0] >= 0) with row_start[q] + idx[q][slot] == n; a point no key names is +0.0f.
+ * dz1[row][c] = fmaf(k[c], dy1[row][c], fmaf(A[c], z1[row][c], B[c])) with the layer-1 launch's own coefficients: after the call the first
+ * 4 * C1 floats of scratch hold {k, md, mx, mean} per channel, and A = -k * mx * save_invstd1, B = k * (mx * save_invstd1 * mean - md), every
+ * product and sum rounded to fp32.  Weight, BatchNorm and feature gradients come from the unchanged launches, which sum in a fixed order.
+ * scratch: sv_sa_train_backward_ordered_scratch_bytes bytes = the ordinary scratch followed by int32 key counts and segments per support point
+ * and twice the M * nsample keys; needs M * nsample < 2^31 and N < 2^31 (else an error, never the atomic route). */
+size_t sv_sa_train_backward_ordered_scratch_bytes(int64_t M, int64_t N, int C, int nsample, int C1, int C2);
+int sv_sa_train_backward_ordered(const float* xyz, const float* features, const float* new_xyz, const int32_t* idx, const int32_t* row_start,
+                                 int64_t M, int64_t N, int C, int nsample, const float* w1, const float* gamma1, const float* beta1, int C1,
+                                 const float* w2, const float* gamma2, const float* beta2, int C2, const float* z1, const float* z2,
+                                 const float* save_mean1, const float* save_invstd1, const float* save_mean2, const float* save_invstd2,
+                                 const float* sel, const uint8_t* arg, const float* out, const float* grad_out, void* scratch, float* dy1,
+                                 float* aux, float* scatter, float* grad_features, float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1,
+                                 float* dgamma2, float* dbeta2, void* stream);
 /* group_points_wrapper / group_points_grad_wrapper (src/group_points.cpp:31-69, kernels group_points_gpu.cu:15-102):
  * out (M,C,nsample)[m][c][s] = features[row_start[m] + idx[m][s]][c]; row_start[m] = first feature row of query m's scene.
  * The gradient zero-fills grad_features (N,C) and scatter-adds with fp32 atomics like the reference. */
@@ -494,6 +512,16 @@ int sv_group_points_stack(int M, int C, int nsample, const float* features, cons
                           float* out, void* stream);
 int sv_group_points_grad_stack(int M, int C, int N, int nsample, const float* grad_out, const int32_t* idx,
                                const int32_t* row_start, float* grad_features, void* stream);
+/* group_points_grad_wrapper (src/group_points.cpp:52-69, kernel group_points_gpu.cu:15-45) with a fixed summation order (opt-in): no float
+ * atomics, no zero-fill, every element of grad_features (N,C) written once as
+ *   grad_features[n][c] = +0.0f + grad_out[m][c][s]   summed in ascending key m * nsample + s
+ * over the pairs with row_start[m] + idx[m][s] == n, every sum rounded to fp32.  Slots that repeat the first neighbour are keys like any other;
+ * a slot with a negative idx (the empty-ball mark) or a row outside [0, N) names nothing; a row no key names is +0.0f.
+ * scratch: sv_group_points_grad_stack_ordered_scratch_bytes bytes (uninitialised): int32 key counts and segments per row and twice the
+ * M * nsample keys; needs M * nsample < 2^31 (else an error, never the atomic route). */
+size_t sv_group_points_grad_stack_ordered_scratch_bytes(int M, int N, int nsample);
+int sv_group_points_grad_stack_ordered(int M, int C, int N, int nsample, const float* grad_out, const int32_t* idx, const int32_t* row_start,
+                                       void* scratch, float* grad_features, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Rotated-box geometry (detector3d/pcdet/ops/iou3d_nms/src/iou3d_nms_api.cpp:12-17,
@@ -777,6 +805,16 @@ int sv_chamfer_forward(const float* xyz1, const float* xyz2, int batch, int n, i
                        int32_t* idx2, void* stream);
 int sv_chamfer_backward(const float* xyz1, const float* xyz2, const int32_t* idx1, const int32_t* idx2, const float* grad_dist1,
                         const float* grad_dist2, int batch, int n, int m, float* grad_xyz1, float* grad_xyz2, void* stream);
+/* chamfer backward (chamfer_cuda.cpp:38, chamfer_dist_grad_kernel chamfer.cu:134-166) with a fixed summation order (opt-in): the terms of
+ * sv_chamfer_backward, no float atomics, no zero-fill, every element written once.  For point (b, i) of cloud 1 and coordinate d:
+ *   grad_xyz1[b][i][d] = +0.0f + (2 * grad_dist1[b][i]) * (xyz1[b][i][d] - xyz2[b][idx1[b][i]][d])
+ *                              + -((2 * grad_dist2[b][k]) * (xyz2[b][k][d] - xyz1[b][i][d]))   for every k with idx2[b][k] == i, ascending k,
+ * every product and sum rounded to fp32; cloud 2 likewise (own term from direction 2, then the idx1 hits in ascending j).  The hits are found
+ * by a scan of the other cloud's idx: sv_chamfer_backward_ordered_scratch_bytes is 0 and scratch may be null.  batch <= 65535. */
+size_t sv_chamfer_backward_ordered_scratch_bytes(int batch, int n, int m);
+int sv_chamfer_backward_ordered(const float* xyz1, const float* xyz2, const int32_t* idx1, const int32_t* idx2, const float* grad_dist1,
+                                const float* grad_dist2, int batch, int n, int m, void* scratch, float* grad_xyz1, float* grad_xyz2,
+                                void* stream);
 
 /* ---- VCN post-processing (CPU code in the reference) ------------------------------------------
  * partial_with_KDTree / get_partial_mesh_batch (see/surface_completion/models/vcn/utils/sampling.py:8-41,69-81): per object,

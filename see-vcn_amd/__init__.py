@@ -7,5 +7,8 @@ Layout:
   pcdet/     mirror of the reference's pcdet module registries + op wrappers for this path
   vcn/       VCN_VC / VCN_CN / VCN.inference mirror
   synth.py   deterministic synthetic inputs (tests, bench)
+  ordered.py set_ordered_gradients / ordered_gradients: the opt-in order-fixed gradients of Chamfer and the stacked point ops
 """
 __version__ = "0.1.0"
+
+from .ordered import ordered_gradient_calls, ordered_gradients, set_ordered_gradients  # noqa: E402,F401

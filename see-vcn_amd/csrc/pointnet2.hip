@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "inverse_lists.h"
 
 // ------------------------------------------------------------------------------------------------
 // Farthest point sampling.  Selection rule reproduced exactly (index-exact, including ties):
@@ -548,6 +549,52 @@ extern "C" int sv_group_points_grad_stack(int M, int C, int N, int nsample, cons
   SV_CHECK_ARG(grad_out && idx && row_start, "group_points_grad: null pointer");
   const int64_t pairs = (int64_t)M * C;
   hipLaunchKernelGGL(k_group_points_grad, dim3(sv_grid_1d(pairs, 256, 256 * 64)), dim3(256), 0, st, pairs, C, nsample, grad_out, idx, row_start,
+                     grad_features);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+// The same gradient with a fixed summation order and no float atomics: grad_features[n][c] = +0.0f + grad_out[m][c][s] summed in ascending key
+// m * nsample + s over the pairs with row_start[m] + idx[m][s] == n (inverse_lists.h), every sum rounded to fp32; slots that repeat the first
+// neighbour are keys like any other.  One wave per support row, lanes along c, 128 channels a trip; every element is written once.
+__global__ __launch_bounds__(256) void k_group_points_grad_gather(int64_t N, int C, int nsample, const float* __restrict__ grad_out, SvInvLists L,
+                                                                  float* __restrict__ grad_features) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t n = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); n < N; n += nwaves) {
+    int32_t cnt;
+    const int32_t* keys = sv_inv_list(L, n, cnt);
+    for (int cb = 0; cb < C; cb += 128) {
+      const int c0 = cb + lane, c1 = cb + 64 + lane;
+      float a0 = 0.f, a1 = 0.f;
+      for (int32_t i = 0; i < cnt; ++i) {
+        const int32_t key = keys[i];
+        const int64_t m = key / nsample;
+        const float* g = grad_out + m * C * nsample + (key - m * nsample);
+        if (c0 < C) a0 = a0 + g[(int64_t)c0 * nsample];
+        if (c1 < C) a1 = a1 + g[(int64_t)c1 * nsample];
+      }
+      if (c0 < C) grad_features[n * C + c0] = a0;
+      if (c1 < C) grad_features[n * C + c1] = a1;
+    }
+  }
+}
+
+extern "C" size_t sv_group_points_grad_stack_ordered_scratch_bytes(int M, int N, int nsample) {
+  if (!sv_inv_lists_fit(M, nsample, N)) return 0;
+  return sv_inv_lists_bytes((int64_t)M * nsample, N);
+}
+
+extern "C" int sv_group_points_grad_stack_ordered(int M, int C, int N, int nsample, const float* grad_out, const int32_t* idx,
+                                                  const int32_t* row_start, void* scratch, float* grad_features, void* stream) {
+  SV_CHECK_ARG(M >= 0 && C > 0 && nsample > 0 && N >= 0, "group_points_grad_ordered: bad arguments");
+  SV_CHECK_ARG(sv_inv_lists_fit(M, nsample, N), "group_points_grad_ordered: the keys M * nsample (%d * %d) exceed int32", M, nsample);
+  if (N == 0) return SV_OK;
+  SV_CHECK_ARG(grad_features && scratch && (M == 0 || (grad_out && idx && row_start)), "group_points_grad_ordered: null pointer");
+  hipStream_t st = sv_stream(stream);
+  const SvInvLists L = sv_inv_lists_view(scratch, (int64_t)M * nsample, N);
+  if (int rc = sv_inv_lists_build(idx, row_start, M, nsample, N, false, L, st)) return rc;
+  hipLaunchKernelGGL(k_group_points_grad_gather, dim3(sv_grid_1d((int64_t)N * 64, 256, 256 * 16)), dim3(256), 0, st, (int64_t)N, C, nsample, grad_out, L,
                      grad_features);
   SV_LAUNCH_CHECK();
   return SV_OK;

@@ -25,6 +25,7 @@
 // At the RoI-grid pool (pvrcnn_head.py:64-109: 110 592 queries x 16 neighbours, C = 128, 64/64 channels): 43.5 GFLOP per scale on the fp32
 // matrix core (layer 2 forward, its data and weight gradients) instead of the 109 GFLOP of the literal formulation, 9 x 453 MB of per-row
 // traffic (z1, z2, dy1).
+#include "inverse_lists.h"
 #include "norm.h"
 
 typedef float st_f4 __attribute__((ext_vector_type(4)));
@@ -602,6 +603,28 @@ __global__ __launch_bounds__(SG_THREADS) void k_sa_bwd1(SaT a_in) {
   }
 }
 
+// Order-fixed form of bwd1's scatter (bwd1 then runs with S == nullptr): S[n][c] = +0.0f + dz1[row][c] summed in ascending row = q * nsample +
+// slot over the rows of non-empty balls whose neighbour is support point n (inverse_lists.h), dz1 recomputed per key with bwd1's own expression
+// and coefficients; every element written once, no float atomics.  A group of C1 lanes per support point (64 / C1 points a wave).
+__global__ __launch_bounds__(256) void k_sa_scatter_gather(SaT a, SvInvLists L) {
+  const int lane = threadIdx.x & 63;
+  const int per = 64 / a.C1, sub = lane / a.C1, c = lane - sub * a.C1;                 // C1 = 48: one point a wave, 16 idle lanes
+  if (sub >= per) return;
+  const float md = a.coef1[a.C1 + c], mx = a.coef1[2 * a.C1 + c], m = a.coef1[3 * a.C1 + c], is = a.istd1[c];
+  const float k = a.coef1[c], A = -k * mx * is, B = k * (mx * is * m - md);
+  const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6) * per;
+  for (int64_t n = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * per + sub; n < a.N; n += stride) {
+    int32_t cnt;
+    const int32_t* keys = sv_inv_list(L, n, cnt);
+    float acc = 0.f;
+    for (int32_t i = 0; i < cnt; ++i) {
+      const int64_t row = keys[i];
+      acc = acc + fmaf(k, a.dy1[row * a.C1 + c], fmaf(A, a.z1[row * a.C1 + c], B));
+    }
+    a.S[n * a.C1 + c] = acc;
+  }
+}
+
 // wgp: the feature columns of dW1 = S^T . F, a contraction over the N support points on the matrix core.  blockIdx.y = feature tile (16
 // columns of F), a wave takes 16 points at a time: A = S tile read column-wise (point 4 kk + s is the k index of MFMA s), B = F tile likewise.
 // Partial (gridDim.x, C1, C).
@@ -743,6 +766,8 @@ extern "C" size_t sv_sa_train_scratch_bytes(int C, int C1, int C2) {
   return (4 * (size_t)(C1 + C2) + (size_t)SG_GRID * 2 * ST_MAXC + w) * sizeof(float);
 }
 
+static size_t sa_lists_offset(int C, int C1, int C2) { return (sv_sa_train_scratch_bytes(C, C1, C2) + 15) & ~(size_t)15; }
+
 struct SaScratch {
   float *coef1, *coef2, *part, *wpart;
 };
@@ -802,18 +827,20 @@ extern "C" int sv_sa_train_forward(const float* xyz, const float* features, cons
 // grad_out (M, C2) -> grad_w1 (C1, 3 + C), grad_w2 (C2, C1), dgamma / dbeta of both norms, scatter (N, C1) = sum over a support point's
 // (query, slot) pairs of dz1 (zeroed here), grad_features (N, C) = scatter . w1[:, 3:] (null: not wanted).  z1 / z2 / sel / arg / out /
 // save_* as the forward left them; dy1 (R, C1) and aux (M, C2) are work buffers.
-extern "C" int sv_sa_train_backward(const float* xyz, const float* features, const float* new_xyz, const int32_t* idx, const int32_t* row_start,
-                                    int64_t M, int64_t N, int C, int nsample, const float* w1, const float* gamma1, const float* beta1, int C1,
-                                    const float* w2, const float* gamma2, const float* beta2, int C2, const float* z1, const float* z2,
-                                    const float* save_mean1, const float* save_invstd1, const float* save_mean2, const float* save_invstd2,
-                                    const float* sel, const uint8_t* arg, const float* out, const float* grad_out, void* scratch, float* dy1,
-                                    float* aux, float* scatter, float* grad_features, float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1,
-                                    float* dgamma2, float* dbeta2, void* stream) {
-  if (int rc = sa_train_check("sv_sa_train_backward", M, C, nsample, C1, C2)) return rc;
+// `ordered`: the scatter comes from k_sa_scatter_gather over inverse lists kept behind the ordinary scratch instead of bwd1's float atomics
+static int sa_train_backward(const char* who, bool ordered, const float* xyz, const float* features, const float* new_xyz, const int32_t* idx,
+                             const int32_t* row_start, int64_t M, int64_t N, int C, int nsample, const float* w1, const float* gamma1,
+                             const float* beta1, int C1, const float* w2, const float* gamma2, const float* beta2, int C2, const float* z1,
+                             const float* z2, const float* save_mean1, const float* save_invstd1, const float* save_mean2, const float* save_invstd2,
+                             const float* sel, const uint8_t* arg, const float* out, const float* grad_out, void* scratch, float* dy1, float* aux,
+                             float* scatter, float* grad_features, float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1, float* dgamma2,
+                             float* dbeta2, void* stream) {
+  if (int rc = sa_train_check(who, M, C, nsample, C1, C2)) return rc;
+  SV_CHECK_ARG(!ordered || sv_inv_lists_fit(M, nsample, N), "%s: the keys M * nsample or the point count exceed int32", who);
   SV_CHECK_ARG(xyz && new_xyz && idx && row_start && w1 && w2 && z1 && z2 && save_mean1 && save_invstd1 && save_mean2 && save_invstd2 && sel && arg &&
                    out && grad_out && scratch && dy1 && aux && grad_w1 && grad_w2 && dgamma1 && dbeta1 && dgamma2 && dbeta2 &&
                    ((features && scatter) || C == 0),
-               "sv_sa_train_backward: null pointer");
+               "%s: null pointer", who);
   hipStream_t st = sv_stream(stream);
   const SaScratch sc = sa_scratch(scratch, C1, C2);
   const int64_t R = M * nsample;
@@ -822,7 +849,7 @@ extern "C" int sv_sa_train_backward(const float* xyz, const float* features, con
   a.z1 = const_cast<float*>(z1), a.z2 = const_cast<float*>(z2), a.dy1 = dy1, a.part = sc.part, a.coef1 = sc.coef1, a.coef2 = sc.coef2;
   a.istd1 = save_invstd1, a.mean1 = save_mean1, a.istd2 = save_invstd2, a.mean2 = save_mean2;
   a.zmax = const_cast<float*>(sel), a.zmin = aux, a.amax = const_cast<uint8_t*>(arg), a.out = const_cast<float*>(out), a.dout = grad_out;
-  a.wpart = sc.wpart, a.S = C ? scatter : nullptr, a.M = M, a.N = N, a.C = C, a.Kp = 16 * (C / 16 + 1), a.C1 = C1, a.C2 = C2, a.ns = nsample;
+  a.wpart = sc.wpart, a.S = C && !ordered ? scatter : nullptr, a.M = M, a.N = N, a.C = C, a.Kp = 16 * (C / 16 + 1), a.C1 = C1, a.C2 = C2, a.ns = nsample;
   // BatchNorm 2 backward sums
   const int g0 = sa_grid(M, 64);
   hipLaunchKernelGGL(k_sa_bwd0, dim3(g0), dim3(256), 0, st, a);
@@ -842,13 +869,19 @@ extern "C" int sv_sa_train_backward(const float* xyz, const float* features, con
   b.gamma = gamma1, b.beta = beta1, b.save_mean = const_cast<float*>(save_mean1), b.save_invstd = const_cast<float*>(save_invstd1);
   b.dgamma = dgamma1, b.dbeta = dbeta1, b.coef = sc.coef1, b.C = C1, b.wgs = grid;
   sv_bn_finalize_bwd(b, st);
-  if (C) SV_HIP(hipMemsetAsync(scatter, 0, (size_t)N * C1 * sizeof(float), st));
+  if (a.S) SV_HIP(hipMemsetAsync(scatter, 0, (size_t)N * C1 * sizeof(float), st));
   const int grid1 = sg_grid(M);
   if (C1 == 64 && C2 == 64) hipLaunchKernelGGL((k_sa_bwd1<4, 4>), dim3(grid1), dim3(SG_THREADS), 0, st, a);
   else if (C1 == 32 && C2 == 32) hipLaunchKernelGGL((k_sa_bwd1<2, 2>), dim3(grid1), dim3(SG_THREADS), 0, st, a);
   else if (C1 == 16 && C2 == 16) hipLaunchKernelGGL((k_sa_bwd1<1, 1>), dim3(grid1), dim3(SG_THREADS), 0, st, a);
   else hipLaunchKernelGGL((k_sa_bwd1<0, 0>), dim3(grid1), dim3(SG_THREADS), 0, st, a);
   hipLaunchKernelGGL(k_sa_wreduce, dim3(sv_div_up((int64_t)C1 * 3, 16)), dim3(256), 0, st, sc.wpart, grid1, C1, 4, 3, grad_w1, C + 3, 0);      // xyz columns
+  if (C && ordered && N > 0) {                                                                                                    // the scatter, in key order
+    const SvInvLists L = sv_inv_lists_view(reinterpret_cast<char*>(scratch) + sa_lists_offset(C, C1, C2), R, N);
+    if (int rc = sv_inv_lists_build(idx, row_start, M, nsample, N, true, L, st)) return rc;
+    a.S = scatter;
+    hipLaunchKernelGGL(k_sa_scatter_gather, dim3(sv_grid_1d(sv_div_up(N, 64 / C1) * 64, 256, 256 * 16)), dim3(256), 0, st, a, L);
+  }
   if (C) {                                                                                                                        // feature columns
     const int gp = sv_grid_1d((N + 15) / 16, SP_THREADS / 64, WGP_GRID);
     hipLaunchKernelGGL(k_sa_wgrad1_points, dim3(gp, C / 16), dim3(SP_THREADS), 0, st, a);
@@ -857,4 +890,34 @@ extern "C" int sv_sa_train_backward(const float* xyz, const float* features, con
   if (C && grad_features) hipLaunchKernelGGL(k_sa_feat_grad, dim3(sv_grid_1d(N, 256 / (C / 4), 1024)), dim3(256), 0, st, scatter, w1, N, C, C1, grad_features);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+extern "C" int sv_sa_train_backward(const float* xyz, const float* features, const float* new_xyz, const int32_t* idx, const int32_t* row_start,
+                                    int64_t M, int64_t N, int C, int nsample, const float* w1, const float* gamma1, const float* beta1, int C1,
+                                    const float* w2, const float* gamma2, const float* beta2, int C2, const float* z1, const float* z2,
+                                    const float* save_mean1, const float* save_invstd1, const float* save_mean2, const float* save_invstd2,
+                                    const float* sel, const uint8_t* arg, const float* out, const float* grad_out, void* scratch, float* dy1,
+                                    float* aux, float* scatter, float* grad_features, float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1,
+                                    float* dgamma2, float* dbeta2, void* stream) {
+  return sa_train_backward("sv_sa_train_backward", false, xyz, features, new_xyz, idx, row_start, M, N, C, nsample, w1, gamma1, beta1, C1, w2, gamma2,
+                           beta2, C2, z1, z2, save_mean1, save_invstd1, save_mean2, save_invstd2, sel, arg, out, grad_out, scratch, dy1, aux, scatter,
+                           grad_features, grad_w1, grad_w2, dgamma1, dbeta1, dgamma2, dbeta2, stream);
+}
+
+// scratch: the ordinary scratch (16-byte rounded) | the inverse lists of (idx, row_start)
+extern "C" size_t sv_sa_train_backward_ordered_scratch_bytes(int64_t M, int64_t N, int C, int nsample, int C1, int C2) {
+  if (!sv_inv_lists_fit(M, nsample, N)) return 0;
+  return sa_lists_offset(C, C1, C2) + sv_inv_lists_bytes(M * nsample, N);
+}
+
+extern "C" int sv_sa_train_backward_ordered(const float* xyz, const float* features, const float* new_xyz, const int32_t* idx,
+                                            const int32_t* row_start, int64_t M, int64_t N, int C, int nsample, const float* w1, const float* gamma1,
+                                            const float* beta1, int C1, const float* w2, const float* gamma2, const float* beta2, int C2,
+                                            const float* z1, const float* z2, const float* save_mean1, const float* save_invstd1,
+                                            const float* save_mean2, const float* save_invstd2, const float* sel, const uint8_t* arg, const float* out,
+                                            const float* grad_out, void* scratch, float* dy1, float* aux, float* scatter, float* grad_features,
+                                            float* grad_w1, float* grad_w2, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* stream) {
+  return sa_train_backward("sv_sa_train_backward_ordered", true, xyz, features, new_xyz, idx, row_start, M, N, C, nsample, w1, gamma1, beta1, C1, w2,
+                           gamma2, beta2, C2, z1, z2, save_mean1, save_invstd1, save_mean2, save_invstd2, sel, arg, out, grad_out, scratch, dy1, aux,
+                           scatter, grad_features, grad_w1, grad_w2, dgamma1, dbeta1, dgamma2, dbeta2, stream);
 }

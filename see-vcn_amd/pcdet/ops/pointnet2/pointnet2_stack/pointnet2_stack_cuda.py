@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from ..... import _lib
+from ..... import _lib, ordered
 
 
 def _version(t):
@@ -87,6 +87,14 @@ def group_points_grad_wrapper(B, M, C, N, nsample, grad_out, idx, idx_batch_cnt,
     lib = _lib.load()
     _lib.require_cuda(grad_out, idx, grad_features)
     rs = _row_start(idx_batch_cnt, features_batch_cnt, M)
+    if ordered.ordered_gradients():                       # same terms in ascending (query, slot) order, no float atomics
+        nbytes = lib.sv_group_points_grad_stack_ordered_scratch_bytes(int(M), int(N), int(nsample))
+        scratch = _lib.workspace.scratch("group_grad_ordered", nbytes, grad_out.device)
+        rc = lib.sv_group_points_grad_stack_ordered(int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs),
+                                                    _lib.ptr(scratch), _lib.ptr(grad_features), _lib.stream())
+        _lib.check(rc, "sv_group_points_grad_stack_ordered")
+        ordered.count_call("group_points")
+        return 1
     rc = lib.sv_group_points_grad_stack(int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs),
                                         _lib.ptr(grad_features), _lib.stream())
     _lib.check(rc, "sv_group_points_grad_stack")

@@ -97,7 +97,7 @@ class SAScaleTrain(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from ..... import _lib
+        from ..... import _lib, ordered
         lib = _lib.load()
         xyz, features, new_xyz, idx, row_start, w1c, g1, b1, w2c, g2, b2, z1, z2, stats, sel, arg, out = ctx.saved_tensors
         dev = xyz.device
@@ -113,13 +113,19 @@ class SAScaleTrain(Function):
         gw1, gw2 = torch.empty((C1, C + 3), **f32), torch.empty((C2, C1), **f32)
         gbn = torch.empty((2 * C1 + 2 * C2,), **f32)
         dg1, db1, dg2, db2 = gbn[:C1], gbn[C1:2 * C1], gbn[2 * C1:2 * C1 + C2], gbn[2 * C1 + C2:]
-        scratch = _lib.workspace.scratch("sa_train", lib.sv_sa_train_scratch_bytes(C, C1, C2), dev)
-        _lib.check(lib.sv_sa_train_backward(_lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C,
-                                            ns, _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), C1, _lib.ptr(w2c), _lib.ptr(g2.detach()),
-                                            _lib.ptr(b2.detach()), C2, _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1), _lib.ptr(sm2), _lib.ptr(si2),
-                                            _lib.ptr(sel), _lib.ptr(arg), _lib.ptr(out), _lib.ptr(grad_out.contiguous()), _lib.ptr(scratch), _lib.ptr(dy1),
-                                            _lib.ptr(aux), _lib.ptr(scatter), _lib.ptr(gf), _lib.ptr(gw1), _lib.ptr(gw2), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dg2),
-                                            _lib.ptr(db2), _lib.stream()), "sv_sa_train_backward")
+        if ordered.ordered_gradients():                   # the scatter summed in ascending (query, slot) order instead of float atomics
+            entry, name = lib.sv_sa_train_backward_ordered, "sv_sa_train_backward_ordered"
+            scratch = _lib.workspace.scratch("sa_train_ordered", lib.sv_sa_train_backward_ordered_scratch_bytes(M, N, C, ns, C1, C2), dev)
+            ordered.count_call("sa_train")
+        else:
+            entry, name = lib.sv_sa_train_backward, "sv_sa_train_backward"
+            scratch = _lib.workspace.scratch("sa_train", lib.sv_sa_train_scratch_bytes(C, C1, C2), dev)
+        _lib.check(entry(_lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C,
+                         ns, _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), C1, _lib.ptr(w2c), _lib.ptr(g2.detach()),
+                         _lib.ptr(b2.detach()), C2, _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1), _lib.ptr(sm2), _lib.ptr(si2),
+                         _lib.ptr(sel), _lib.ptr(arg), _lib.ptr(out), _lib.ptr(grad_out.contiguous()), _lib.ptr(scratch), _lib.ptr(dy1),
+                         _lib.ptr(aux), _lib.ptr(scatter), _lib.ptr(gf), _lib.ptr(gw1), _lib.ptr(gw2), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dg2),
+                         _lib.ptr(db2), _lib.stream()), name)
         s1, s2 = ctx.w_shapes
         return (None, gf, None, None, None, gw1.view(s1), dg1, db1, gw2.view(s2), dg2, db2, None, None, None, None, None, None, None, None)
 
