@@ -598,8 +598,9 @@ int sv_bev_interpolate_grad(const float* keypoints, int64_t num_keypoints, const
  * Gradient: no float atomics and a fixed order.  grad_bev[pixel, c] = +0.0f + grad_out[m, c] * w_t summed in ascending key 4 * m + t over the
  * taps that land on the pixel (t = 0..3: the taps y0x0, y1x0, y0x1, y1x1 of keypoint m; two taps of one keypoint clamped onto one pixel are two
  * terms), every product and every sum rounded to fp32; a pixel without taps is +0.0f.  Every element is written exactly once, the map is never
- * cleared or copied.  scratch (sv_bev_interpolate_grad_nhwc_scratch_bytes bytes, uninitialised): int32 tap counts and key-list segments per
- * pixel and the 4 * M keys; needs B*H*W < 2^31 and M < 2^29.  M == 0 writes the zero map and reads no scratch. */
+ * cleared or copied.  scratch (sv_bev_interpolate_grad_nhwc_scratch_bytes bytes, uninitialised), int32 words: allocator (4) | tap counts
+ * (B*H*W) | key-list segments (B*H*W) | the 4 * M keys in arrival order | the 4 * M keys, every pixel's ascending; needs B*H*W < 2^31 and
+ * M < 2^29.  M == 0 writes the zero map and reads no scratch. */
 int sv_bev_interpolate_nhwc(const float* keypoints, int64_t num_keypoints, const float* bev, int batch, int C, int H, int W, float x_min,
                             float y_min, float voxel_x, float voxel_y, float bev_stride, float* out, void* stream);
 size_t sv_bev_interpolate_grad_nhwc_scratch_bytes(int64_t num_keypoints, int batch, int H, int W);

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "sparse_conv.h"
+#include "wave.h"
 
 // ================================================================================================
 // Plan of a rulebook table for the MFMA kernel
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(PL_WG) void k_plan_hist(PlanArgs a) {
 // consecutive classes per thread (a single 1024-thread workgroup for all regions took 17 us: one CU moving 0.5 MB).
 __global__ __launch_bounds__(128) void k_plan_scan(PlanArgs a) {
   constexpr int RC = PL_REGIONS * PL_CLASSES;
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, g = r * 128 + tid;      // g: global 32-class group
+  const int r = blockIdx.x, tid = threadIdx.x, g = r * 128 + tid;      // g: global 32-class group
   int32_t* cnt = a.hist + (size_t)g * 32;
   int v[32], sum = 0;
   {
@@ -111,12 +112,7 @@ __global__ __launch_bounds__(128) void k_plan_scan(PlanArgs a) {
 #pragma unroll
     for (int u = 0; u < 32; ++u) sum += v[u];
   }
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
+  const int incl = sv_wave_incl_scan(sum);
   __shared__ int s_wave0;
   if (tid == 63) s_wave0 = incl;
   __syncthreads();
@@ -267,8 +263,7 @@ extern "C" int sv_conv_table_rows(const int32_t* nbr, int64_t n_rows, int K, int
 // lanes 0..31, a round = 32 readlanes to rank the loads + the slot writes.  Deterministic (ties by bin index): a table still has one plan.
 // AND of a region's masks: lanes hand in the AND of their rows' masks (all ones without a row), one LDS atomic per wave
 __device__ __forceinline__ void plan_and_masks(unsigned* s_and, unsigned mine) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine &= (unsigned)__shfl_xor((int)mine, off, 64);
+  mine = sv_wave_reduce_and(mine);
   if ((threadIdx.x & 63) == 0) atomicAnd(s_and, mine);
 }
 // ... and only with at least four rounds of units to deal (a bin takes one unit per round whatever it costs: with two or three rounds a unit of four
@@ -459,12 +454,7 @@ __device__ __forceinline__ void plan_region_body(const PlanFusedArgs& a, const i
     int v[4], sum = 0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = s_start[tid * 4 + u], sum += v[u];
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
+    const int incl = sv_wave_incl_scan(sum);
     if (lane == 63) s_wsum[wid] = incl;
     __syncthreads();
     int run = (int)row0 + incl - sum;
@@ -601,12 +591,7 @@ __device__ __forceinline__ void plan_region_body_stable(const PlanFusedArgs& a, 
       }
       sum += tot[u];
     }
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
+    const int incl = sv_wave_incl_scan(sum);
     if (lane == 63) s_wsum[wid] = incl;
     __syncthreads();
     int run = incl - sum;

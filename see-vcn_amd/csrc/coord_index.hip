@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "wave.h"
 
 // ------------------------------------------------------------------ error state (per host thread)
 static thread_local char g_err[512] = "";
@@ -36,37 +37,6 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 4096 items per workgroup
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & (SV_WAVE - 1);
-#pragma unroll
-  for (int d = 1; d < SV_WAVE; d <<= 1) {
-    const int t = __shfl_up(v, d, SV_WAVE);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-// exclusive scan of one value per thread across the workgroup; returns exclusive prefix, *total = sum
-template <int THREADS>
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {
-  __shared__ int wsum[THREADS / SV_WAVE];
-  const int lane = threadIdx.x & (SV_WAVE - 1);
-  const int wid = threadIdx.x / SV_WAVE;
-  const int incl = wave_incl_scan(v);
-  if (lane == SV_WAVE - 1) wsum[wid] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < THREADS / SV_WAVE; ++i) {
-    const int s = wsum[i];
-    if (i < wid) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_block_sums(const int32_t* __restrict__ in, int64_t n,
                                                                   int32_t* __restrict__ block_sums) {
   const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
@@ -82,8 +52,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_block_sums(const int32_t*
     for (int i = 0; i < SCAN_ITEMS; ++i)
       if (base + i < n) s += in[base + i];
   }
+  __shared__ int wsum[SCAN_THREADS / SV_WAVE];
   int tot;
-  block_excl_scan<SCAN_THREADS>(s, &tot);
+  sv_block_excl_scan<SCAN_THREADS>(s, &tot, wsum);
+  __syncthreads();
   if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -92,10 +64,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_block_sums(const int32_t*
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_downsweep(const int32_t* __restrict__ in, int64_t n,
                                                                  const int32_t* __restrict__ block_sums,
                                                                  int32_t* __restrict__ out, int32_t* __restrict__ total_out) {
+  __shared__ int wsum[SCAN_THREADS / SV_WAVE];
   int before = 0;
   for (int j = threadIdx.x; j < (int)blockIdx.x; j += SCAN_THREADS) before += block_sums[j];
   int block_off;
-  block_excl_scan<SCAN_THREADS>(before, &block_off);
+  sv_block_excl_scan<SCAN_THREADS>(before, &block_off, wsum);
+  __syncthreads();                                       // wsum is used again below
   const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
   int v[SCAN_ITEMS];
   const bool full = base + SCAN_ITEMS <= n;
@@ -114,7 +88,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_downsweep(const int32_t* 
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; ++i) { const int t = v[i]; v[i] = s; s += t; }
   int tot;
-  const int off = block_excl_scan<SCAN_THREADS>(s, &tot) + block_off;
+  const int off = sv_block_excl_scan<SCAN_THREADS>(s, &tot, wsum) + block_off;
+  __syncthreads();
   if (total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = block_off + tot;
   if (full) {
     int4* q = reinterpret_cast<int4*>(out + base);

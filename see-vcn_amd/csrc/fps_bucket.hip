@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -34,15 +35,6 @@ __device__ __forceinline__ unsigned long long fb_key(float d, int k, int log2t) 
   const unsigned int rev = log2t ? (__brev(lo) >> (32 - log2t)) : 0u;
   const unsigned int tie = (rev << (31 - log2t)) | ((unsigned int)k >> log2t);
   return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0x7FFFFFFFu - tie);
-}
-
-__device__ __forceinline__ unsigned long long fb_wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
 }
 
 // wave-wide maximum of non-negative floats (and the -1.0f "nothing here" mark) as a uniform value: their bit patterns order as signed integers,
@@ -94,17 +86,6 @@ __device__ __forceinline__ float fb_min(float a, float b) {       // fminf witho
   return r;
 }
 
-__device__ __forceinline__ float fb_wave_min(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ float fb_wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-
 __device__ __forceinline__ float fb_readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 #ifdef FB_STATS
@@ -147,7 +128,7 @@ __global__ __launch_bounds__(FB_SORT_THREADS) void k_fps_bucket_sort(const float
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    lo[a] = fb_wave_min(lo[a]), hi[a] = fb_wave_max(hi[a]);
+    lo[a] = sv_wave_reduce_min(lo[a]), hi[a] = sv_wave_reduce_max(hi[a]);
     if (lane == 0) red[a][wid] = lo[a], red[3 + a][wid] = hi[a];
   }
   for (int c = tid; c < FB_CELLS; c += FB_SORT_THREADS) hist[c] = 0u;
@@ -196,12 +177,7 @@ __global__ __launch_bounds__(FB_SORT_THREADS) void k_fps_bucket_sort(const float
   unsigned int local[PER], sum = 0;
 #pragma unroll
   for (int i = 0; i < PER; ++i) local[i] = hist[tid * PER + i], sum += local[i];
-  unsigned int inc = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
+  const unsigned int inc = sv_wave_incl_scan(sum);
   if (lane == 63) wsum[wid] = inc;
   __syncthreads();
   unsigned int base = inc - sum;
@@ -248,10 +224,10 @@ __global__ __launch_bounds__(FB_THREADS) void k_fps_bucket(const float* __restri
     const bool ok = p < npad && sk[p] >= 0;
     const float x = p < npad ? sx[p] : 0.f, y = p < npad ? sy[p] : 0.f, z = p < npad ? sz[p] : 0.f, t = ok ? 1e10f : -1.f;
     px.set(i, x), py.set(i, y), pz.set(i, z), pt.set(i, t);
-    const float ax = fb_wave_min(ok ? x : 3.0e38f), bx = fb_wave_max(ok ? x : -3.0e38f);
-    const float ay = fb_wave_min(ok ? y : 3.0e38f), by = fb_wave_max(ok ? y : -3.0e38f);
-    const float az = fb_wave_min(ok ? z : 3.0e38f), bz = fb_wave_max(ok ? z : -3.0e38f);
-    const float any = fb_wave_max(t);
+    const float ax = sv_wave_reduce_min(ok ? x : 3.0e38f), bx = sv_wave_reduce_max(ok ? x : -3.0e38f);
+    const float ay = sv_wave_reduce_min(ok ? y : 3.0e38f), by = sv_wave_reduce_max(ok ? y : -3.0e38f);
+    const float az = sv_wave_reduce_min(ok ? z : 3.0e38f), bz = sv_wave_reduce_max(ok ? z : -3.0e38f);
+    const float any = sv_wave_reduce_max(t);
     if (lane == i) lox = ax, hix = bx, loy = ay, hiy = by, loz = az, hiz = bz, bmax = any;
   }
   if (tid == 0) idx[0] = add_offset ? start : 0;
@@ -330,7 +306,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_fps_bucket(const float* __restri
               if (key > best) best = key, bx = px.get(r), by = py.get(r), bz = pz.get(r), bp = p;
             }
           }
-          const unsigned long long wbest = fb_wave_max_u64(best);
+          const unsigned long long wbest = sv_wave_reduce_max(best);
           const int l = __ffsll((long long)__ballot(best == wbest)) - 1;      // keys are unique per point
           wx = fb_readlane(bx, l), wy = fb_readlane(by, l), wz = fb_readlane(bz, l);
           wpos = __builtin_amdgcn_readlane(bp, l);
@@ -355,7 +331,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_fps_bucket(const float* __restri
       src = __builtin_ctzll(tc);
     } else {
       const unsigned long long key = e.x == top ? fb_key(top, (int)s_orig[epos], log2t) : 0ull;
-      const unsigned long long kb = fb_wave_max_u64(key);
+      const unsigned long long kb = sv_wave_reduce_max(key);
       src = __ffsll((long long)__ballot(key == kb)) - 1;
     }
     x1 = fb_readlane(e.y, src), y1 = fb_readlane(e.z, src), z1 = fb_readlane(e.w, src);

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "inverse_lists.h"
 
 constexpr float PI_F = 3.14159265358979323846f;
 
@@ -362,15 +363,7 @@ __global__ __launch_bounds__(256) void k_bev_interp_cl(const float* __restrict__
 
 // Gradient on the channel-last map with a fixed summation order and no float atomics: every pixel's C floats are written once, as
 //   +0.0f + gout[m, :] * w_t   over the pixel's taps in ascending key 4 * m + t   (t = 0..3: wa, wb, wc, wd; each product and sum rounded to fp32).
-// The taps of a pixel are found through per-pixel key lists built with integer atomics: count the taps of every pixel, give every pixel a
-// segment of the key buffer, fill the segments (in arrival order -- the gather orders them), then one wave per pixel gathers.
-struct BevLists {
-  int32_t* total;   // 1 word (+3 of padding): the segment allocator
-  int32_t* cnt;     // (B * H * W) taps per pixel
-  int32_t* seg;     // (B * H * W) segment start; the fill advances it to the segment's end
-  int32_t* keys;    // (4 * M)
-};
-
+// The taps of a pixel are its inverse list (inverse_lists.h) under BevTapRow; one wave per pixel walks it.
 __device__ __forceinline__ void bev_tap_pixels(const BevGeom& g, int b, int x0, int x1, int y0, int y1, int64_t pix[4]) {
   const int64_t base = (int64_t)b * g.H * g.W;
   pix[0] = base + (int64_t)y0 * g.W + x0;       // wa
@@ -379,90 +372,40 @@ __device__ __forceinline__ void bev_tap_pixels(const BevGeom& g, int b, int x0, 
   pix[3] = base + (int64_t)y1 * g.W + x1;       // wd
 }
 
-// FILL == 0: cnt[pixel] += 1 per tap.  FILL == 1: keys[seg[pixel]++] = 4 * m + t.
-template <int FILL>
-__global__ __launch_bounds__(256) void k_bev_tap_lists(const float* __restrict__ kps, int64_t M, BevGeom g, BevLists L) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M * 4; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t m = e >> 2;
-    const int t = (int)(e & 3);
+// Key 4 * m + t names the pixel of tap t of keypoint m; a keypoint whose batch index is out of range has no taps.
+struct BevTapRow {
+  const float* kps;
+  BevGeom g;
+  __device__ __forceinline__ int64_t operator()(int64_t key) const {
     int b, x0, x1, y0, y1; float wa, wb, wc, wd;
-    bev_taps(kps + m * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
-    if (b < 0 || b >= g.B) continue;
+    bev_taps(kps + (key >> 2) * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
+    if (b < 0 || b >= g.B) return -1;
     int64_t pix[4];
     bev_tap_pixels(g, b, x0, x1, y0, y1, pix);
-    const int64_t p = t == 0 ? pix[0] : t == 1 ? pix[1] : t == 2 ? pix[2] : pix[3];
-    if (FILL) L.keys[atomicAdd(&L.seg[p], 1)] = (int32_t)e;
-    else atomicAdd(&L.cnt[p], 1);
+    const int t = (int)(key & 3);
+    return t == 0 ? pix[0] : t == 1 ? pix[1] : t == 2 ? pix[2] : pix[3];
   }
-}
+};
 
-// seg[pixel] = start of a segment of cnt[pixel] keys.  The segments need not lie in pixel order (nothing reads across them), so a workgroup
-// sums its 1024 pixels and takes its range with ONE integer atomic instead of a device-wide scan.
-__global__ __launch_bounds__(256) void k_bev_tap_segments(int64_t npix, BevLists L) {
-  __shared__ int32_t wave_sum[4];
-  __shared__ int32_t block_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  int32_t c[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c[j] = p0 + j < npix ? L.cnt[p0 + j] : 0;
-  const int32_t mine = c[0] + c[1] + c[2] + c[3];
-  int32_t incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int32_t up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int32_t all = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-    block_base = all ? atomicAdd(L.total, all) : 0;
-  }
-  __syncthreads();
-  int32_t at = block_base + incl - mine;
-  for (int w = 0; w < wave; ++w) at += wave_sum[w];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (p0 + j < npix) L.seg[p0 + j] = at;
-    at += c[j];
-  }
-}
-
-__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-  return v;
-}
-
-// One wave per pixel.  The next term is the smallest key above the last one taken: lists of up to 64 keys sit in one register a lane, longer ones
-// (clustered keypoints) are read again for every term -- correct at any length, quadratic in it.
+// One wave per pixel, the terms in the order of the pixel's list.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_bev_interp_grad_gather(const float* __restrict__ kps, const float* __restrict__ gout, BevGeom g,
-                                                                int64_t npix, BevLists L, float* __restrict__ gbev) {
+                                                                int64_t npix, SvInvLists L, float* __restrict__ gbev) {
   constexpr int MAXV = 2;                                          // channel groups of 64 lanes held in registers at once: C <= 128 * VEC
   const int lane = threadIdx.x & 63;
   const int cv = g.C / VEC;
   const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
   for (int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < npix; p += nwaves) {
-    const int32_t n = L.cnt[p];
-    const int32_t* keys = L.keys + (L.seg[p] - n);
-    const int32_t k0 = lane < n ? keys[lane] : INT32_MAX;
+    int32_t n;
+    const int32_t* keys = sv_inv_list(L, p, n);
     for (int cb = 0; cb < cv; cb += 64 * MAXV) {                  // one trip for C <= 128 * VEC
       float acc[MAXV][VEC];
 #pragma unroll
       for (int u = 0; u < MAXV; ++u)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[u][v] = 0.f;
-      int32_t last = -1;
       for (int32_t i = 0; i < n; ++i) {
-        int32_t best = k0 > last ? k0 : INT32_MAX;
-        for (int32_t j = 64 + lane; j < n; j += 64) {
-          const int32_t k = keys[j];
-          if (k > last && k < best) best = k;
-        }
-        best = __builtin_amdgcn_readfirstlane(wave_min_i32(best));
-        last = best;
+        const int32_t best = __builtin_amdgcn_readfirstlane(keys[i]);
         const int64_t m = best >> 2;
         int b, x0, x1, y0, y1; float wa, wb, wc, wd;
         bev_taps(kps + m * 4, g, b, x0, x1, y0, y1, wa, wb, wc, wd);
@@ -514,10 +457,10 @@ extern "C" int sv_bev_interpolate_nhwc(const float* keypoints, int64_t num_keypo
   return SV_OK;
 }
 
-// layout: total (16 bytes) | cnt (B*H*W int32) | seg (B*H*W int32) | keys (4*M int32)
+// an SvInvLists of 4 * M keys over B * H * W rows
 extern "C" size_t sv_bev_interpolate_grad_nhwc_scratch_bytes(int64_t num_keypoints, int batch, int H, int W) {
   if (num_keypoints < 0 || batch <= 0 || H <= 0 || W <= 0) return 0;
-  return 16 + ((size_t)batch * H * W * 2 + (size_t)num_keypoints * 4) * sizeof(int32_t);
+  return sv_inv_lists_bytes(num_keypoints * 4, (int64_t)batch * H * W);
 }
 
 extern "C" int sv_bev_interpolate_grad_nhwc(const float* keypoints, int64_t num_keypoints, const float* grad_out, int batch, int C, int H, int W,
@@ -532,17 +475,9 @@ extern "C" int sv_bev_interpolate_grad_nhwc(const float* keypoints, int64_t num_
     return SV_OK;
   }
   SV_CHECK_ARG(keypoints && grad_out && scratch, "bev_interpolate_grad_nhwc: null pointer");
-  BevLists L;
-  L.total = reinterpret_cast<int32_t*>(scratch);
-  L.cnt = L.total + 4;
-  L.seg = L.cnt + npix;
-  L.keys = L.seg + npix;
-  SV_HIP(hipMemsetAsync(L.total, 0, 16 + (size_t)npix * 4, st));     // the allocator and the counts; the gradient map itself is never cleared
   BevGeom g{x_min, y_min, voxel_x, voxel_y, bev_stride, batch, C, H, W};
-  const dim3 tap_grid(sv_grid_1d(num_keypoints * 4, 256));
-  hipLaunchKernelGGL(k_bev_tap_lists<0>, tap_grid, dim3(256), 0, st, keypoints, num_keypoints, g, L);
-  hipLaunchKernelGGL(k_bev_tap_segments, dim3((unsigned)((npix + 1023) / 1024)), dim3(256), 0, st, npix, L);
-  hipLaunchKernelGGL(k_bev_tap_lists<1>, tap_grid, dim3(256), 0, st, keypoints, num_keypoints, g, L);
+  const SvInvLists L = sv_inv_lists_view(scratch, num_keypoints * 4, npix);
+  if (int rc = sv_inv_lists_build(num_keypoints * 4, npix, BevTapRow{keypoints, g}, L, st)) return rc;      // the gradient map itself is never cleared
   const dim3 gather_grid(sv_grid_1d(npix * 64, 256, 256 * 16));
   if (C % 4 == 0 && sv_aligned16(grad_out) && sv_aligned16(grad_bev))
     hipLaunchKernelGGL(k_bev_interp_grad_gather<4>, gather_grid, dim3(256), 0, st, keypoints, grad_out, g, npix, L, grad_bev);

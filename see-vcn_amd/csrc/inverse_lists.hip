@@ -1,47 +1,21 @@
-// Inverse neighbour lists of an (idx, row_start) pair -- see inverse_lists.h.
+// Inverse lists: the kernels that do not depend on how a key finds its row -- see inverse_lists.h.
 #include "inverse_lists.h"
-
-// FILL == 0: cnt[row] += 1 per key.  FILL == 1: raw[seg[row]++] = key.
-template <int FILL>
-__global__ __launch_bounds__(256) void k_inv_keys(const int32_t* __restrict__ idx, const int32_t* __restrict__ row_start, int64_t nkeys, int nsample,
-                                                  int64_t N, int skip_empty_balls, SvInvLists L) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nkeys; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t m = e / nsample;
-    const int32_t j = idx[e];
-    if (j < 0 || (skip_empty_balls && idx[m * nsample] < 0)) continue;
-    const int64_t row = (int64_t)row_start[m] + j;
-    if (row < 0 || row >= N) continue;
-    if (FILL) L.raw[atomicAdd(&L.seg[row], 1)] = (int32_t)e;
-    else atomicAdd(&L.cnt[row], 1);
-  }
-}
+#include "wave.h"
 
 // seg[row] = start of a segment of cnt[row] keys.  The segments need not lie in row order (nothing reads across them), so a workgroup sums its
 // 1024 rows and takes its range with ONE integer atomic instead of a device-wide scan.
 __global__ __launch_bounds__(256) void k_inv_segments(int64_t N, SvInvLists L) {
   __shared__ int32_t wave_sum[4];
   __shared__ int32_t block_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   int32_t c[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) c[j] = p0 + j < N ? L.cnt[p0 + j] : 0;
-  const int32_t mine = c[0] + c[1] + c[2] + c[3];
-  int32_t incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int32_t up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
+  int32_t all;
+  const int32_t before = sv_block_excl_scan<256>(c[0] + c[1] + c[2] + c[3], &all, wave_sum);
+  if (threadIdx.x == 0) block_base = all ? atomicAdd(L.total, all) : 0;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int32_t all = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-    block_base = all ? atomicAdd(L.total, all) : 0;
-  }
-  __syncthreads();
-  int32_t at = block_base + incl - mine;
-  for (int w = 0; w < wave; ++w) at += wave_sum[w];
+  int32_t at = block_base + before;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (p0 + j < N) L.seg[p0 + j] = at;
@@ -68,20 +42,10 @@ __global__ __launch_bounds__(256) void k_inv_sort(int64_t N, SvInvLists L) {
   }
 }
 
-int sv_inv_lists_build(const int32_t* idx, const int32_t* row_start, int64_t M, int nsample, int64_t N, bool skip_empty_balls, const SvInvLists& L,
-                       hipStream_t st) {
-  if (N == 0) return SV_OK;
-  SV_HIP(hipMemsetAsync(L.total, 0, 16 + (size_t)N * 4, st));          // the allocator and the counts
-  const int64_t nkeys = M * nsample;
-  if (nkeys > 0) {
-    const dim3 key_grid(sv_grid_1d(nkeys, 256));
-    hipLaunchKernelGGL(k_inv_keys<0>, key_grid, dim3(256), 0, st, idx, row_start, nkeys, nsample, N, (int)skip_empty_balls, L);
-    hipLaunchKernelGGL(k_inv_segments, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, st, N, L);
-    hipLaunchKernelGGL(k_inv_keys<1>, key_grid, dim3(256), 0, st, idx, row_start, nkeys, nsample, N, (int)skip_empty_balls, L);
-    hipLaunchKernelGGL(k_inv_sort, dim3(sv_grid_1d(N * 64, 256, 256 * 16)), dim3(256), 0, st, N, L);
-  } else {
-    SV_HIP(hipMemsetAsync(L.seg, 0, (size_t)N * 4, st));
-  }
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+void sv_inv_lists_launch_segments(int64_t nrows, const SvInvLists& L, hipStream_t st) {
+  hipLaunchKernelGGL(k_inv_segments, dim3((unsigned)((nrows + 1023) / 1024)), dim3(256), 0, st, nrows, L);
+}
+
+void sv_inv_lists_launch_sort(int64_t nrows, const SvInvLists& L, hipStream_t st) {
+  hipLaunchKernelGGL(k_inv_sort, dim3(sv_grid_1d(nrows * 64, 256, 256 * 16)), dim3(256), 0, st, nrows, L);
 }

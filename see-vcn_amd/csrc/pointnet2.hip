@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wave.h"
 #include "inverse_lists.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -32,15 +33,6 @@ __device__ __forceinline__ unsigned long long fps_key(float d, int k, int log2t)
   const unsigned int rev = log2t ? (__brev(lo) >> (32 - log2t)) : 0u;
   const unsigned int tie = (rev << (31 - log2t)) | ((unsigned int)k >> log2t);   // smaller tie = preferred
   return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0x7FFFFFFFu - tie);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
 }
 
 // one workgroup per scene; xyz (n,3) of the scene, idx (m) output (scene-local indices, + start when add_offset)
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_reg(const float* __restrict
       bx = up ? px[i] : bx; by = up ? py[i] : by; bz = up ? pz[i] : bz;
     }
     const unsigned long long best = bk >= 0 ? fps_key(bd, bk, l2) : 0ull;
-    const unsigned long long wbest = wave_max_u64(best);
+    const unsigned long long wbest = sv_wave_reduce_max(best);
     // the lane that holds the wave's winner publishes key + coordinates (keys are unique per point)
     if (best == wbest && best != 0ull) {
       skey[par][wid] = wbest;
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_reg(const float* __restrict
     __syncthreads();                                            // the only barrier of the round (slots alternate by parity)
     const int sl = lane & (NW - 1);
     const unsigned long long mine = skey[par][sl];
-    const unsigned long long w = wave_max_u64(mine);            // every wave reduces the 16 partials redundantly
+    const unsigned long long w = sv_wave_reduce_max(mine);            // every wave reduces the 16 partials redundantly
     const int src = __ffsll((long long)__ballot(mine == w)) - 1;
     x1 = __shfl(sxyz[par][sl][0], src, 64);
     y1 = __shfl(sxyz[par][sl][1], src, 64);
@@ -151,11 +143,11 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_stream(const float* __restr
       const unsigned long long key = fps_key(d2, k, log2t);
       best = key > best ? key : best;
     }
-    best = wave_max_u64(best);
+    best = sv_wave_reduce_max(best);
     if (lane == 0) slot[par][wid] = best;
     __syncthreads();
     unsigned long long w = slot[par][lane & (FPS_THREADS / 64 - 1)];
-    w = wave_max_u64(w);
+    w = sv_wave_reduce_max(w);
     const unsigned int tie = 0x7FFFFFFFu - (unsigned int)(w & 0xFFFFFFFFull);
     const unsigned int rev = log2t ? (tie >> (31 - log2t)) : 0u;
     const unsigned int lo = log2t ? (__brev(rev) >> (32 - log2t)) : 0u;
@@ -245,7 +237,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_multi(const float* __restri
       bx = up ? px[i] : bx; by = up ? py[i] : by; bz = up ? pz[i] : bz;
     }
     const unsigned long long best = bk >= 0 ? fps_key(bd, bk, log2t) : 0ull;
-    const unsigned long long wbest = wave_max_u64(best);
+    const unsigned long long wbest = sv_wave_reduce_max(best);
     if (best == wbest && best != 0ull) {
       skey[par][wid] = wbest;
       sxyz[par][wid][0] = bx; sxyz[par][wid][1] = by; sxyz[par][wid][2] = bz;
@@ -258,7 +250,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_multi(const float* __restri
     if (wid == 0) {                                             // this workgroup's candidate -> its record
       const int sl = lane & (NW - 1);
       const unsigned long long mine = skey[par][sl];
-      const unsigned long long wg_best = wave_max_u64(mine);
+      const unsigned long long wg_best = sv_wave_reduce_max(mine);
       const int src = __ffsll((long long)__ballot(mine == wg_best)) - 1;
       if (lane == src || lane == src + NW) {                    // two lanes hold the winner (NW < 64): one stores each granule
         fps_u32x4 v;
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_multi(const float* __restri
       __builtin_amdgcn_s_sleep(1);
     }
     const unsigned long long key = lane < FPS_W ? ((unsigned long long)g.y << 32) | g.x : 0ull;
-    const unsigned long long win = wave_max_u64(key);
+    const unsigned long long win = sv_wave_reduce_max(key);
     const int wl = __ffsll((long long)__ballot(lane < FPS_W && key == win)) - 1;
     x1 = __uint_as_float(__shfl(g.z, wl, 64));
     y1 = __uint_as_float(__shfl(g.x, wl + FPS_W, 64));
@@ -593,7 +585,7 @@ extern "C" int sv_group_points_grad_stack_ordered(int M, int C, int N, int nsamp
   SV_CHECK_ARG(grad_features && scratch && (M == 0 || (grad_out && idx && row_start)), "group_points_grad_ordered: null pointer");
   hipStream_t st = sv_stream(stream);
   const SvInvLists L = sv_inv_lists_view(scratch, (int64_t)M * nsample, N);
-  if (int rc = sv_inv_lists_build(idx, row_start, M, nsample, N, false, L, st)) return rc;
+  if (int rc = sv_inv_lists_build((int64_t)M * nsample, N, SvBallRow{idx, row_start, nsample, false}, L, st)) return rc;
   hipLaunchKernelGGL(k_group_points_grad_gather, dim3(sv_grid_1d((int64_t)N * 64, 256, 256 * 16)), dim3(256), 0, st, (int64_t)N, C, nsample, grad_out, L,
                      grad_features);
   SV_LAUNCH_CHECK();
@@ -650,12 +642,7 @@ __global__ __launch_bounds__(1024) void k_bqh_scan(int32_t* __restrict__ count, 
     int4 v = make_int4(0, 0, 0, 0);
     if (e < T) v = *reinterpret_cast<const int4*>(count + e);           // T is a power of two >= 4096
     const int local = v.x + v.y + v.z + v.w;
-    int inc = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(inc, off);
-      if (lane >= off) inc += o;
-    }
+    const int inc = sv_wave_incl_scan(local);
     if (lane == 63) s_wave[wid] = inc;
     __syncthreads();
     int base = s_carry;
@@ -703,9 +690,7 @@ __device__ __forceinline__ int bqh_take_min(int32_t* list, int L, int lane) {
     const int v = list[t];
     if (v < best) best = v, at = t;
   }
-  int wb = best;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wb = min(wb, __shfl_xor(wb, off));
+  const int wb = sv_wave_reduce_min(best);
   const unsigned long long own = __ballot(best == wb && at >= 0);
   if (own && lane == __ffsll((long long)own) - 1) list[at] = 0x7fffffff;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -738,12 +723,7 @@ __global__ __launch_bounds__(256) void k_bqh_query(int M, const float* __restric
       n = start[bk + 1] - s;
       beg[lane] = s;
     }
-    int inc = n;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      const int o = __shfl_up(inc, off);
-      if (lane >= off) inc += o;
-    }
+    const int inc = sv_wave_incl_scan<32>(n);                         // lanes 0..26 hold the cells
     if (lane < 27) pre[lane + 1] = inc;
     if (lane == 0) pre[0] = 0;
     const int total = __shfl(inc, 26);

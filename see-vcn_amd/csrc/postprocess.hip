@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define PP_MAXN 1024     // points per object (resample_num and the network's coarse size)
 #define PP_THREADS 1024
@@ -18,16 +19,6 @@ __device__ __forceinline__ bool lex_less(float ax, float ay, float az, float bx,
   if (ax != bx) return ax < bx;
   if (ay != by) return ay < by;
   return az < bz;
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
-    unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
 }
 
 // CPython 3.10 set insertion order for small non-negative ints (hash(v) == v): Objects/setobject.c set_add_entry /
@@ -492,11 +483,7 @@ __global__ __launch_bounds__(256) void k_points_near_set(const float* __restrict
 #pragma unroll
       for (int c = 0; c < D; ++c) {
         float lo = dropped ? INFINITY : s_r[t * D + c], hi = dropped ? -INFINITY : s_r[t * D + c];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          lo = fminf(lo, __shfl_xor(lo, off));
-          hi = fmaxf(hi, __shfl_xor(hi, off));
-        }
+        lo = sv_wave_reduce_min(lo), hi = sv_wave_reduce_max(hi);
         if ((threadIdx.x & 63) == 0) s_wlo[threadIdx.x >> 6][c] = lo, s_whi[threadIdx.x >> 6][c] = hi;
       }
     }
@@ -555,8 +542,7 @@ __global__ __launch_bounds__(256) void k_unique_compact(const int32_t* __restric
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int acc = 0;
   for (int i = tid; i < b; i += 256) acc += counts[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  acc = sv_wave_reduce_sum(acc);
   if (lane == 0) s_part[wave] = acc;
   __syncthreads();
   const int first = s_part[0] + s_part[1] + s_part[2] + s_part[3];
@@ -711,11 +697,7 @@ __global__ __launch_bounds__(NB_TILE) void k_near_boxes(const float* __restrict_
 #pragma unroll
   for (int c = 0; c < D; ++c) {
     float lo = live ? r[i * D + c] : INFINITY, hi = live ? r[i * D + c] : -INFINITY;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = fminf(lo, __shfl_xor(lo, off));
-      hi = fmaxf(hi, __shfl_xor(hi, off));
-    }
+    lo = sv_wave_reduce_min(lo), hi = sv_wave_reduce_max(hi);
     if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6][c] = lo, s_hi[threadIdx.x >> 6][c] = hi;
   }
   __syncthreads();

@@ -13,6 +13,7 @@
 // spconv is an un-vendored third-party dependency of the reference (docker/Dockerfile:58); call sites replaced:
 // detector3d/pcdet/models/backbones_3d/spconv_backbone.py:77-117 (layer definitions), :141-157 (forward).
 #include "common.h"
+#include "wave.h"
 
 struct ConvGeom {
   int batch;
@@ -58,12 +59,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_index_prefix(SvIndexView ix, int
         const int64_t w = cc * SV_CHUNK_WORDS + (lane & 31);
         const uint32_t bits = ix.words[w].x;
         int p = __popc(bits);
-        int incl = p;
-#pragma unroll
-        for (int d = 1; d < 32; d <<= 1) {
-          const int t = __shfl_up(incl, d, 32);
-          if ((lane & 31) >= d) incl += t;
-        }
+        const int incl = sv_wave_incl_scan<32>(p);
         if (bits) ix.words[w].y = (uint32_t)(ix.chunk_base[cc] + incl - p);
       }
     }
@@ -437,12 +433,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_index_count(SvIndexView ix, int6
     const int64_t w = c * SV_CHUNK_WORDS + lane;
     const uint32_t bits = ix.words[w].x;
     const int p = __popc(bits);
-    int incl = p;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const int t = __shfl_up(incl, d, 32);
-      if (lane >= d) incl += t;
-    }
+    const int incl = sv_wave_incl_scan<32>(p);
     if (bits) ix.words[w].y = (uint32_t)(incl - p);
     if (lane == 31) ix.chunk_cnt[c] = incl;
   }
@@ -719,12 +710,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_chain_count(SvIndexView ix, int6
     if (!((any >> (32 * (sub & 1))) & 0xffffffffull)) continue;         // uniform over the 32-lane group
     const int64_t c = c0 + sub + (RB_THREADS / 32) * i;
     const int p = __popc(bits[i]);
-    int incl = p;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const int t = __shfl_up(incl, d, 32);
-      if (lane >= d) incl += t;
-    }
+    const int incl = sv_wave_incl_scan<32>(p);
     if (bits[i]) ix.words[c * SV_CHUNK_WORDS + lane].y = (uint32_t)(incl - p);
     if (lane == 31) ix.chunk_cnt[c] = incl, mine += incl;
   }
@@ -752,17 +738,11 @@ __global__ __launch_bounds__(RB_THREADS) void k_chain_emit(SvIndexView ix, int64
   const int tid = threadIdx.x, lane32 = tid & 31, sub = tid >> 5, b = blockIdx.x, lane = tid & 63, wid = tid >> 6;
   int before = 0;
   for (int j = tid; j < b; j += RB_THREADS) before += block_sums[j];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, SV_WAVE);
+  before = sv_wave_reduce_sum(before);
   // exclusive scan of the block's chunk counts (one chunk per thread: CH_BLOCK == RB_THREADS) and the list of its non-empty chunks
   const int64_t c_mine = (int64_t)b * CH_BLOCK + tid;
   const int cnt = c_mine < nchunks ? ix.chunk_cnt[c_mine] : 0;
-  int incl = cnt;
-#pragma unroll
-  for (int d = 1; d < SV_WAVE; d <<= 1) {
-    const int t = __shfl_up(incl, d, SV_WAVE);
-    if (lane >= d) incl += t;
-  }
+  const int incl = sv_wave_incl_scan(cnt);
   const unsigned long long ne = __ballot(cnt > 0);
   if (lane == 0) s_red[wid] = before, s_wne[wid] = __popcll(ne);
   if (lane == 63) s_wtot[wid] = incl;

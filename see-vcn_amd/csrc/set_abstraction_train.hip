@@ -878,7 +878,7 @@ static int sa_train_backward(const char* who, bool ordered, const float* xyz, co
   hipLaunchKernelGGL(k_sa_wreduce, dim3(sv_div_up((int64_t)C1 * 3, 16)), dim3(256), 0, st, sc.wpart, grid1, C1, 4, 3, grad_w1, C + 3, 0);      // xyz columns
   if (C && ordered && N > 0) {                                                                                                    // the scatter, in key order
     const SvInvLists L = sv_inv_lists_view(reinterpret_cast<char*>(scratch) + sa_lists_offset(C, C1, C2), R, N);
-    if (int rc = sv_inv_lists_build(idx, row_start, M, nsample, N, true, L, st)) return rc;
+    if (int rc = sv_inv_lists_build(R, N, SvBallRow{idx, row_start, nsample, true}, L, st)) return rc;
     a.S = scatter;
     hipLaunchKernelGGL(k_sa_scatter_gather, dim3(sv_grid_1d(sv_div_up(N, 64 / C1) * 64, 256, 256 * 16)), dim3(256), 0, st, a, L);
   }

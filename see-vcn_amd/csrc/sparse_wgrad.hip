@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "sparse_conv.h"
+#include "wave.h"
 
 // ------------------------------------------------------------------------------------------------
 // Weight gradient: dW[k][c][n] = sum_o X[nbr[k][o]][c] * dY[o][n]   (reduction over rows)
@@ -730,23 +731,6 @@ __global__ __launch_bounds__(256) void k_wgrad_plan_count(WgradPlanBatch b) {
   }
 }
 
-// 1024 threads: inclusive scan of one value per thread -- shuffles inside a wave, the 16 wave totals through LDS (two barriers)
-__device__ __forceinline__ int wgp_block_scan_inclusive(int* s_wave, int v, int tid) {
-  const int lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  __syncthreads();                                       // s_wave may still be read from the previous scan
-  if (lane == 63) s_wave[wid] = v;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) base += w < wid ? s_wave[w] : 0;
-  return v + base;
-}
-
 __global__ __launch_bounds__(1024) void k_wgrad_plan_cuts(WgradPlanBatch b) {
   __shared__ int s_wave[16];
   __shared__ int s_run[1025];                            // pairs in front of every thread's run of units (+ the total): the coarse level of the cut search
@@ -780,7 +764,9 @@ __global__ __launch_bounds__(1024) void k_wgrad_plan_cuts(WgradPlanBatch b) {
     }
     for (; u < b1; ++u) sum += pre[u];
   }
-  const int incl = wgp_block_scan_inclusive(s_wave, sum, tid);
+  int all;
+  __syncthreads();
+  const int incl = sv_block_excl_scan<1024>(sum, &all, s_wave) + sum;
   s_run[tid] = incl - sum;
   if (tid == 1023) s_run[1024] = incl;
   if (in_regs) {
@@ -867,7 +853,9 @@ __global__ __launch_bounds__(1024) void k_wgrad_plan_cuts(WgradPlanBatch b) {
   }
   int carry = 0;
   for (int q = 0; q < 2; ++q) {
-    const int inc = wgp_block_scan_inclusive(s_wave, seg[q], tid);
+    int all;
+    __syncthreads();                                     // s_wave may still be read from the previous scan
+    const int inc = sv_block_excl_scan<1024>(seg[q], &all, s_wave) + seg[q];
     first[q] = carry + inc - seg[q];
     __syncthreads();
     if (tid == 1023) s_run[0] = inc;

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wave.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -564,8 +565,7 @@ extern "C" int sv_pointwise_conv3_gather(const float* xyz, const int64_t* sel, i
 constexpr int ST = 32;
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  v = sv_wave_reduce_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();

@@ -13,6 +13,7 @@
 // atomic sum as before, so it propagates or is summed in arrival order.  The finalize pass divides (fixed sum * 2^-32 +
 // fp32 sum) by the count in fp64 and rounds once to fp32.  More features: fp32 atomic sums only.
 #include "common.h"
+#include "wave.h"
 
 struct VoxGeom {
   float lo[3];
@@ -311,27 +312,6 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_insert(HardVoxArgs a) {
   a.pt_next[p0 + i] = next;
 }
 
-__device__ __forceinline__ int hv_block_excl_scan(int v, int* total, int* wsum /* [HV_THREADS / 64] */) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wid] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < HV_THREADS / 64; ++i) {
-    const int s = wsum[i];
-    if (i < wid) base += s;
-    tot += s;
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
 __device__ __forceinline__ bool hv_is_first(const HardVoxArgs& a, int b, int p0, int n, int i) {
   if (i >= n) return false;
   const int s = a.pt_slot[p0 + i];
@@ -343,7 +323,7 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_count(HardVoxArgs a) {
   const int b = blockIdx.y, i = blockIdx.x * HV_THREADS + threadIdx.x;
   const int p0 = a.scene_start[b], n = a.scene_cnt[b];
   int total;
-  hv_block_excl_scan(hv_is_first(a, b, p0, n, i) ? 1 : 0, &total, wsum);
+  sv_block_excl_scan<HV_THREADS>(hv_is_first(a, b, p0, n, i) ? 1 : 0, &total, wsum);
   if (threadIdx.x == 0) a.block_off[(int64_t)b * a.blocks_per_scene + blockIdx.x] = total;
 }
 
@@ -358,12 +338,7 @@ __global__ __launch_bounds__(1024) void k_hv_offsets(HardVoxArgs a) {
   for (int base = 0; base < a.blocks_per_scene; base += 1024) {
     const int j = base + tid;
     const int v = j < a.blocks_per_scene ? off[j] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
+    const int incl = sv_wave_incl_scan(v);
     if (lane == 63) wsum[wid] = incl;
     __syncthreads();
     int pre = carry, tot = 0;
@@ -386,7 +361,7 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_fill(HardVoxArgs a) {
   const int p0 = a.scene_start[b], n = a.scene_cnt[b];
   const bool first = hv_is_first(a, b, p0, n, i);
   int total;
-  const int vid = a.block_off[(int64_t)b * a.blocks_per_scene + blockIdx.x] + hv_block_excl_scan(first ? 1 : 0, &total, wsum);
+  const int vid = a.block_off[(int64_t)b * a.blocks_per_scene + blockIdx.x] + sv_block_excl_scan<HV_THREADS>(first ? 1 : 0, &total, wsum);
   if (!first || vid >= a.max_voxels) return;
   const int slot = a.pt_slot[p0 + i];
   const int K = a.max_points;

@@ -121,14 +121,12 @@ def _gp_case(C):
     return idx, row_start, grad_out
 
 
-@functools.lru_cache(maxsize=None)
-def _gp_ref(C):
+def _gp_loop(idx, row_start, grad_out, N):
     """-> fp32 result of the stated order (N, C), float64 sum of |terms|, term counts (N,)"""
-    idx, row_start, grad_out = _gp_case(C)
-    N = sum(GP_N)
+    nsample, C = idx.shape[1], grad_out.shape[1]
     out, mag, cnt = np.zeros((N, C), F), np.zeros((N, C)), np.zeros(N)
     for key in range(idx.size):                                                  # ascending key = m * nsample + s
-        m, s = divmod(key, GP_NS)
+        m, s = divmod(key, nsample)
         if idx[m, s] < 0:
             continue                                                             # the empty-ball mark names nothing
         n = row_start[m] + idx[m, s]
@@ -136,6 +134,11 @@ def _gp_ref(C):
         mag[n] += np.abs(grad_out[m, :, s].astype(np.float64))
         cnt[n] += 1
     return out, mag, cnt
+
+
+@functools.lru_cache(maxsize=None)
+def _gp_ref(C):
+    return _gp_loop(*_gp_case(C), sum(GP_N))
 
 
 def _gp_without_mark(C):
@@ -148,6 +151,21 @@ def _gp_without_mark(C):
 
 
 GP_CHANNELS = [1, 3, 64, 130]
+
+# lists at the 64-lane edge of the sort: 4 support rows named by exactly 65, 64, 63 and 0 of the 12 * 16 keys, in no particular key order
+EDGE_N, EDGE_M, EDGE_COUNTS, EDGE_CHANNELS = 4, 12, (65, 64, 63, 0), [3, 130]
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_case(C):
+    rng = np.random.default_rng(200 + C)
+    idx = rng.permutation(np.repeat(np.arange(EDGE_N, dtype=np.int32), EDGE_COUNTS)).reshape(EDGE_M, GP_NS)
+    return idx, np.zeros(EDGE_M, np.int32), rng.normal(0, 1, (EDGE_M, C, GP_NS)).astype(F)
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_ref(C):
+    return _gp_loop(*_edge_case(C), EDGE_N)
 
 
 # ------------------------------------------------------------------------------------------------ SA-MSG training backward
@@ -306,6 +324,17 @@ def test_group_points_stated_order_agrees_with_the_float64_oracle(C):
     assert np.all(_bits(ref)[cnt == 0] == 0)
 
 
+@pytest.mark.parametrize("C", EDGE_CHANNELS)
+def test_group_points_edge_lists_agree_with_the_float64_oracle(C):
+    from oracle import pointnet2 as op
+    ref, mag, cnt = _edge_ref(C)
+    idx, _, grad_out = _edge_case(C)
+    want = op.group_points_grad(grad_out, idx, np.array([EDGE_M]), np.array([EDGE_N]), EDGE_N)
+    _assert_bound(ref, want, (cnt[:, None] + 3) * U * mag, f"group_points_grad edge lists C={C}: fp32 loop vs oracle")
+    assert tuple(cnt) == EDGE_COUNTS
+    assert np.all(_bits(ref)[3] == 0)
+
+
 def test_fma_emulation_is_correctly_rounded():
     """_fma32 against exact rational arithmetic, including sums that sit next to an fp32 rounding tie"""
     from fractions import Fraction
@@ -403,11 +432,11 @@ def test_hip_chamfer_ordered_equals_the_stated_order_bit_for_bit(cuda, hip_lib, 
         _assert_bound(atom, exact, bound, f"chamfer {name} {side}: atomic")
 
 
-def _gp_gpu(cuda, lib, C, ordered):
+def _gp_gpu(cuda, lib, C, ordered, case=None, N=sum(GP_N)):
     import torch
     import seevcn_amd._lib as L
-    idx, row_start, grad_out = (torch.from_numpy(a).to(cuda) for a in (_gp_case(C) if ordered else _gp_without_mark(C)))
-    M, N = sum(GP_M), sum(GP_N)
+    idx, row_start, grad_out = (torch.from_numpy(a).to(cuda) for a in case or (_gp_case(C) if ordered else _gp_without_mark(C)))
+    M = len(idx)
     out = torch.full((N, C), float("nan"), dtype=torch.float32, device=cuda)
     p = L.ptr
     if ordered:
@@ -434,6 +463,18 @@ def test_hip_group_points_grad_ordered_equals_the_stated_order_bit_for_bit(cuda,
     bound = (cnt[:, None] + 3) * U * mag
     _assert_bound(got, exact, bound, f"group_points_grad C={C}: ordered")
     _assert_bound(atom, exact, bound, f"group_points_grad C={C}: atomic")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", EDGE_CHANNELS)
+def test_hip_group_points_grad_ordered_lists_at_the_wave_edge(cuda, hip_lib, C):
+    """Rows named by exactly 65, 64 and 63 keys (the sort's second trip of a wave, a full wave, one lane short) and a row named by none;
+    C = 130 crosses the 128-channel trip.  Bit for bit the fp32 ascending-key loop, twice; the unnamed row is +0.0f."""
+    ref, _, cnt = _edge_ref(C)
+    got, again = (_gp_gpu(cuda, hip_lib, C, True, _edge_case(C), EDGE_N) for _ in range(2))
+    _assert_bits(got, ref, f"group_points_grad edge lists C={C}")
+    _assert_bits(again, got, f"group_points_grad edge lists C={C}, second call")
+    assert tuple(cnt) == EDGE_COUNTS and np.all(_bits(got)[3] == 0)
 
 
 @pytest.mark.gpu
