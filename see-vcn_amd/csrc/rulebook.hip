@@ -145,8 +145,10 @@ static int fill_geom(ConvGeom& g, int batch, const int32_t* in_shape, const int3
     g.pad[d] = subm ? (ksize[d] / 2) * (dil ? dil[d] : 1) : pad[d];
     g.dil[d] = dil ? dil[d] : 1;
     SV_CHECK_ARG(g.in_shape[d] > 0 && g.ksize[d] > 0 && g.stride[d] > 0 && g.pad[d] >= 0 && g.dil[d] > 0, "rulebook: bad conv geometry");
-    // floor((D + 2p - dil*(K-1) - 1)/s) + 1
-    g.out_shape[d] = subm ? g.in_shape[d] : (g.in_shape[d] + 2 * g.pad[d] - g.dil[d] * (g.ksize[d] - 1) - 1) / g.stride[d] + 1;
+    // floor((D + 2p - dil*(K-1) - 1)/s) + 1.  A kernel wider than the padded input makes the numerator negative: floor gives no output cell (spconv
+    // refuses such a layer), where C's division towards zero would invent one whose window hangs over the grid.
+    const int span = g.in_shape[d] + 2 * g.pad[d] - g.dil[d] * (g.ksize[d] - 1) - 1;
+    g.out_shape[d] = subm ? g.in_shape[d] : (span < 0 ? 0 : span / g.stride[d] + 1);
     SV_CHECK_ARG(g.out_shape[d] > 0, "rulebook: empty output shape");
     g.K *= g.ksize[d];
   }

@@ -1180,7 +1180,7 @@ def test_hip_network_index_equals_the_layer_by_layer_build(cuda, hip_lib, lazy_c
     from seevcn_amd import _lib
     from seevcn_amd.spconv import functional as Fsp
     rng = np.random.default_rng(11)
-    batch, shape = 3, (21, 96, 80)
+    batch, shape = 3, (25, 96, 80)           # z 25 -> 13 -> 7 -> 3 -> 1: the least depth at which the last level's (3, 1, 1) kernel still fits its input
     coords = torch.from_numpy(_rand_coords(rng, 20000, batch, shape)).to(cuda)
     n0 = coords.shape[0]
     S = Fsp.ConvSpec
