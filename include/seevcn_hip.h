@@ -523,6 +523,32 @@ size_t sv_group_points_grad_stack_ordered_scratch_bytes(int M, int N, int nsampl
 int sv_group_points_grad_stack_ordered(int M, int C, int N, int nsample, const float* grad_out, const int32_t* idx, const int32_t* row_start,
                                        void* scratch, float* grad_features, void* stream);
 
+/* ---- Voxel R-CNN's voxel RoI pooling (csrc/voxel_pool.hip).
+ * generate_voxel2pinds / scatter_point_inds (detector3d/pcdet/utils/common_utils.py:235-252): volume (B, Z, Y, X) int32 = -1 everywhere and r at
+ * [b, z, y, x] of row r of coords (N, 4), offsets in 64 bits (the volume may hold 2^31 cells or more); a row outside the volume writes nothing.
+ * fill = 1 sets the whole volume to -1 first.  clear = 1 writes -1 where it would write r: with fill = 0 the same N-row scatter returns a
+ * volume that was all -1 on entry to all -1 (a persistent volume costs two N-row scatters a call and no pass over its cells). */
+int sv_voxel2pinds(const int32_t* coords, int64_t N, int B, int Z, int Y, int X, int fill, int clear, int32_t* volume, void* stream);
+/* voxel_query_wrapper (pointnet2_stack/src/voxel_query.cpp, kernel voxel_query_gpu.cu:10-89), element for element: for query m with cell
+ * new_coords[m] = [b, z, y, x] the window z - z_range .. z + z_range (outermost), y, x (innermost) of point_indices (B, R1, R2, R3) is walked,
+ * cells outside the volume and cells holding -1 are passed over, a neighbour row j is kept unless
+ *   (xyz[j].x - new_xyz[m].x)^2 + (.y)^2 + (.z)^2 > radius * radius     (each product and sum rounded to fp32, this operand order)
+ * and the first nsample kept rows fill idx[m][0..]; the first kept row also fills every slot behind the last kept one; a query that keeps
+ * nothing gets idx[m][0] = -1 and its other slots stay as the caller left them.  One wave per query, 64 cells of the clipped window per pass.
+ * Beyond the reference: a query whose b is outside [0, B) keeps nothing, and a cell value >= n_points (the rows of xyz) is passed over.
+ * Window extents up to 1024 each. */
+int sv_voxel_query_stack(int M, int B, int R1, int R2, int R3, int64_t n_points, int nsample, float radius, int z_range, int y_range, int x_range,
+                         const float* new_xyz, const float* xyz, const int32_t* new_coords, const int32_t* point_indices, int32_t* idx,
+                         void* stream);
+/* The eval-mode tail of one scale of NeighborVoxelSAModuleMSG.forward (pointnet2_stack/voxel_pool_modules.py:96-120, max_pool) without the
+ * grouped (M, C1, nsample) and (M, 3, nsample) tensors:
+ *   out[m][c] = max_s ReLU(f_in[idx[m][s]][c] + wp[c] . (xyz[idx[m][s]] - new_xyz[m]) + bp[c])
+ * f_in (N, C1) = mlps_in applied to the support voxels, wp (C1, 3) / bp (C1) = mlps_pos with its eval-mode BatchNorm2d folded in, idx (M, nsample)
+ * GLOBAL rows as sv_voxel_query_stack leaves them; a query with idx[m][0] < 0 gives ReLU(bp[c]) (the reference zeroes both grouped tensors of an
+ * empty query).  C1 in {16, 32, 48, 64}, nsample <= 32; f_in, bp, out 16-byte aligned. */
+int sv_voxel_pool_max(const float* f_in, const float* xyz, const float* new_xyz, const int32_t* idx, const float* wp, const float* bp, int64_t M,
+                      int64_t N, int C1, int nsample, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Rotated-box geometry (detector3d/pcdet/ops/iou3d_nms/src/iou3d_nms_api.cpp:12-17,
  * detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:172-177). Boxes are (N,7) fp32 [x,y,z,dx,dy,dz,heading].
@@ -915,7 +941,8 @@ int sv_isolate_largest_cluster(const float* points, int row_stride, const int32_
 /* ---- roiaware_pool3d_cuda.points_in_boxes_cpu (detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-165; a host loop in the
  * reference): out (N,M) int32 0/1, box test with MARGIN 1e-2 (points_in_boxes_gpu uses 1e-5 and returns one box per point).
  * The RoI-aware pooling entries of that module (forward / backward: PartA2 only) and the PV-RCNN++ entries of pointnet2_stack_cuda
- * (voxel_query, vector_pool, local 3-NN) are not on the path of any BASELINE config and are not part of this library. */
+ * (vector_pool, local 3-NN) are not on the path of any BASELINE config and are not part of this library; voxel_query is
+ * sv_voxel_query_stack above. */
 int sv_points_in_boxes_matrix(const float* boxes, const float* pts, int num_boxes, int num_points, int32_t* out, void* stream);
 
 #ifdef __cplusplus

@@ -135,7 +135,10 @@ SIGNATURES = {
     "sv_group_points_grad_stack": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_group_points_grad_stack_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "sv_group_points_grad_stack_ordered": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "sv_boxes_overlap_bev": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "sv_voxel2pinds": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "sv_voxel_query_stack": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_voxel_pool_max": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p]),
+    "sv_boxes_overlap_bev":(c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "sv_boxes_iou3d_batch": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_nms_scratch_bytes": (c_sz, [c_i]),
     "sv_nms": (c_i, [c_p, c_i, c_f, c_i, c_p, c_p, c_p, c_p]),

@@ -34,6 +34,15 @@ __device__ __forceinline__ T sv_block_excl_scan(T v, T* total, T* wave_sums) {
   return base + incl - v;
 }
 
+// Exclusive scan of one flag per lane through a ballot: the number of set flags in the lanes below this one; *total = set flags in the wave (the
+// same in every lane).  sv_wave_ballot_first: the lowest lane whose flag is set (-1: none).  Every lane of the wave must be active.
+__device__ __forceinline__ int sv_wave_ballot_rank(bool flag, int* total) {
+  const unsigned long long m = __ballot(flag);
+  *total = __popcll(m);
+  return __popcll(m & ((1ull << (threadIdx.x & (SV_WAVE - 1))) - 1ull));
+}
+__device__ __forceinline__ int sv_wave_ballot_first(bool flag) { return __ffsll((long long)__ballot(flag)) - 1; }
+
 // One xor butterfly over the wave's 64 lanes, d = 32 -> 1; every lane gets the result.  A 64-bit value travels as two 32-bit halves.
 __device__ __forceinline__ unsigned long long sv_shfl_xor(unsigned long long v, int d) {
   const unsigned lo = __shfl_xor((unsigned)v, d, SV_WAVE), hi = __shfl_xor((unsigned)(v >> 32), d, SV_WAVE);

@@ -103,6 +103,37 @@ def pvrcnn_model_cfg(**kw):
                 MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=SECOND_BACKBONE_2D, DENSE_HEAD=SECOND_DENSE_HEAD,
                 PFE=pfe, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)
 
+# detector3d/tools/cfgs/kitti_models/voxel_rcnn_car.yaml:32-180 (values as data)
+VOXELRCNN_CLASS_NAMES = ['Car']
+VOXELRCNN_BACKBONE_2D = dict(NAME='BaseBEVBackbone', LAYER_NUMS=[5, 5], LAYER_STRIDES=[1, 2], NUM_FILTERS=[64, 128], UPSAMPLE_STRIDES=[1, 2],
+                             NUM_UPSAMPLE_FILTERS=[128, 128])
+
+
+def voxelrcnn_cfg(features_source=('x_conv2', 'x_conv3', 'x_conv4'), roi_per_image=128, nms_post_train=512, nms_pre_train=9000, dp_ratio=0.3):
+    """ROI_HEAD section of voxel_rcnn_car.yaml:92-166."""
+    radius = dict(x_conv2=0.4, x_conv3=0.8, x_conv4=1.6)
+    layers = {s: dict(MLPS=[[32, 32]], QUERY_RANGES=[[4, 4, 4]], POOL_RADIUS=[radius[s]], NSAMPLE=[16], POOL_METHOD='max_pool') for s in features_source}
+    return dict(
+        NAME='VoxelRCNNHead', CLASS_AGNOSTIC=True, SHARED_FC=[256, 256], CLS_FC=[256, 256], REG_FC=[256, 256], DP_RATIO=dp_ratio,
+        NMS_CONFIG=dict(TRAIN=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, NMS_PRE_MAXSIZE=nms_pre_train, NMS_POST_MAXSIZE=nms_post_train, NMS_THRESH=0.8),
+                        TEST=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, USE_FAST_NMS=False, SCORE_THRESH=0.0, NMS_PRE_MAXSIZE=2048,
+                                  NMS_POST_MAXSIZE=100, NMS_THRESH=0.7)),
+        ROI_GRID_POOL=dict(FEATURES_SOURCE=list(features_source), PRE_MLP=True, GRID_SIZE=6, POOL_LAYERS=layers),
+        TARGET_CONFIG=dict(BOX_CODER='ResidualCoder', ROI_PER_IMAGE=roi_per_image, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE='roi_iou',
+                           CLS_FG_THRESH=0.75, CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55),
+        LOSS_CONFIG=dict(CLS_LOSS='BinaryCrossEntropy', REG_LOSS='smooth-l1', CORNER_LOSS_REGULARIZATION=True, GRID_3D_IOU_LOSS=False,
+                         LOSS_WEIGHTS=dict(rcnn_cls_weight=1.0, rcnn_reg_weight=1.0, rcnn_corner_weight=1.0, rcnn_iou3d_weight=1.0, code_weights=[1.0] * 7)))
+
+
+def voxelrcnn_model_cfg(dynamic_vfe=False, **kw):
+    """MODEL section of voxel_rcnn_car.yaml (one class: build with num_class=1 and VOXELRCNN_CLASS_NAMES); dynamic_vfe swaps MeanVFE for DynMeanVFE
+    as waymo_models/voxel_rcnn_with_centerhead_dyn_voxel.yaml does."""
+    head = dict(SECOND_DENSE_HEAD, ANCHOR_GENERATOR_CONFIG=[_anchor('Car', [3.9, 1.6, 1.56], -1.78, 0.6, 0.45)])
+    pp = dict(SECOND_POST_PROCESSING, SCORE_THRESH=0.3, NMS_CONFIG=dict(SECOND_POST_PROCESSING['NMS_CONFIG'], NMS_THRESH=0.1))
+    return dict(NAME='VoxelRCNN', VFE=dict(NAME='DynMeanVFE' if dynamic_vfe else 'MeanVFE'), BACKBONE_3D=dict(NAME='VoxelBackBone8x'),
+                MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=VOXELRCNN_BACKBONE_2D, DENSE_HEAD=head,
+                ROI_HEAD=voxelrcnn_cfg(**kw), POST_PROCESSING=pp)
+
 # detector3d/tools/cfgs/nuscenes_models/cbgs_voxel0075_res3d_centerpoint.yaml:1-140 (values as data)
 NUSC_CLASS_NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle', 'pedestrian', 'traffic_cone']
 CENTER_HEAD = dict(

@@ -4,6 +4,7 @@ from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
 from .second_net import SECONDNet
 from .second_net_iou import SECONDNetIoU
+from .voxel_rcnn import VoxelRCNN
 
 # same registry shape as the reference (detectors/__init__.py:13-26)
 __all__ = {
@@ -13,6 +14,7 @@ __all__ = {
     'PointPillar': PointPillar,
     'PVRCNN': PVRCNN,
     'CenterPoint': CenterPoint,
+    'VoxelRCNN': VoxelRCNN,
 }
 
 

@@ -1,0 +1,12 @@
+from .detector3d_template import Detector3DTemplate
+
+
+class VoxelRCNN(Detector3DTemplate):
+    """VFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle / CenterHead -> VoxelRCNNHead, which pools the sparse
+    taps x_conv2..x_conv4 directly: no keypoints, no point head; training loss = rpn + rcnn (reference detectors/voxel_rcnn.py:4-37).  Module
+    loop, train / eval branching and the loss sum live in Detector3DTemplate."""
+    LOSS_HEADS = ('dense_head', 'roi_head')
+
+    def __init__(self, model_cfg, num_class, dataset):
+        super().__init__(model_cfg=model_cfg, num_class=num_class, dataset=dataset)
+        self.module_list = self.build_networks()

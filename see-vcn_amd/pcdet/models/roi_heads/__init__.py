@@ -1,9 +1,11 @@
 from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
 from .second_head import SECONDHead
+from .voxelrcnn_head import VoxelRCNNHead
 
 __all__ = {
     'RoIHeadTemplate': RoIHeadTemplate,
     'PVRCNNHead': PVRCNNHead,
     'SECONDHead': SECONDHead,
+    'VoxelRCNNHead': VoxelRCNNHead,
 }

@@ -4,10 +4,10 @@ import torch.nn as nn
 from ...ops.pointnet2.pointnet2_stack import pointnet2_modules as pointnet2_stack_modules
 from ...utils import common_utils
 from ...utils.common_utils import cfg_get
-from .roi_head_template import RoIHeadTemplate
+from .roi_head_template import RoIGridPointsMixin, RoIHeadTemplate
 
 
-class PVRCNNHead(RoIHeadTemplate):
+class PVRCNNHead(RoIGridPointsMixin, RoIHeadTemplate):
     """RoI-grid pooling head of PV-RCNN (reference roi_heads/pvrcnn_head.py:8-175): 6^3 grid points per RoI, set abstraction
     of the keypoint features around them (HIP ball query / grouping), shared FC 27648->256->256, cls / reg branches."""
 
@@ -37,22 +37,6 @@ class PVRCNNHead(RoIHeadTemplate):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
         nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
-
-    @staticmethod
-    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
-        # rois.new_ones((g, g, g)).nonzero() of the reference = the g^3 index triples in C order: a constant, made once per device
-        import numpy as np
-        dense_idx = common_utils.const_tensor(np.stack(np.meshgrid(*([np.arange(grid_size)] * 3), indexing='ij'), axis=-1).reshape(-1, 3), rois.device,
-                                              rois.dtype).repeat(batch_size_rcnn, 1, 1)                               # (B, g^3, 3)
-        size = rois.view(batch_size_rcnn, -1)[:, 3:6]
-        return (dense_idx + 0.5) / grid_size * size.unsqueeze(1) - (size.unsqueeze(1) / 2)
-
-    def get_global_grid_points_of_roi(self, rois, grid_size):
-        rois = rois.view(-1, rois.shape[-1])
-        local = self.get_dense_grid_points(rois, rois.shape[0], grid_size)
-        glob = common_utils.rotate_points_along_z(local.clone(), rois[:, 6]).squeeze(dim=1)
-        glob = glob + rois[:, 0:3].clone().unsqueeze(dim=1)
-        return glob, local
 
     def roi_grid_pool(self, batch_dict):
         batch_size, rois = batch_dict['batch_size'], batch_dict['rois']

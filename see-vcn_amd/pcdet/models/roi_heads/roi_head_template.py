@@ -173,3 +173,23 @@ class RoIHeadTemplate(nn.Module):
         boxes = common_utils.rotate_points_along_z(boxes.unsqueeze(1), roi_ry).squeeze(1)
         boxes[:, 0:3] += roi_xyz
         return batch_cls_preds, boxes.view(batch_size, -1, code)
+
+
+class RoIGridPointsMixin:
+    """The g^3 grid points of every RoI, in its own frame and in the scene's (reference roi_heads/pvrcnn_head.py:136-163 and
+    voxelrcnn_head.py:194-215, the same two helpers): shared by PVRCNNHead and VoxelRCNNHead."""
+
+    @staticmethod
+    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
+        # rois.new_ones((g, g, g)).nonzero() of the reference = the g^3 index triples in C order: a constant, made once per device
+        dense_idx = common_utils.const_tensor(np.stack(np.meshgrid(*([np.arange(grid_size)] * 3), indexing='ij'), axis=-1).reshape(-1, 3), rois.device,
+                                              rois.dtype).repeat(batch_size_rcnn, 1, 1)                               # (B, g^3, 3)
+        size = rois.view(batch_size_rcnn, -1)[:, 3:6]
+        return (dense_idx + 0.5) / grid_size * size.unsqueeze(1) - (size.unsqueeze(1) / 2)
+
+    def get_global_grid_points_of_roi(self, rois, grid_size):
+        rois = rois.view(-1, rois.shape[-1])
+        local = self.get_dense_grid_points(rois, rois.shape[0], grid_size)
+        glob = common_utils.rotate_points_along_z(local.clone(), rois[:, 6]).squeeze(dim=1)
+        glob = glob + rois[:, 0:3].clone().unsqueeze(dim=1)
+        return glob, local

@@ -203,6 +203,20 @@ def stack_farthest_point_sampling_async(points, xyz_batch_cnt, npoint, max_n):
     return FpsHandle(idx, err, stream, lambda: launch(1))
 
 
+def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, point_indices, idx):
+    """src/voxel_query.cpp: new_coords (M, 4) int32 [b, z, y, x], point_indices (B, R1, R2, R3) int32, idx (M, nsample) int32 zero-filled by the caller."""
+    lib = _lib.load()
+    _lib.require_cuda(new_xyz, xyz, new_coords, point_indices, idx)
+    assert new_coords.dtype == torch.int32 and point_indices.dtype == torch.int32 and idx.dtype == torch.int32
+    cells = int(R1) * int(R2) * int(R3)
+    B = point_indices.numel() // cells if cells else 0
+    rc = lib.sv_voxel_query_stack(int(M), B, int(R1), int(R2), int(R3), int(xyz.shape[0]), int(nsample), float(radius), int(z_range), int(y_range),
+                                  int(x_range), _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(new_coords), _lib.ptr(point_indices), _lib.ptr(idx),
+                                  _lib.stream())
+    _lib.check(rc, "sv_voxel_query_stack")
+    return 1
+
+
 def _outside_hot_path(name):
     def stub(*args, **kwargs):
         raise NotImplementedError(f"pointnet2_stack_cuda.{name} is outside the SEE-VCN hot path (SURVEY.md 2: PV-RCNN++ / PartA2 / PointRCNN-style "
@@ -215,7 +229,6 @@ def _outside_hot_path(name):
 three_nn_wrapper = _outside_hot_path("three_nn_wrapper")
 three_interpolate_wrapper = _outside_hot_path("three_interpolate_wrapper")
 three_interpolate_grad_wrapper = _outside_hot_path("three_interpolate_grad_wrapper")
-voxel_query_wrapper = _outside_hot_path("voxel_query_wrapper")
 vector_pool_wrapper = _outside_hot_path("vector_pool_wrapper")
 vector_pool_grad_wrapper = _outside_hot_path("vector_pool_grad_wrapper")
 query_stacked_local_neighbor_idxs_wrapper_stack = _outside_hot_path("query_stacked_local_neighbor_idxs_wrapper_stack")

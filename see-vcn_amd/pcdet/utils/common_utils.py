@@ -67,6 +67,37 @@ def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_ra
     return (centers + 0.5) * vs + pc
 
 
+def scatter_voxel_rows(indices, volume, fill=True, clear=False):
+    """volume (B, Z, Y, X) int32 <- row r at [b, z, y, x] of row r of indices (N, 4) (sv_voxel2pinds: 64-bit offsets).  fill: -1 everywhere first;
+    clear: write -1 where the rows are, which returns a volume that was all -1 before the scatter to all -1."""
+    from ... import _lib
+    lib = _lib.load()
+    _lib.require_cuda(indices, volume)
+    assert volume.dtype == torch.int32 and volume.dim() == 4
+    ind = indices if indices.dtype == torch.int32 else indices.int()
+    B, Z, Y, X = volume.shape
+    _lib.check(lib.sv_voxel2pinds(_lib.ptr(ind.contiguous()), int(ind.shape[0]), int(B), int(Z), int(Y), int(X), int(fill), int(clear), _lib.ptr(volume),
+                                  _lib.stream()), "sv_voxel2pinds")
+    return volume
+
+
+def scatter_point_inds(indices, point_inds, shape):
+    """-1 everywhere, point_inds[r] at indices[r] (common_utils.py:235-241); any number of index columns, torch index ops."""
+    ret = torch.full(tuple(int(s) for s in shape), -1, dtype=point_inds.dtype, device=point_inds.device)
+    flat = indices.view(-1, indices.shape[-1]).long()
+    ret[tuple(flat[:, i] for i in range(flat.shape[1]))] = point_inds
+    return ret
+
+
+def generate_voxel2pinds(sparse_tensor):
+    """(batch_size, Z, Y, X) int32: the row of sparse_tensor.indices that sits in each cell, -1 in an empty one (common_utils.py:244-252).  A
+    tensor of its own, one fill and one scatter launch."""
+    indices = sparse_tensor.indices
+    shape = [int(sparse_tensor.batch_size)] + [int(s) for s in sparse_tensor.spatial_shape]
+    volume = torch.empty(shape, dtype=torch.int32, device=indices.device)
+    return scatter_voxel_rows(indices, volume)
+
+
 def init_dist_pytorch(tcp_port, local_rank, backend='nccl'):
     """One process per GPU under `python -m torch.distributed.launch` / torchrun (common_utils.py:164-182, called by tools/train.py:70-76):
     binds the process to its device and joins the process group described by RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT.  backend 'nccl'
