@@ -549,6 +549,37 @@ int sv_voxel_query_stack(int M, int B, int R1, int R2, int R3, int64_t n_points,
 int sv_voxel_pool_max(const float* f_in, const float* xyz, const float* new_xyz, const int32_t* idx, const float* wp, const float* bp, int64_t M,
                       int64_t N, int C1, int nsample, float* out, void* stream);
 
+/* ---- Part-A2's RoI-aware point feature pooling (csrc/roiaware_pool.hip).  Every entry refuses null and host pointers, out sizes above 255
+ * (the reference packs a cell into 3 x 8 bits and silently corrupts beyond), more than 4096 cells per box and max_pts_each_voxel < 2;
+ * n_boxes == 0 and n_pts == 0 return cleanly.
+ * generate_pts_mask_for_box3d + collect_inside_pts_for_box3d (detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu:39-108) without
+ * the (boxes x points) mask and without one thread walking every point of the scene: pts_idx_of_voxels (n_boxes, out_x, out_y, out_z,
+ * max_pts_each_voxel) int32, slot 0 of a cell = its count (at most max_pts_each_voxel - 1), slots 1..count = the rows of pts (n_pts, 3) inside
+ * box rois[box] (7 floats) that fall into the cell, in ASCENDING row order, the later ones dropped.  The in-box test is the reference's (:16-36,
+ * the one sv_points_in_boxes uses), the cell is int((local + d / 2) / (d / out)) per axis in fp32, clamped to the grid.  box_pt_range (n_boxes, 2)
+ * int32 device, or NULL: box b looks at rows [lo, hi) only (clipped to [0, n_pts)) -- the rows of its scene, so that the boxes of every scene of
+ * a batch are assigned in one launch; the stored rows are absolute.  Every count is written, so the tensor needs no zero-fill; slots behind a
+ * count are left as they were and nothing reads them. */
+int sv_roiaware_assign(const float* rois, int n_boxes, const float* pts, int n_pts, const int32_t* box_pt_range, int out_x, int out_y, int out_z,
+                       int max_pts_each_voxel, int32_t* pts_idx_of_voxels, void* stream);
+/* roiaware_maxpool3d / roiaware_avgpool3d (roiaware_pool3d_kernel.cu:111-190) over lists that sv_roiaware_assign left; cells = out_x * out_y *
+ * out_z.  pool_method 0 = max: pooled (n_boxes, cells, C) = the largest feature of the listed rows, strict > in list order (the first row of
+ * the largest value wins), argmax (n_boxes, cells, C) int32 = that row; an empty cell is 0 and -1.  pool_method 1 = avg: the fp32 sum in list
+ * order over the count, an empty cell is 0; argmax may be NULL.  Every element of pooled (and argmax) is written. */
+int sv_roiaware_pool(const float* pts_feature, int C, const int32_t* pts_idx_of_voxels, int n_boxes, int cells, int max_pts_each_voxel,
+                     int pool_method, float* pooled, int32_t* argmax, void* stream);
+/* roiaware_maxpool3d_backward / roiaware_avgpool3d_backward (roiaware_pool3d_kernel.cu:236-286): grad_in (n_pts, C) is zero-filled, then
+ * max: grad_in[argmax] += grad_out; avg: grad_in[p] += grad_out / max(count, 1) for every listed row p -- with fp32 atomics like the reference. */
+int sv_roiaware_pool_backward(const int32_t* pts_idx_of_voxels, const int32_t* argmax, const float* grad_out, int n_boxes, int cells, int C,
+                              int max_pts_each_voxel, int pool_method, int n_pts, float* grad_in, void* stream);
+/* The same gradient with a fixed summation order (opt-in): no float atomics, no zero-fill, every element of grad_in written once as
+ * +0.0f + its contributions in ascending (box, cell) order, every sum rounded to fp32.  scratch: sv_roiaware_pool_backward_ordered_scratch_bytes
+ * bytes (uninitialised) -- the inverse lists over the key space n_boxes * cells * C (max) or n_boxes * cells * max_pts_each_voxel (avg), which
+ * must stay below 2^31 (else 0 bytes and an error, never the atomic route). */
+size_t sv_roiaware_pool_backward_ordered_scratch_bytes(int n_boxes, int cells, int C, int max_pts_each_voxel, int pool_method, int n_pts);
+int sv_roiaware_pool_backward_ordered(const int32_t* pts_idx_of_voxels, const int32_t* argmax, const float* grad_out, int n_boxes, int cells, int C,
+                                      int max_pts_each_voxel, int pool_method, int n_pts, void* scratch, float* grad_in, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Rotated-box geometry (detector3d/pcdet/ops/iou3d_nms/src/iou3d_nms_api.cpp:12-17,
  * detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:172-177). Boxes are (N,7) fp32 [x,y,z,dx,dy,dz,heading].

@@ -138,6 +138,11 @@ SIGNATURES = {
     "sv_voxel2pinds": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "sv_voxel_query_stack": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sv_voxel_pool_max": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p]),
+    "sv_roiaware_assign": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "sv_roiaware_pool": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "sv_roiaware_pool_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "sv_roiaware_pool_backward_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "sv_roiaware_pool_backward_ordered": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "sv_boxes_overlap_bev":(c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "sv_boxes_iou3d_batch": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_nms_scratch_bytes": (c_sz, [c_i]),

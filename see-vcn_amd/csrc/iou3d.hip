@@ -14,6 +14,7 @@
 //   * per-box sin/cos are computed once per tile/box, not once per pair.
 #include <math.h>
 
+#include "box_test.h"
 #include "common.h"
 
 struct P2 { float x, y; };
@@ -343,10 +344,8 @@ __global__ __launch_bounds__(256) void k_points_in_boxes(int T, int M, const flo
   int32_t found = -1;
   for (int k = 0; k < T; ++k) {
     const float* s = sbox + k * 8;
-    if (fabsf(z - s[2]) > s[5] / 2.0) continue;              // double-precision compare like the reference (:28)
-    const float sx = x - s[0], sy = y - s[1];
-    const float lx = sx * s[6] + sy * (-s[7]), ly = sx * s[7] + sy * s[6];
-    if (fabs(lx) < s[3] / 2.0 + (double)1e-5f && fabs(ly) < s[4] / 2.0 + (double)1e-5f) { found = k; break; }
+    float lx, ly;
+    if (sv_pt_in_box3d(x, y, z, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], lx, ly)) { found = k; break; }
   }
   out[(int64_t)b * M + m] = found;
 }

@@ -134,6 +134,37 @@ def voxelrcnn_model_cfg(dynamic_vfe=False, **kw):
                 MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=VOXELRCNN_BACKBONE_2D, DENSE_HEAD=head,
                 ROI_HEAD=voxelrcnn_cfg(**kw), POST_PROCESSING=pp)
 
+# detector3d/tools/cfgs/kitti_models/PartA2.yaml:31-170 (values as data)
+def parta2_cfg(pool_size=12, max_points_per_voxel=128, num_features=128, roi_per_image=128, nms_post_train=512, nms_pre_train=9000, dp_ratio=0.3,
+               shared_fc=(256, 256, 256)):
+    """POINT_HEAD / ROI_HEAD sections of PartA2.yaml:95-160."""
+    point_head = dict(NAME='PointIntraPartOffsetHead', CLS_FC=[], PART_FC=[], CLASS_AGNOSTIC=True, TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2]),
+                      LOSS_CONFIG=dict(LOSS_REG='smooth-l1', LOSS_WEIGHTS=dict(point_cls_weight=1.0, point_part_weight=1.0)))
+    roi_head = dict(
+        NAME='PartA2FCHead', CLASS_AGNOSTIC=True, SHARED_FC=list(shared_fc), CLS_FC=[256, 256], REG_FC=[256, 256], DP_RATIO=dp_ratio,
+        SEG_MASK_SCORE_THRESH=0.3,
+        NMS_CONFIG=dict(TRAIN=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, NMS_PRE_MAXSIZE=nms_pre_train, NMS_POST_MAXSIZE=nms_post_train, NMS_THRESH=0.8),
+                        TEST=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, NMS_PRE_MAXSIZE=1024, NMS_POST_MAXSIZE=100, NMS_THRESH=0.7)),
+        ROI_AWARE_POOL=dict(POOL_SIZE=pool_size, NUM_FEATURES=num_features, MAX_POINTS_PER_VOXEL=max_points_per_voxel),
+        TARGET_CONFIG=dict(BOX_CODER='ResidualCoder', ROI_PER_IMAGE=roi_per_image, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE='roi_iou',
+                           CLS_FG_THRESH=0.75, CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.65),
+        LOSS_CONFIG=dict(CLS_LOSS='BinaryCrossEntropy', REG_LOSS='smooth-l1', CORNER_LOSS_REGULARIZATION=True,
+                         LOSS_WEIGHTS=dict(rcnn_cls_weight=1.0, rcnn_reg_weight=1.0, rcnn_corner_weight=1.0, code_weights=[1.0] * 7)))
+    return point_head, roi_head
+
+
+def parta2_model_cfg(dynamic_vfe=False, **kw):
+    """MODEL section of kitti_models/PartA2.yaml (its three anchors sit at bottom height -1.78); the keywords size the RoI head like
+    voxelrcnn_model_cfg's.  dynamic_vfe swaps MeanVFE for DynMeanVFE."""
+    point_head, roi_head = parta2_cfg(**kw)
+    head = dict(SECOND_DENSE_HEAD, ANCHOR_GENERATOR_CONFIG=[_anchor('Car', [3.9, 1.6, 1.56], -1.78, 0.6, 0.45),
+                                                            _anchor('Pedestrian', [0.8, 0.6, 1.73], -1.78, 0.5, 0.35),
+                                                            _anchor('Cyclist', [1.76, 0.6, 1.73], -1.78, 0.5, 0.35)])
+    pp = dict(SECOND_POST_PROCESSING, NMS_CONFIG=dict(SECOND_POST_PROCESSING['NMS_CONFIG'], NMS_THRESH=0.1))
+    return dict(NAME='PartA2Net', VFE=dict(NAME='DynMeanVFE' if dynamic_vfe else 'MeanVFE'), BACKBONE_3D=dict(NAME='UNetV2'),
+                MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=SECOND_BACKBONE_2D, DENSE_HEAD=head,
+                POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)
+
 # detector3d/tools/cfgs/nuscenes_models/cbgs_voxel0075_res3d_centerpoint.yaml:1-140 (values as data)
 NUSC_CLASS_NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle', 'pedestrian', 'traffic_cone']
 CENTER_HEAD = dict(

@@ -2,6 +2,7 @@ from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
 from .point_head_simple import PointHeadSimple
+from .point_intra_part_head import PointIntraPartOffsetHead
 
 # same registry shape as the reference (dense_heads/__init__.py:9-17)
 __all__ = {
@@ -9,4 +10,5 @@ __all__ = {
     'AnchorHeadSingle': AnchorHeadSingle,
     'PointHeadSimple': PointHeadSimple,
     'CenterHead': CenterHead,
+    'PointIntraPartOffsetHead': PointIntraPartOffsetHead,
 }

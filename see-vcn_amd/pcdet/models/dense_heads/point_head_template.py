@@ -25,10 +25,12 @@ class PointHeadTemplate(nn.Module):
         layers.append(nn.Linear(c_in, output_channels, bias=True))
         return nn.Sequential(*layers)
 
-    def assign_stack_targets(self, points, gt_boxes, extend_gt_boxes=None, set_ignore_flag=True, points_per_scene=None):
+    def assign_stack_targets(self, points, gt_boxes, extend_gt_boxes=None, set_ignore_flag=True, points_per_scene=None, ret_part_labels=False):
         """points (N,4) [b,x,y,z] stacked scene by scene with equal counts or ragged; gt_boxes (B,M,8).
         Labels: class (or 1) inside a box, -1 inside the enlarged box only, 0 elsewhere (reference :49-129,
-        set_ignore_flag branch).  One batched points-in-boxes launch per box set instead of a python loop over scenes."""
+        set_ignore_flag branch).  One batched points-in-boxes launch per box set instead of a python loop over scenes.
+        ret_part_labels: point_part_labels (N, 3), the position of every foreground point inside its box as a fraction of the box's extent per
+        axis (0.5 = the centre), 0 for the others (:114-122)."""
         assert len(points.shape) == 2 and points.shape[1] == 4 and len(gt_boxes.shape) == 3 and gt_boxes.shape[2] == 8
         assert set_ignore_flag, "ball-constraint targets are outside the built path"
         B = gt_boxes.shape[0]
@@ -49,7 +51,12 @@ class PointHeadTemplate(nn.Module):
             labels = torch.where(fg, torch.ones_like(labels), labels)
         else:
             labels = torch.where(fg, gt_boxes[points[:, 0].long(), box_idx.clamp(min=0), -1].long(), labels)
-        return {'point_cls_labels': labels, 'point_box_labels': None, 'point_part_labels': None}
+        part_labels = None
+        if ret_part_labels:
+            gt_of_point = gt_boxes[points[:, 0].long(), box_idx.clamp(min=0)]                     # (N, 8); rows of background points are not used
+            local = common_utils.rotate_points_along_z((points[:, 1:4] - gt_of_point[:, 0:3]).view(-1, 1, 3), -gt_of_point[:, 6]).view(-1, 3)
+            part_labels = torch.where(fg.unsqueeze(-1), local / gt_of_point[:, 3:6] + 0.5, torch.zeros_like(local))
+        return {'point_cls_labels': labels, 'point_box_labels': None, 'point_part_labels': part_labels}
 
     def get_cls_layer_loss(self, tb_dict=None):
         labels = self.forward_ret_dict['point_cls_labels'].view(-1)
@@ -64,6 +71,18 @@ class PointHeadTemplate(nn.Module):
         loss = loss * cfg_get(self.model_cfg, 'LOSS_CONFIG')['LOSS_WEIGHTS']['point_cls_weight']
         tb_dict = {} if tb_dict is None else tb_dict
         tb_dict.update({'point_loss_cls': common_utils.tb_value(loss), 'point_pos_num': common_utils.tb_value(pos_normalizer)})
+        return loss, tb_dict
+
+    def get_part_layer_loss(self, tb_dict=None):
+        """binary cross entropy of sigmoid(point_part_preds) against point_part_labels over the foreground points, / (3 * their number) (:157-170)"""
+        pos_mask = self.forward_ret_dict['point_cls_labels'] > 0
+        pos_normalizer = torch.clamp(pos_mask.sum().float(), min=1.0)                             # stays on the device: no read of the count
+        labels, preds = self.forward_ret_dict['point_part_labels'], self.forward_ret_dict['point_part_preds']
+        loss = torch.nn.functional.binary_cross_entropy(torch.sigmoid(preds), labels, reduction='none')
+        loss = (loss.sum(dim=-1) * pos_mask.float()).sum() / (3 * pos_normalizer)
+        loss = loss * cfg_get(self.model_cfg, 'LOSS_CONFIG')['LOSS_WEIGHTS']['point_part_weight']
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_loss_part': common_utils.tb_value(loss)})
         return loss, tb_dict
 
     def forward(self, **kwargs):

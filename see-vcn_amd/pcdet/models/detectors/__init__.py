@@ -1,3 +1,4 @@
+from .PartA2_net import PartA2Net
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .pointpillar import PointPillar
@@ -15,6 +16,7 @@ __all__ = {
     'PVRCNN': PVRCNN,
     'CenterPoint': CenterPoint,
     'VoxelRCNN': VoxelRCNN,
+    'PartA2Net': PartA2Net,
 }
 
 

@@ -1,3 +1,4 @@
+from .partA2_head import PartA2FCHead
 from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
 from .second_head import SECONDHead
@@ -8,4 +9,5 @@ __all__ = {
     'PVRCNNHead': PVRCNNHead,
     'SECONDHead': SECONDHead,
     'VoxelRCNNHead': VoxelRCNNHead,
+    'PartA2FCHead': PartA2FCHead,
 }

@@ -144,7 +144,9 @@ class RoIHeadTemplate(nn.Module):
         rcnn_cls = forward_ret_dict['rcnn_cls']
         labels = forward_ret_dict['rcnn_cls_labels'].view(-1)
         if cfg_get(lc, 'CLS_LOSS') == 'BinaryCrossEntropy':
-            batch_loss = F.binary_cross_entropy(torch.sigmoid(rcnn_cls.view(-1)), labels.float(), reduction='none')
+            # an ignored RoI's label is -1 and its term is masked below; torch's kernel checks 0 <= target <= 1 on the device and aborts the launch
+            # otherwise (PartA2FCHead marks every RoI -1 when fewer than 3 cells are occupied), so the masked rows are handed a 0
+            batch_loss = F.binary_cross_entropy(torch.sigmoid(rcnn_cls.view(-1)), labels.float().clamp(min=0), reduction='none')
         elif cfg_get(lc, 'CLS_LOSS') == 'CrossEntropy':
             batch_loss = F.cross_entropy(rcnn_cls, labels, reduction='none', ignore_index=-1)
         else:

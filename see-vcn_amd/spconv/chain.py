@@ -277,6 +277,8 @@ def flatten(stages):
         while j < len(mods):
             m = mods[j]
             if isinstance(m, SparseConvolution):
+                if m.inverse:
+                    return None                                                     # no launch-list rows for a mirrored table: module tree
                 if j + 2 >= len(mods) or norm.route(mods[j + 1]) is None or type(mods[j + 2]) is not torch.nn.ReLU:
                     return None
                 entries.append(Entry(m, mods[j + 1], True, None, False))

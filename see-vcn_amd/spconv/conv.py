@@ -23,13 +23,12 @@ class SparseConvolution(SparseModule):
     def __init__(self, ndim, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, subm=False, output_padding=0, transposed=False, inverse=False, indice_key=None, **kwargs):
         super().__init__()
-        assert ndim == 3 and groups == 1 and not transposed, "only 3-D submanifold and strided convs are built"
-        assert not inverse, "inverse convolutions are not built"
+        assert ndim == 3 and groups == 1 and not transposed, "only 3-D submanifold, strided and inverse convs are built"
         self.ndim = ndim
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride = _triple(kernel_size), _triple(stride)
         self.padding, self.dilation = _triple(padding), _triple(dilation)
-        self.subm, self.indice_key = subm, indice_key
+        self.subm, self.indice_key, self.inverse = subm, indice_key, bool(inverse)
         self.weight = nn.Parameter(torch.empty(out_channels, *self.kernel_size, in_channels))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self.reset_parameters()
@@ -62,6 +61,8 @@ class SparseConvolution(SparseModule):
         return hit[2]
 
     def get_rulebook(self, x):
+        if self.inverse:
+            return self._inverse_rulebook(x)
         rb = x.find_indice_pair(self.indice_key)
         if rb is not None and self.subm:
             assert rb.subm and rb.ksize == self.kernel_size, f"indice_key {self.indice_key} reused with a different kernel"
@@ -77,6 +78,20 @@ class SparseConvolution(SparseModule):
         if self.indice_key is not None:
             x.indice_dict[self.indice_key] = rb
         return rb
+
+    def _inverse_rulebook(self, x):
+        """The mirror (Fsp.MirrorRulebook) of the strided layer's rulebook under this layer's key, cached in the same dictionary."""
+        paired = x.find_indice_pair(self.indice_key)
+        if paired is None or paired.subm:
+            raise ValueError(f"SparseInverseConv3d: indice_key {self.indice_key!r} names no strided convolution's rulebook on this tensor "
+                             f"({'nothing was built under it' if paired is None else 'it belongs to a submanifold convolution'}); an inverse "
+                             f"convolution undoes the SparseConv3d that ran earlier under the same key")
+        assert paired.ksize == self.kernel_size, f"indice_key {self.indice_key} was built with kernel {paired.ksize}, not {self.kernel_size}"
+        assert x.indices.shape[0] == paired.n_out, f"indice_key {self.indice_key}: the input has {x.indices.shape[0]} rows, the paired layer made {paired.n_out}"
+        mirror = x.indice_dict.get((self.indice_key, "inverse"))
+        if mirror is None or mirror.paired is not paired:
+            mirror = x.indice_dict[(self.indice_key, "inverse")] = Fsp.MirrorRulebook(paired)
+        return mirror
 
     def forward(self, x):
         assert isinstance(x, SparseConvTensor)
@@ -122,12 +137,12 @@ class SparseConv3d(SparseConvolution):
 
 
 class SparseInverseConv3d(SparseConvolution):
-    """Name kept so that `spconv.SparseInverseConv3d` resolves (spconv_backbone.py:16-18 builds it for the UNet backbones only, SURVEY.md 2:
-    outside the hot path).  Constructing one fails at model-build time with a clear message."""
+    """spconv.SparseInverseConv3d as the UNet decoders use it (spconv_backbone.py:16-18): undoes the SparseConv3d that ran under the same
+    indice_key -- the output sites are that layer's input sites, z[i] = sum_k u[nbr_in[k][i]] W[k] over that layer's input-major table."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("SparseInverseConv3d (UNet decoders of UNetV2 / PartA2) is outside the SEE-VCN hot path and not built; "
-                                  "see INTEGRATION.md 'Unsupported surface'")
+    def __init__(self, in_channels, out_channels, kernel_size, indice_key=None, bias=True, **kwargs):
+        assert indice_key is not None, "an inverse convolution needs the indice_key of the strided layer it undoes"
+        super().__init__(3, in_channels, out_channels, kernel_size, bias=bias, subm=False, inverse=True, indice_key=indice_key, **kwargs)
 
 
 _registration_epoch = [0]
@@ -145,6 +160,8 @@ def _sparse_convs(root):
     """The SparseConvolution modules under `root` in definition order; the walk over nn.Module.modules() is cached on the root (0.25 ms per
     step otherwise) and redone whenever a submodule was registered or replaced anywhere since (global registration hook above) or the
     number of direct children changed (a deleted one)."""
+    if isinstance(root, (list, tuple)):
+        return [m for r in root for m in _sparse_convs(r)]
     n = (_registration_epoch[0], len(root._modules))
     hit = root.__dict__.get('_seevcn_sparse_convs')
     if hit is None or hit[0] != n:
@@ -163,6 +180,8 @@ def _index_specs(root, x):
     """ConvSpec list of the keyed convolutions in front of `root`'s walk, or None when the batch form does not apply to them."""
     specs, seen, level = [], {}, 0
     for m in _sparse_convs(root):
+        if m.inverse:
+            continue                                      # owns no table: it mirrors the one of its key
         if m.indice_key is None:
             break
         if x.indice_dict.get(m.indice_key) is not None:
@@ -185,7 +204,8 @@ def prebuild_rulebooks(root, x, with_backward=True, n0_dev=None):
     counted on the device, ONE read, all tables and plans in a handful of launches.  `root` is walked in definition order, which is the
     execution order of the reference's backbones; convolutions without an indice_key end the walk (they are then handled lazily).
     n0_dev: x.indices / x.features still have CAPACITY rows and the true count is this device word (a voxeliser called with sync=False): the
-    count comes back with the same read and x is narrowed in place.  -> x"""
+    count comes back with the same read and x is narrowed in place.  root: a module, or a list of modules walked one after the other (UNetV2
+    passes its encoder stages).  Inverse convolutions are passed over: they own no table.  -> x"""
     if BATCH_INDEX or n0_dev is not None:
         specs = _index_specs(root, x) if BATCH_INDEX else None
         built = Fsp.build_network_index(x.indices, x.batch_size, x.spatial_shape, specs, n0_dev=n0_dev, with_backward=with_backward) if specs else None
@@ -217,6 +237,8 @@ def _prebuild_layer_by_layer(root, x, with_backward):
     # in front of every later read -- ~145 us of index kernels per level that the host waited for four times per step.
     todo = []                                             # (module, its input indices, their shape) in execution order
     for m in _sparse_convs(root):
+        if m.inverse:
+            continue                                      # owns no table: it mirrors the one of its key
         if m.indice_key is None:
             break
         if m.subm and DEFER_INDEX_WORK:

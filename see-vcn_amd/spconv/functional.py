@@ -180,13 +180,18 @@ class Rulebook(_ArenaViews):
             return None
         key = "fwd" if (direction == "fwd" or self.subm) else "bwd"
         g = lib.sv_conv_tiles_per_wave(n_rows, kd, nc)
+        tp = self._table_plan(key, n_rows, g)
+        return tp, tp.tiles(g), g, (direction == "bwd" and self.subm)
+
+    def _table_plan(self, key, n_rows, g):
+        """The TablePlan of the output-major ('fwd') or input-major ('bwd') table, made on first use (build_network_index leaves the ones it was
+        asked for; with_backward=False leaves no 'bwd' one)."""
         if key not in self._plans:
             if key == "fwd":
                 self._plans[key] = TablePlan(self.nbr_out, n_rows, self.K, self.rows_out, self.masks_out, g=g)
             else:
                 self._plans[key] = TablePlan(self.nbr_in, n_rows, self.K, self.rows_in, self.masks_in, g=g)
-        tp = self._plans[key]
-        return tp, tp.tiles(g), g, (direction == "bwd" and self.subm)
+        return self._plans[key]
 
     def plan_addrs(self, direction, kd, nc):
         """plan() as device addresses for a launch list: (rows, perm, masks_p, tile_of, tiles_per_wave, table_k_reversed) or None -- no tensor view
@@ -244,6 +249,33 @@ class Rulebook(_ArenaViews):
         _lib.check(lib.sv_rulebook_pair_counts(_lib.ptr(self.nbr_out), self.n_out, self.K, _lib.ptr(counts), _lib.stream()),
                    "sv_rulebook_pair_counts")
         return counts
+
+
+class MirrorRulebook(Rulebook):
+    """The rulebook of the inverse convolution that undoes a strided layer: that layer's rulebook with the two sides swapped.  Its output-major
+    table is the paired layer's input-major one (z[i] = sum_k u[nbr_in[k][i]] W[k]: the gather-GEMM of the paired layer's data gradient with
+    weights of its own), its outputs are the paired layer's input sites.  Tables, row-major twins and masks are the paired rulebook's tensors;
+    the TablePlans are the paired rulebook's OBJECTS, made there on first use, so both layers deal their tiles from one regrouping.  Only the
+    weight-gradient plan is this rulebook's own (it depends on which side is the output).  The mirror refers to the paired rulebook, never the
+    other way round (no reference cycle around an index arena)."""
+
+    def __init__(self, paired):
+        assert not paired.subm and paired.nbr_in is not None and paired.in_indices is not None
+        super().__init__(paired.nbr_in, paired.nbr_out, paired.in_indices, list(paired.in_shape), paired.n_out, paired.n_in, False, list(paired.ksize))
+        self.paired = paired
+        self._K = paired.K
+        self.rows_out, self.masks_out, self.rows_in, self.masks_in = paired.rows_in, paired.masks_in, paired.rows_out, paired.masks_out
+        self.in_indices, self.in_shape = paired.out_indices, list(paired.out_shape)
+
+    def _table_plan(self, key, n_rows, g):
+        return self.paired._table_plan("bwd" if key == "fwd" else "fwd", n_rows, g)
+
+    def plan_addrs(self, direction, kd, nc):
+        p = self.plan(direction, kd, nc)
+        if p is None:
+            return None
+        tp, tile_of, g, rev = p
+        return tp.addr("rows"), tp.addr("perm"), tp.addr("masks_p"), tile_of.data_ptr(), g, rev
 
 
 # dense cell -> row maps (4 B per cell) up to this size replace the rank dictionary in submanifold rulebooks (MI355X: 288 GB of HBM)
