@@ -99,8 +99,9 @@ def _nms(boxes, scores, thresh, pre_maxsize, normal, max_keep=None, padded=None,
         valid = torch.arange(padded, device=dev) < torch.clamp(num_out, max=padded)
         if n == 0:
             return torch.zeros((padded,), dtype=torch.int64, device=dev), valid
-        kept = torch.where(valid, keep[:padded], torch.zeros_like(keep[:padded]))
-        return (kept if order is None else order[kept]), valid
+        zeros = torch.zeros_like(keep[:padded])
+        kept = torch.where(valid, keep[:padded], zeros)
+        return (kept if order is None else torch.where(valid, order[kept], zeros)), valid      # (order[0] is the best box, not "no box")
     kept = keep[:int(num_out.item())]
     return (kept if order is None else order[kept]).contiguous(), None
 
