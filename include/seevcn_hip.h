@@ -580,6 +580,18 @@ size_t sv_roiaware_pool_backward_ordered_scratch_bytes(int n_boxes, int cells, i
 int sv_roiaware_pool_backward_ordered(const int32_t* pts_idx_of_voxels, const int32_t* argmax, const float* grad_out, int n_boxes, int cells, int C,
                                       int max_pts_each_voxel, int pool_method, int n_pts, void* scratch, float* grad_in, void* stream);
 
+/* ---- PointRCNN's RoI point pooling (csrc/roipoint_pool.hip; detector3d/pcdet/ops/roipoint_pool3d/src/roipoint_pool3d_kernel.cu:38-165) in ONE
+ * launch, without the reference's (B, N, M) table and its one-thread-per-box walk.  xyz (B, N, 3), pts_feature (B, N, C), boxes3d (B, M, 7)
+ * already enlarged by the caller; pooled (B, M, S, 3 + C), empty_flag (B, M) int32, S = n_sampled.  The list of box (b, m) is the rows of scene b
+ * that pass the in-box test (the one sv_points_in_boxes uses), ascending, cut after S; cnt == 0: flag 1 and S rows of zeros; 0 < cnt < S: slot
+ * k >= cnt repeats slot k % cnt; row s = [xyz[b, list[s]] | pts_feature[b, list[s]]].  EVERY element of pooled and empty_flag is written (the
+ * reference relies on zero-filled outputs).  canonical = 1 (seevcn extension): the three xyz columns hold the point in the box's frame instead,
+ * (lx, ly) of the in-box test and z - cz in fp32 -- rotate_points_along_z(p - centre, -heading) of pointrcnn_head.py:121-128, fused.
+ * batch == 0, n_boxes == 0, n_pts == 0 (every box empty) and C == 0 (rows of xyz only) return cleanly; n_sampled outside 1..4096, a negative
+ * size, a null or a host pointer is an error. */
+int sv_roipoint_pool3d(const float* xyz, const float* pts_feature, const float* boxes3d, int batch, int n_pts, int n_boxes, int C, int n_sampled,
+                       int canonical, float* pooled, int32_t* empty_flag, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Rotated-box geometry (detector3d/pcdet/ops/iou3d_nms/src/iou3d_nms_api.cpp:12-17,
  * detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:172-177). Boxes are (N,7) fp32 [x,y,z,dx,dy,dz,heading].

@@ -143,6 +143,7 @@ SIGNATURES = {
     "sv_roiaware_pool_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "sv_roiaware_pool_backward_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "sv_roiaware_pool_backward_ordered": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "sv_roipoint_pool3d": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "sv_boxes_overlap_bev":(c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "sv_boxes_iou3d_batch": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_nms_scratch_bytes": (c_sz, [c_i]),

@@ -33,6 +33,16 @@ void sv_set_error(const char* fmt, ...);
 
 static inline hipStream_t sv_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Whether the runtime knows p as device (or managed) memory; a host pointer or one it has never seen is not.
+static inline bool sv_on_device(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();                // a pointer the runtime does not know: clear the sticky error it leaves
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
 static inline int sv_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Grid for a grid-stride 1-D kernel: enough workgroups to fill 256 CUs x 8, never more than the work.

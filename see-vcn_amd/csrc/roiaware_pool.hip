@@ -12,15 +12,6 @@ constexpr int RA_THREADS = 256;
 constexpr int RA_MAX_CELLS = 4096;          // cell counters of one box in LDS: 16 KB
 constexpr int RA_MAX_OUT = 255;             // the reference packs a cell into 3 x 8 bits (:72) and silently corrupts beyond
 
-static bool ra_on_device(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();                // a pointer the runtime does not know: clear the sticky error it leaves
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Assignment.  Chunks of 256 consecutive points; every lane tests its point (sv_pt_in_box3d) and computes its cell with the reference's fp32
 // statements (:57-70).  The inside points of a chunk are compacted IN INDEX ORDER into an LDS staging list (ballot rank in the wave, wave totals
@@ -110,8 +101,8 @@ extern "C" int sv_roiaware_assign(const float* rois, int n_boxes, const float* p
   SV_CHECK_ARG(max_pts_each_voxel >= 2, "roiaware_assign: max_pts_each_voxel %d holds no point (slot 0 is the count)", max_pts_each_voxel);
   if (n_boxes == 0) return SV_OK;
   SV_CHECK_ARG(rois && pts_idx_of_voxels && (n_pts == 0 || pts), "roiaware_assign: null pointer");
-  SV_CHECK_ARG(ra_on_device(rois) && ra_on_device(pts_idx_of_voxels) && (n_pts == 0 || ra_on_device(pts)) &&
-                   (!box_pt_range || ra_on_device(box_pt_range)),
+  SV_CHECK_ARG(sv_on_device(rois) && sv_on_device(pts_idx_of_voxels) && (n_pts == 0 || sv_on_device(pts)) &&
+                   (!box_pt_range || sv_on_device(box_pt_range)),
                "roiaware_assign: a pointer is not device memory");
   hipLaunchKernelGGL(k_roiaware_assign, dim3(n_boxes), dim3(RA_THREADS), 0, sv_stream(stream), rois, pts, n_pts, box_pt_range, out_x, out_y, out_z,
                      max_pts_each_voxel, pts_idx_of_voxels);
@@ -193,8 +184,8 @@ extern "C" int sv_roiaware_pool(const float* pts_feature, int C, const int32_t* 
   SV_CHECK_ARG(pool_method == 0 || pool_method == 1, "roiaware_pool: pool_method %d is neither 0 (max) nor 1 (avg)", pool_method);
   if (n_boxes == 0) return SV_OK;
   SV_CHECK_ARG(pts_idx_of_voxels && pooled && (pool_method == 1 || argmax), "roiaware_pool: null pointer");
-  SV_CHECK_ARG(ra_on_device(pts_idx_of_voxels) && ra_on_device(pooled) && (pool_method == 1 || ra_on_device(argmax)) &&
-                   (!pts_feature || ra_on_device(pts_feature)),
+  SV_CHECK_ARG(sv_on_device(pts_idx_of_voxels) && sv_on_device(pooled) && (pool_method == 1 || sv_on_device(argmax)) &&
+                   (!pts_feature || sv_on_device(pts_feature)),
                "roiaware_pool: a pointer is not device memory");
   // pts_feature may be NULL when there are no points: every count is 0 then and no row is read
   const bool vec = C % 4 == 0 && (((uintptr_t)pts_feature | (uintptr_t)pooled | (uintptr_t)argmax) & 15) == 0;
@@ -244,13 +235,13 @@ extern "C" int sv_roiaware_pool_backward(const int32_t* pts_idx_of_voxels, const
   if (int rc = ra_check_pool_shape("roiaware_pool_backward", C, n_boxes, cells, max_pts_each_voxel)) return rc;
   SV_CHECK_ARG(n_pts >= 0 && (pool_method == 0 || pool_method == 1), "roiaware_pool_backward: bad arguments");
   if (n_pts == 0) return SV_OK;
-  SV_CHECK_ARG(grad_in && ra_on_device(grad_in), "roiaware_pool_backward: grad_in is null or not device memory");
+  SV_CHECK_ARG(grad_in && sv_on_device(grad_in), "roiaware_pool_backward: grad_in is null or not device memory");
   hipStream_t st = sv_stream(stream);
   SV_HIP(hipMemsetAsync(grad_in, 0, (size_t)n_pts * C * 4, st));
   if (n_boxes == 0) return SV_OK;
   const int32_t* need = pool_method == 0 ? argmax : pts_idx_of_voxels;
   SV_CHECK_ARG(grad_out && need, "roiaware_pool_backward: null pointer");
-  SV_CHECK_ARG(ra_on_device(grad_out) && ra_on_device(need), "roiaware_pool_backward: a pointer is not device memory");
+  SV_CHECK_ARG(sv_on_device(grad_out) && sv_on_device(need), "roiaware_pool_backward: a pointer is not device memory");
   const int64_t total = (int64_t)n_boxes * cells * C;
   const dim3 grid(sv_grid_1d(total, 256, 256 * 32)), block(256);
   if (pool_method == 0)
@@ -328,10 +319,10 @@ extern "C" int sv_roiaware_pool_backward_ordered(const int32_t* pts_idx_of_voxel
   if (int rc = ra_check_pool_shape("roiaware_pool_backward_ordered", C, n_boxes, cells, max_pts_each_voxel)) return rc;
   SV_CHECK_ARG(n_pts >= 0 && (pool_method == 0 || pool_method == 1), "roiaware_pool_backward_ordered: bad arguments");
   if (n_pts == 0) return SV_OK;
-  SV_CHECK_ARG(grad_in && scratch && ra_on_device(grad_in) && ra_on_device(scratch),
+  SV_CHECK_ARG(grad_in && scratch && sv_on_device(grad_in) && sv_on_device(scratch),
                "roiaware_pool_backward_ordered: grad_in or scratch is null or not device memory");
   const int32_t* need = pool_method == 0 ? argmax : pts_idx_of_voxels;
-  SV_CHECK_ARG(n_boxes == 0 || (grad_out && need && ra_on_device(grad_out) && ra_on_device(need)),
+  SV_CHECK_ARG(n_boxes == 0 || (grad_out && need && sv_on_device(grad_out) && sv_on_device(need)),
                "roiaware_pool_backward_ordered: a pointer is null or not device memory");
   hipStream_t st = sv_stream(stream);
   const int64_t keys = ra_ordered_keys(n_boxes, cells, C, max_pts_each_voxel, pool_method);

@@ -221,3 +221,42 @@ def see_pvrcnn_model_cfg(dynamic_vfe=True, **kw):
     return dict(NAME='PVRCNN', VFE=dict(NAME='DynMeanVFE' if dynamic_vfe else 'MeanVFE'), BACKBONE_3D=dict(NAME='VoxelBackBone8x'),
                 MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=SECOND_BACKBONE_2D, DENSE_HEAD=head,
                 PFE=pfe, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)
+
+
+# detector3d/tools/cfgs/kitti_models/pointrcnn.yaml:22-138 and pointrcnn_iou.yaml (values as data)
+def pointrcnn_cfg(npoints=(4096, 1024, 256, 64), roi_npoints=(128, 32, -1), num_sampled_points=512, roi_per_image=128, nms_pre_train=9000,
+                  nms_post_train=512, nms_pre_test=9000, nms_post_test=100, cls_score_type='cls', use_bn=False):
+    """BACKBONE_3D / POINT_HEAD / ROI_HEAD sections of pointrcnn.yaml; cls_score_type='roi_iou' gives pointrcnn_iou.yaml (its CLS_SCORE_TYPE and
+    the two classification thresholds are all that differ).  The keywords scale the model down for tests; radii, sample counts and channel
+    widths stay the yaml's."""
+    assert cls_score_type in ('cls', 'roi_iou') and len(npoints) == 4 and len(roi_npoints) == 3
+    backbone = dict(NAME='PointNet2MSG',
+                    SA_CONFIG=dict(NPOINTS=list(npoints), RADIUS=[[0.1, 0.5], [0.5, 1.0], [1.0, 2.0], [2.0, 4.0]], NSAMPLE=[[16, 32]] * 4,
+                                   MLPS=[[[16, 16, 32], [32, 32, 64]], [[64, 64, 128], [64, 96, 128]], [[128, 196, 256], [128, 196, 256]],
+                                         [[256, 256, 512], [256, 384, 512]]]),
+                    FP_MLPS=[[128, 128], [256, 256], [512, 512], [512, 512]])
+    point_head = dict(NAME='PointHeadBox', CLS_FC=[256, 256], REG_FC=[256, 256], CLASS_AGNOSTIC=False, USE_POINT_FEATURES_BEFORE_FUSION=False,
+                      TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], BOX_CODER='PointResidualCoder',
+                                         BOX_CODER_CONFIG=dict(use_mean_size=True, mean_size=[[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]])),
+                      LOSS_CONFIG=dict(LOSS_REG='WeightedSmoothL1Loss', LOSS_WEIGHTS=dict(point_cls_weight=1.0, point_box_weight=1.0, code_weights=[1.0] * 8)))
+    fg, bg = (0.6, 0.45) if cls_score_type == 'cls' else (0.7, 0.25)
+    roi_head = dict(
+        NAME='PointRCNNHead', CLASS_AGNOSTIC=True,
+        ROI_POINT_POOL=dict(POOL_EXTRA_WIDTH=[0.0, 0.0, 0.0], NUM_SAMPLED_POINTS=num_sampled_points, DEPTH_NORMALIZER=70.0),
+        XYZ_UP_LAYER=[128, 128], CLS_FC=[256, 256], REG_FC=[256, 256], DP_RATIO=0.0, USE_BN=use_bn,
+        SA_CONFIG=dict(NPOINTS=list(roi_npoints), RADIUS=[0.2, 0.4, 100], NSAMPLE=[16, 16, 16], MLPS=[[128, 128, 128], [128, 128, 256], [256, 256, 512]]),
+        NMS_CONFIG=dict(TRAIN=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, NMS_PRE_MAXSIZE=nms_pre_train, NMS_POST_MAXSIZE=nms_post_train, NMS_THRESH=0.8),
+                        TEST=dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False, NMS_PRE_MAXSIZE=nms_pre_test, NMS_POST_MAXSIZE=nms_post_test, NMS_THRESH=0.85)),
+        TARGET_CONFIG=dict(BOX_CODER='ResidualCoder', ROI_PER_IMAGE=roi_per_image, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True,
+                           CLS_SCORE_TYPE=cls_score_type, CLS_FG_THRESH=fg, CLS_BG_THRESH=bg, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55),
+        LOSS_CONFIG=dict(CLS_LOSS='BinaryCrossEntropy', REG_LOSS='smooth-l1', CORNER_LOSS_REGULARIZATION=True,
+                         LOSS_WEIGHTS=dict(rcnn_cls_weight=1.0, rcnn_reg_weight=1.0, rcnn_corner_weight=1.0, code_weights=[1.0] * 7)))
+    return backbone, point_head, roi_head
+
+
+def pointrcnn_model_cfg(**kw):
+    """MODEL section of kitti_models/pointrcnn.yaml (pointrcnn_iou.yaml with cls_score_type='roi_iou'): no VFE, no BEV branch, no dense head.
+    Build it with a dataset of 4 point features (x, y, z, intensity)."""
+    backbone, point_head, roi_head = pointrcnn_cfg(**kw)
+    pp = dict(SECOND_POST_PROCESSING, NMS_CONFIG=dict(SECOND_POST_PROCESSING['NMS_CONFIG'], NMS_THRESH=0.1))
+    return dict(NAME='PointRCNN', BACKBONE_3D=backbone, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)

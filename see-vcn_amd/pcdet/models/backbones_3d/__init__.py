@@ -1,3 +1,4 @@
+from .pointnet2_backbone import PointNet2MSG
 from .spconv_backbone import VoxelBackBone8x, VoxelResBackBone8x
 from .spconv_unet import UNetV2
 
@@ -6,4 +7,5 @@ __all__ = {
     'VoxelBackBone8x': VoxelBackBone8x,
     'VoxelResBackBone8x': VoxelResBackBone8x,
     'UNetV2': UNetV2,
+    'PointNet2MSG': PointNet2MSG,
 }

@@ -1,6 +1,7 @@
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
+from .point_head_box import PointHeadBox
 from .point_head_simple import PointHeadSimple
 from .point_intra_part_head import PointIntraPartOffsetHead
 
@@ -11,4 +12,5 @@ __all__ = {
     'PointHeadSimple': PointHeadSimple,
     'CenterHead': CenterHead,
     'PointIntraPartOffsetHead': PointIntraPartOffsetHead,
+    'PointHeadBox': PointHeadBox,
 }

@@ -1,6 +1,7 @@
 from .PartA2_net import PartA2Net
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
+from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
 from .second_net import SECONDNet
@@ -17,6 +18,7 @@ __all__ = {
     'CenterPoint': CenterPoint,
     'VoxelRCNN': VoxelRCNN,
     'PartA2Net': PartA2Net,
+    'PointRCNN': PointRCNN,
 }
 
 

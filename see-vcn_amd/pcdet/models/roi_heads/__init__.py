@@ -1,4 +1,5 @@
 from .partA2_head import PartA2FCHead
+from .pointrcnn_head import PointRCNNHead
 from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
 from .second_head import SECONDHead
@@ -10,4 +11,5 @@ __all__ = {
     'SECONDHead': SECONDHead,
     'VoxelRCNNHead': VoxelRCNNHead,
     'PartA2FCHead': PartA2FCHead,
+    'PointRCNNHead': PointRCNNHead,
 }
