@@ -523,6 +523,58 @@ size_t sv_group_points_grad_stack_ordered_scratch_bytes(int M, int N, int nsampl
 int sv_group_points_grad_stack_ordered(int M, int C, int N, int nsample, const float* grad_out, const int32_t* idx, const int32_t* row_start,
                                        void* scratch, float* grad_features, void* stream);
 
+/* ---- PV-RCNN++'s vector-pool local aggregation (csrc/vector_pool.hip).  Stacked batches as for sv_ball_query_stack: per-scene start and
+ * count arrays for the queries (M rows in all) and the support points (N rows in all); max_queries_per_scene may be any upper bound (M).
+ * Nothing is sized on the host, read back or retried (the reference's Python wrappers re-run their kernels in a `while True` loop with a
+ * larger buffer, pointnet2_utils.py:331-347, 399-415).
+ *
+ * sv_vector_pool_choice: vector_pool_kernel_stack with pooling_type == 1, `voxel_random_choice` (src/vector_pool_gpu.cu:243-373, launcher
+ * :376-430).  Per query, walk its scene in ascending row order; local = p - q in fp32; a row is in range unless any |local| > R (cube) or
+ * lx^2 + ly^2 + lz^2 > R * R (neighbor_type == 1, ball); its cell is ix * ny * nz + iy * nz + iz with i = floorf((local + R) / gs),
+ * gs = R * 2 / n in fp32, THEN clamped to [0, G - 1] (so a row at local == +R aliases, as in the reference); an in-range row whose cell is
+ * still empty is taken; the walk ends after nsample taken rows (nsample > 0) or G.  G = nx * ny * nz <= 512.
+ * Writes every element of: choice (M, G) global support row or -1; point_cnt (M, G) in {0, 1}; new_local_xyz (M, 3 G) the taken row's
+ * local, zeros for an empty cell; new_features (M, G * c_each): channel j of a cell = features[row][c_in - c_each + j] (the reference's
+ * `i % c_each` overwrite: the last channel group wins), zeros for an empty cell.  These are final: the reference's division by
+ * clamp_min(cnt, 1e-6) divides by 1 or yields 0. */
+int sv_vector_pool_choice(int batch, int M, int N, int max_queries_per_scene, const float* new_xyz, const int32_t* new_xyz_batch_start,
+                          const int32_t* new_xyz_batch_cnt, const float* xyz, const float* features, const int32_t* xyz_batch_start,
+                          const int32_t* xyz_batch_cnt, int c_in, int c_each, int nx, int ny, int nz, float max_neighbour_distance,
+                          int nsample, int neighbor_type, int32_t* choice, int32_t* point_cnt, float* new_local_xyz, float* new_features,
+                          void* stream);
+/* vector_pool_grad_kernel_stack (src/vector_pool_gpu.cu:433-458) over choice instead of grouped_idxs: for every c < c_in
+ *   grad_support[choice[m][g]][c] += grad_new[m][g * c_each + c % c_each] * (1 / max(cnt[m][g], 1))
+ * (every input channel group receives the gradient).  The plain entry zero-fills grad_support (N, c_in) and adds with fp32 atomics; the
+ * ordered entry (opt-in) writes every element once, +0.0f + the terms in ascending key m * G + g, every sum rounded to fp32, no float
+ * atomics; scratch: sv_vector_pool_choice_grad_ordered_scratch_bytes bytes (uninitialised), needs M * G < 2^31. */
+int sv_vector_pool_choice_grad(int M, int N, int G, int c_in, int c_each, const float* grad_new, const int32_t* choice,
+                               const int32_t* point_cnt, float* grad_support, void* stream);
+size_t sv_vector_pool_choice_grad_ordered_scratch_bytes(int M, int N, int G);
+int sv_vector_pool_choice_grad_ordered(int M, int N, int G, int c_in, int c_each, const float* grad_new, const int32_t* choice,
+                                       const int32_t* point_cnt, void* scratch, float* grad_support, void* stream);
+/* `local_interpolation`: query_stacked_local_neighbor_idxs_kernel + query_three_nn_by_stacked_local_idxs_kernel (src/vector_pool_gpu.cu:122-205,
+ * 19-86) in one launch, without stack_neighbor_idxs / start_len / cumsum.  A query's list = the first min(1000, nsample if nsample > 0) rows
+ * of its scene, ascending, that pass the rejection test above with R = max_neighbour_distance (the caller passes distance * multiplier).  Per
+ * grid centre (new_xyz_grid_centers (M, G, 3)): the three list entries smallest under (d, position in list), d = (cx-x)^2 + (cy-y)^2 + (cz-z)^2
+ * in fp32.  idx (M, G, 3) global rows, dist2 (M, G, 3); one entry found: slots 2 and 3 repeat slot 1; two: slot 3 repeats slot 1; none:
+ * idx = -1, dist2 = +inf. */
+int sv_vector_pool_three_nn(int batch, int M, int N, int max_queries_per_scene, const float* new_xyz, const float* new_xyz_grid_centers,
+                            const int32_t* new_xyz_batch_start, const int32_t* new_xyz_batch_cnt, const float* xyz,
+                            const int32_t* xyz_batch_start, const int32_t* xyz_batch_cnt, int num_total_grids, float max_neighbour_distance,
+                            int nsample, int neighbor_type, int32_t* idx, float* dist2, void* stream);
+/* three_interpolate_kernel_stack / three_interpolate_grad_kernel_stack (src/interpolate_gpu.cu:107-126, 151-172): features (n_features, C),
+ * idx / weight (rows, 3) -> out (rows, C) = w0 * f[i0] + w1 * f[i1] + w2 * f[i2], three rounded products summed left to right.  The plain
+ * gradient zero-fills grad_features (n_features, C) and adds fp32(grad_out[r][c] * w[r][t]) with fp32 atomics; the ordered entry (opt-in) sums
+ * the same terms from +0.0f in ascending key 3 r + t and writes every element once (scratch: ..._ordered_scratch_bytes, 3 * rows < 2^31).
+ * An index outside [0, n_features) contributes nothing anywhere. */
+int sv_three_interpolate_stack(int rows, int C, int n_features, const float* features, const int32_t* idx, const float* weight, float* out,
+                               void* stream);
+int sv_three_interpolate_grad_stack(int rows, int C, int n_features, const float* grad_out, const int32_t* idx, const float* weight,
+                                    float* grad_features, void* stream);
+size_t sv_three_interpolate_grad_stack_ordered_scratch_bytes(int rows, int n_features);
+int sv_three_interpolate_grad_stack_ordered(int rows, int C, int n_features, const float* grad_out, const int32_t* idx, const float* weight,
+                                            void* scratch, float* grad_features, void* stream);
+
 /* ---- Voxel R-CNN's voxel RoI pooling (csrc/voxel_pool.hip).
  * generate_voxel2pinds / scatter_point_inds (detector3d/pcdet/utils/common_utils.py:235-252): volume (B, Z, Y, X) int32 = -1 everywhere and r at
  * [b, z, y, x] of row r of coords (N, 4), offsets in 64 bits (the volume may hold 2^31 cells or more); a row outside the volume writes nothing.
@@ -983,9 +1035,8 @@ int sv_isolate_largest_cluster(const float* points, int row_stride, const int32_
 
 /* ---- roiaware_pool3d_cuda.points_in_boxes_cpu (detector3d/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-165; a host loop in the
  * reference): out (N,M) int32 0/1, box test with MARGIN 1e-2 (points_in_boxes_gpu uses 1e-5 and returns one box per point).
- * The RoI-aware pooling entries of that module (forward / backward: PartA2 only) and the PV-RCNN++ entries of pointnet2_stack_cuda
- * (vector_pool, local 3-NN) are not on the path of any BASELINE config and are not part of this library; voxel_query is
- * sv_voxel_query_stack above. */
+ * The PV-RCNN++ entries of pointnet2_stack_cuda (vector_pool, local 3-NN) are the sv_vector_pool_* entries above, voxel_query is
+ * sv_voxel_query_stack. */
 int sv_points_in_boxes_matrix(const float* boxes, const float* pts, int num_boxes, int num_points, int32_t* out, void* stream);
 
 #ifdef __cplusplus

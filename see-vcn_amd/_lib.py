@@ -135,6 +135,16 @@ SIGNATURES = {
     "sv_group_points_grad_stack": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_group_points_grad_stack_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "sv_group_points_grad_stack_ordered": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vector_pool_choice": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p,
+                                    c_p, c_p]),
+    "sv_vector_pool_choice_grad": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vector_pool_choice_grad_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sv_vector_pool_choice_grad_ordered": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vector_pool_three_nn": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p]),
+    "sv_three_interpolate_stack": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_three_interpolate_grad_stack": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_three_interpolate_grad_stack_ordered_scratch_bytes": (c_sz, [c_i, c_i]),
+    "sv_three_interpolate_grad_stack_ordered": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sv_voxel2pinds": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "sv_voxel_query_stack": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sv_voxel_pool_max": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p]),

@@ -96,6 +96,26 @@ def pvrcnn_cfg(num_keypoints=2048, features_source=('bev', 'x_conv1', 'x_conv2',
     return pfe, point_head, roi_head
 
 
+def _vector_pool(kind, reduced, post_msg, groups, **extra):
+    d = dict(NAME='VectorPoolAggregationModuleMSG', NUM_GROUPS=len(groups), LOCAL_AGGREGATION_TYPE=kind, NUM_REDUCED_CHANNELS=reduced,
+             NUM_CHANNELS_OF_LOCAL_AGGREGATION=32, MSG_POST_MLPS=[post_msg], **extra)
+    for k, (voxels, dist, nsample, post) in enumerate(groups):
+        d[f'GROUP_CFG_{k}'] = dict(NUM_LOCAL_VOXEL=list(voxels), MAX_NEIGHBOR_DISTANCE=dist, NEIGHBOR_NSAMPLE=nsample, POST_MLPS=[post, post])
+    return d
+
+
+# detector3d/tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml:76-140, 160-179 (values as data): the vector-pool SA_LAYERs of the PFE and the
+# ROI_GRID_POOL of the PVRCNNHead.  FILTER_NEIGHBOR_WITH_ROI / RADIUS_OF_NEIGHBOR_WITH_ROI are the yaml's; nothing built reads them yet.
+PVRCNNPP_SA_LAYER = dict(
+    raw_points=_vector_pool('local_interpolation', 2, 32, [((2, 2, 2), 0.2, -1, 32), ((3, 3, 3), 0.4, -1, 32)],
+                            FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=2.4),
+    x_conv3=_vector_pool('local_interpolation', 32, 128, [((3, 3, 3), 1.2, -1, 64), ((3, 3, 3), 2.4, -1, 64)], DOWNSAMPLE_FACTOR=4,
+                         INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=4.0),
+    x_conv4=_vector_pool('local_interpolation', 32, 128, [((3, 3, 3), 2.4, -1, 64), ((3, 3, 3), 4.8, -1, 64)], DOWNSAMPLE_FACTOR=8,
+                         INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=6.4))
+PVRCNNPP_ROI_GRID_POOL = _vector_pool('voxel_random_choice', 30, 128, [((3, 3, 3), 0.8, 32, 64), ((3, 3, 3), 1.6, 32, 64)], GRID_SIZE=6)
+
+
 def pvrcnn_model_cfg(**kw):
     pfe, point_head, roi_head = pvrcnn_cfg(**kw)
     pp = dict(SECOND_POST_PROCESSING, NMS_CONFIG=dict(SECOND_POST_PROCESSING['NMS_CONFIG'], NMS_THRESH=0.1))

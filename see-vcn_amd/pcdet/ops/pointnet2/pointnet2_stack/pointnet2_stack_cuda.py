@@ -217,19 +217,117 @@ def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_rang
     return 1
 
 
-def _outside_hot_path(name):
+def three_interpolate_wrapper(features, idx, weight, out):
+    """src/interpolate.cpp three_interpolate_wrapper_stack: features (M, C), idx / weight (N, 3) -> out (N, C), every element written."""
+    lib = _lib.load()
+    _lib.require_cuda(features, idx, weight, out)
+    assert idx.dtype == torch.int32 and features.dtype == weight.dtype == out.dtype == torch.float32
+    rc = lib.sv_three_interpolate_stack(int(idx.shape[0]), int(features.shape[1]), int(features.shape[0]), _lib.ptr(features), _lib.ptr(idx),
+                                        _lib.ptr(weight), _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "sv_three_interpolate_stack")
+    return 1
+
+
+def three_interpolate_grad_wrapper(grad_out, idx, weight, grad_features):
+    """src/interpolate.cpp three_interpolate_grad_wrapper_stack: grad_out (N, C) -> grad_features (M, C), every element written (the plain
+    route zero-fills and adds with float atomics; the ordered route sums in ascending key 3 r + t)."""
+    lib = _lib.load()
+    _lib.require_cuda(grad_out, idx, weight, grad_features)
+    assert idx.dtype == torch.int32 and grad_out.dtype == weight.dtype == grad_features.dtype == torch.float32
+    rows, C, n = int(idx.shape[0]), int(grad_out.shape[1]), int(grad_features.shape[0])
+    if ordered.ordered_gradients():
+        nbytes = lib.sv_three_interpolate_grad_stack_ordered_scratch_bytes(rows, n)
+        scratch = _lib.workspace.scratch("three_interp_grad_ordered", nbytes, grad_out.device)
+        rc = lib.sv_three_interpolate_grad_stack_ordered(rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(scratch),
+                                                         _lib.ptr(grad_features), _lib.stream())
+        _lib.check(rc, "sv_three_interpolate_grad_stack_ordered")
+        ordered.count_call("three_interpolate")
+        return 1
+    rc = lib.sv_three_interpolate_grad_stack(rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features),
+                                             _lib.stream())
+    _lib.check(rc, "sv_three_interpolate_grad_stack")
+    return 1
+
+
+def vector_pool_choice(support_xyz, xyz_batch_cnt, support_features, new_xyz, new_xyz_batch_cnt, num_grid_x, num_grid_y, num_grid_z,
+                       max_neighbour_distance, num_c_out_each_grid, nsample, neighbor_type):
+    """`voxel_random_choice` vector pooling in one launch (seevcn entry; the reference's vector_pool_wrapper sizes grouped_idxs on the host
+    and is re-run until it fits).  -> choice (M, G) int32 global support row or -1, point_cnt (M, G) int32, new_local_xyz (M, 3 G),
+    new_features (M, G * c_each); all final, nothing is read back."""
+    lib = _lib.load()
+    _lib.require_cuda(support_xyz, support_features, new_xyz)
+    assert support_xyz.dtype == support_features.dtype == new_xyz.dtype == torch.float32
+    qs, qc = _starts(new_xyz_batch_cnt)
+    ps, pc = _starts(xyz_batch_cnt)
+    M, N = int(new_xyz.shape[0]), int(support_xyz.shape[0])
+    G = int(num_grid_x) * int(num_grid_y) * int(num_grid_z)
+    c_in, c_each = int(support_features.shape[1]), int(num_c_out_each_grid)
+    dev = new_xyz.device
+    choice = torch.empty((M, G), dtype=torch.int32, device=dev)
+    point_cnt = torch.empty((M, G), dtype=torch.int32, device=dev)
+    new_local_xyz = torch.empty((M, 3 * G), dtype=torch.float32, device=dev)
+    new_features = torch.empty((M, G * c_each), dtype=torch.float32, device=dev)
+    rc = lib.sv_vector_pool_choice(int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(support_xyz),
+                                   _lib.ptr(support_features), _lib.ptr(ps), _lib.ptr(pc), c_in, c_each, int(num_grid_x), int(num_grid_y),
+                                   int(num_grid_z), float(max_neighbour_distance), int(nsample), int(neighbor_type), _lib.ptr(choice),
+                                   _lib.ptr(point_cnt), _lib.ptr(new_local_xyz), _lib.ptr(new_features), _lib.stream())
+    _lib.check(rc, "sv_vector_pool_choice")
+    return choice, point_cnt, new_local_xyz, new_features
+
+
+def vector_pool_choice_grad(grad_new_features, choice, point_cnt, N, num_c_in):
+    """grad_new_features (M, G * c_each) -> grad_support_features (N, c_in), every element written."""
+    lib = _lib.load()
+    _lib.require_cuda(grad_new_features, choice, point_cnt)
+    M, G = int(choice.shape[0]), int(choice.shape[1])
+    c_each = int(grad_new_features.shape[1]) // G
+    grad_support = torch.empty((int(N), int(num_c_in)), dtype=torch.float32, device=grad_new_features.device)
+    if ordered.ordered_gradients():
+        nbytes = lib.sv_vector_pool_choice_grad_ordered_scratch_bytes(M, int(N), G)
+        scratch = _lib.workspace.scratch("vector_pool_grad_ordered", nbytes, grad_new_features.device)
+        rc = lib.sv_vector_pool_choice_grad_ordered(M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice),
+                                                    _lib.ptr(point_cnt), _lib.ptr(scratch), _lib.ptr(grad_support), _lib.stream())
+        _lib.check(rc, "sv_vector_pool_choice_grad_ordered")
+        ordered.count_call("vector_pool")
+        return grad_support
+    rc = lib.sv_vector_pool_choice_grad(M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice), _lib.ptr(point_cnt),
+                                        _lib.ptr(grad_support), _lib.stream())
+    _lib.check(rc, "sv_vector_pool_choice_grad")
+    return grad_support
+
+
+def vector_pool_three_nn(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt, max_neighbour_distance, nsample,
+                         neighbor_type):
+    """The local neighbour list and the 3-NN of every grid centre over it in one launch (seevcn entry; the reference's two wrappers pass a
+    host-sized stack_neighbor_idxs between them).  -> idx (M, G, 3) int32 global rows or -1, dist2 (M, G, 3) (+inf where idx is -1)."""
+    lib = _lib.load()
+    _lib.require_cuda(support_xyz, new_xyz, new_xyz_grid_centers)
+    assert support_xyz.dtype == new_xyz.dtype == new_xyz_grid_centers.dtype == torch.float32
+    qs, qc = _starts(new_xyz_batch_cnt)
+    ps, pc = _starts(xyz_batch_cnt)
+    M, N, G = int(new_xyz.shape[0]), int(support_xyz.shape[0]), int(new_xyz_grid_centers.shape[1])
+    idx = torch.empty((M, G, 3), dtype=torch.int32, device=new_xyz.device)
+    dist2 = torch.empty((M, G, 3), dtype=torch.float32, device=new_xyz.device)
+    rc = lib.sv_vector_pool_three_nn(int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(new_xyz_grid_centers), _lib.ptr(qs), _lib.ptr(qc),
+                                     _lib.ptr(support_xyz), _lib.ptr(ps), _lib.ptr(pc), G, float(max_neighbour_distance), int(nsample),
+                                     int(neighbor_type), _lib.ptr(idx), _lib.ptr(dist2), _lib.stream())
+    _lib.check(rc, "sv_vector_pool_three_nn")
+    return idx, dist2
+
+
+def _raising(name, why):
     def stub(*args, **kwargs):
-        raise NotImplementedError(f"pointnet2_stack_cuda.{name} is outside the SEE-VCN hot path (SURVEY.md 2: PV-RCNN++ / PartA2 / PointRCNN-style "
-                                  f"heads) and not built; see INTEGRATION.md 'Unsupported surface'")
+        raise NotImplementedError(f"pointnet2_stack_cuda.{name} is not built: {why}; see INTEGRATION.md 'Unsupported surface'")
     stub.__name__ = name
     return stub
 
 
-# names the reference's extension exports (src/pointnet2_api.cpp:12-31) that no SEE-VCN configuration reaches
-three_nn_wrapper = _outside_hot_path("three_nn_wrapper")
-three_interpolate_wrapper = _outside_hot_path("three_interpolate_wrapper")
-three_interpolate_grad_wrapper = _outside_hot_path("three_interpolate_grad_wrapper")
-vector_pool_wrapper = _outside_hot_path("vector_pool_wrapper")
-vector_pool_grad_wrapper = _outside_hot_path("vector_pool_grad_wrapper")
-query_stacked_local_neighbor_idxs_wrapper_stack = _outside_hot_path("query_stacked_local_neighbor_idxs_wrapper_stack")
-query_three_nn_by_stacked_local_idxs_wrapper_stack = _outside_hot_path("query_three_nn_by_stacked_local_idxs_wrapper_stack")
+# Names the reference's extension exports (src/pointnet2_api.cpp:12-31) that stay raising.  The vector-pool four take a host-sized buffer and
+# return a count for the caller's retry loop -- the contract vector_pool_choice / vector_pool_three_nn above remove; the stacked three_nn
+# belongs to StackPointnetFPModule, which no configuration reaches.
+_VP = "its host-sized buffer and returned count are replaced by pointnet2_stack_cuda.vector_pool_choice / vector_pool_three_nn"
+three_nn_wrapper = _raising("three_nn_wrapper", "the stacked three_nn (StackPointnetFPModule) is outside every built configuration")
+vector_pool_wrapper = _raising("vector_pool_wrapper", _VP)
+vector_pool_grad_wrapper = _raising("vector_pool_grad_wrapper", _VP)
+query_stacked_local_neighbor_idxs_wrapper_stack = _raising("query_stacked_local_neighbor_idxs_wrapper_stack", _VP)
+query_three_nn_by_stacked_local_idxs_wrapper_stack = _raising("query_three_nn_by_stacked_local_idxs_wrapper_stack", _VP)

@@ -1,5 +1,5 @@
 """Autograd functions / modules with the reference's names and call signatures
-(detector3d/pcdet/ops/pointnet2/pointnet2_stack/pointnet2_utils.py:8-188)."""
+(detector3d/pcdet/ops/pointnet2/pointnet2_stack/pointnet2_utils.py:8-188, 264-453)."""
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -175,3 +175,82 @@ class FarthestPointSampling(Function):
 
 farthest_point_sample = furthest_point_sample = FarthestPointSampling.apply
 stack_farthest_point_sample = pointnet2.stack_farthest_point_sampling
+
+
+class ThreeInterpolate(Function):
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        """features (M1 + M2 ..., C), idx / weight (N1 + N2 ..., 3) -> (N1 + N2 ..., C)   (reference pointnet2_utils.py:264-303)"""
+        assert idx.shape[0] == weight.shape[0] and idx.shape[1] == weight.shape[1] == 3
+        idx, weight = idx.contiguous(), weight.contiguous()
+        ctx.three_interpolate_for_backward = (idx, weight, features.shape[0])
+        output = torch.empty((idx.shape[0], features.shape[1]), dtype=torch.float32, device=features.device)
+        pointnet2.three_interpolate_wrapper(features.contiguous(), idx, weight, output)
+        return output
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, weight, M = ctx.three_interpolate_for_backward
+        grad_features = torch.empty((M, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
+        pointnet2.three_interpolate_grad_wrapper(grad_out.contiguous(), idx, weight, grad_features)
+        return grad_features, None, None
+
+
+three_interpolate = ThreeInterpolate.apply
+
+
+class ThreeNNForVectorPoolByTwoStep(Function):
+    @staticmethod
+    def forward(ctx, support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt,
+                max_neighbour_distance, nsample, neighbor_type, avg_length_of_neighbor_idxs, num_total_grids,
+                neighbor_distance_multiplier):
+        """Same arguments as the reference (pointnet2_utils.py:306-358) -> (dist (M, G, 3), idx (M, G, 3) int32, avg_length_of_neighbor_idxs).
+        One launch keeps each query's neighbour list on the chip, so nothing is counted, read back or retried: avg_length_of_neighbor_idxs
+        is returned as it came."""
+        assert new_xyz_grid_centers.shape[1] == num_total_grids
+        idx, dist2 = pointnet2.vector_pool_three_nn(
+            support_xyz.contiguous(), xyz_batch_cnt, new_xyz.contiguous(), new_xyz_grid_centers.contiguous(), new_xyz_batch_cnt,
+            max_neighbour_distance * neighbor_distance_multiplier, nsample, neighbor_type)
+        ctx.mark_non_differentiable(idx)
+        return torch.sqrt(dist2), idx, avg_length_of_neighbor_idxs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) * 11
+
+
+three_nn_for_vector_pool_by_two_step = ThreeNNForVectorPoolByTwoStep.apply
+
+
+class VectorPoolWithVoxelQuery(Function):
+    @staticmethod
+    def forward(ctx, support_xyz, xyz_batch_cnt, support_features, new_xyz, new_xyz_batch_cnt, num_grid_x, num_grid_y, num_grid_z,
+                max_neighbour_distance, num_c_out_each_grid, use_xyz, num_mean_points_per_grid=100, nsample=-1, neighbor_type=0,
+                pooling_type=0):
+        """Same arguments and the same four returns as the reference (pointnet2_utils.py:361-453): new_features (M, G * c_each),
+        new_local_xyz (M, 3 G), num_mean_points_per_grid (returned as it came: nothing is counted), point_cnt_of_grid (M, G).
+        Only pooling_type 1 (`voxel_random_choice`) is built; with one row per cell the reference's division by the count is a no-op."""
+        assert support_xyz.is_contiguous() and support_features.is_contiguous() and xyz_batch_cnt.is_contiguous()
+        assert new_xyz.is_contiguous() and new_xyz_batch_cnt.is_contiguous()
+        if pooling_type != 1:
+            raise NotImplementedError("vector_pool_with_voxel_query_op: only pooling_type 1 (voxel_random_choice) is built; no configuration "
+                                      "selects voxel_avg_pool")
+        N, num_c_in = support_features.shape
+        assert num_c_in % num_c_out_each_grid == 0, \
+            f'the input channels ({num_c_in}) should be an integral multiple of num_c_out_each_grid({num_c_out_each_grid})'
+        choice, point_cnt_of_grid, new_local_xyz, new_features = pointnet2.vector_pool_choice(
+            support_xyz, xyz_batch_cnt, support_features, new_xyz, new_xyz_batch_cnt, num_grid_x, num_grid_y, num_grid_z,
+            max_neighbour_distance, num_c_out_each_grid, nsample, neighbor_type)
+        num_mean_points_per_grid = torch.Tensor([num_mean_points_per_grid]).int()
+        ctx.vector_pool_for_backward = (point_cnt_of_grid, choice, N, num_c_in)
+        ctx.mark_non_differentiable(new_local_xyz, num_mean_points_per_grid, point_cnt_of_grid)
+        return new_features, new_local_xyz, num_mean_points_per_grid, point_cnt_of_grid
+
+    @staticmethod
+    def backward(ctx, grad_new_features, grad_local_xyz, grad_num_cum_sum, grad_point_cnt_of_grid):
+        point_cnt_of_grid, choice, N, num_c_in = ctx.vector_pool_for_backward
+        grad_support_features = pointnet2.vector_pool_choice_grad(grad_new_features.contiguous(), choice, point_cnt_of_grid, N, num_c_in)
+        return (None, None, grad_support_features) + (None,) * 12
+
+
+vector_pool_with_voxel_query_op = VectorPoolWithVoxelQuery.apply
