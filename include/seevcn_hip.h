@@ -434,6 +434,40 @@ int sv_fps_bucket_applies(int batch, int max_n, int m);
 size_t sv_fps_bucket_scratch_bytes(int batch, int max_n);
 int sv_farthest_point_sampling_bucketed(const float* xyz, const int32_t* xyz_batch_start, const int32_t* xyz_batch_cnt, int batch, int fixed_n, int max_n,
                                         int m, void* scratch, int32_t* idx, void* stream);
+/* Sectorized proposal-centric keypoint sampling of PV-RCNN++ and its RoI neighbour filter for a whole batch (csrc/spc_sampling.hip): three
+ * launches, nothing read back.
+ * sv_spc_select replaces sample_points_with_roi (backbones_3d/pfe/voxel_set_abstraction.py:45-75) and the sector expression of sector_fps (:88-90)
+ * for all scenes at once: per point the nearest RoI centre by dist = sqrtf(dx*dx + dy*dy + dz*dz) (fp32, summed left to right, correctly rounded
+ * sqrt; lowest RoI index among equal dist), selected iff dist < sqrtf((l/2)^2 + (w/2)^2 + (h/2)^2) + radius of THAT RoI.  rois (batch, num_rois,
+ * roi_stride floats a row, [x, y, z, l, w, h, ...]); all-zero rows take part like any other, as in the reference.  sector (rows of xyz) int32:
+ * -1 not selected, else floorf((atan2f(y, x) + fp32(pi)) / fp32(2 pi / num_sectors)) clamped to [0, num_sectors] (num_sectors itself: selected, in no
+ * sector); the axis cases y == +-0 / x == 0 take their IEEE values whatever the device atan2f returns.  num_sectors == 0: 0 selected / -1 not (the
+ * neighbour filter's mask).  max_n: the host's estimate of the largest scene, it sizes the grid only (every row of every scene is written whatever it is);
+ * num_rois <= 2048, num_sectors <= 63. */
+int sv_spc_select(const float* xyz, const int32_t* xyz_batch_start, const int32_t* xyz_batch_cnt, int batch, int max_n, const float* rois,
+                  int num_rois, int roi_stride, float radius, int num_sectors, int32_t* sector, void* stream);
+/* The per-sector masks, .sum().item() reads, quotas and host-built count tensors of sector_fps (voxel_set_abstraction.py:91-113), one workgroup per
+ * scene, stable and without atomics.  order (rows of xyz) int32: the GLOBAL rows of every (scene, sector) segment in ascending row order, a scene's
+ * segments inside the scene's own row range, sectors ascending, the selected rows of no sector behind them; rows of `order` outside the segments
+ * are not written.  Tables of batch * num_sectors entries, scene-major: seg_start (first position in `order`), seg_cnt, seg_m = min(cnt, ceil(cnt /
+ * n_sel * num_keypoints)) in float64 with n_sel = all selected rows of the scene, seg_out_start (scene b's picks start at b * (num_keypoints +
+ * num_sectors), its segments follow each other); kp_cnt (batch) = the scene's sum of seg_m.  The reference's fallbacks: a scene without a selected row
+ * samples its row 0 alone (segment of 1 row in that row's sector slot, quota 1 -- or slot 0 with quota num_keypoints when that row is in no sector,
+ * :73, :105-108); a scene whose selected rows are all in no sector is ONE segment (slot 0) of all of them with quota num_keypoints.  xyz is read for
+ * the row-0 fallback only.  num_sectors == 0 (tables of `batch` entries): seg_start / seg_cnt / kp_cnt describe the selected rows, seg_m and
+ * seg_out_start are 0. */
+int sv_spc_partition(const int32_t* sector, const float* xyz, const int32_t* xyz_batch_start, const int32_t* xyz_batch_cnt, int batch,
+                     int num_keypoints, int num_sectors, int32_t* order, int32_t* seg_start, int32_t* seg_cnt, int32_t* seg_m,
+                     int32_t* seg_out_start, int32_t* kp_cnt, void* stream);
+/* stack_farthest_point_sampling_wrapper (src/sampling.cpp, kernel sampling_gpu.cu:188-319) with the segment table on the device: one workgroup per
+ * segment samples seg_m[g] of the seg_cnt[g] points xyz[order[seg_start[g] + k]] (order NULL: xyz[seg_start[g] + k]) and writes their GLOBAL rows to
+ * idx[seg_out_start[g] ...].  Index-exact with the reference kernel, whose reduction always runs over 1024 slots; seg_m > seg_cnt is legal (the rule
+ * goes on picking once every running distance is 0).  max_n >= the largest segment (a larger one is left unwritten); temp (n_rows floats) is needed
+ * when max_n > 24576, may be NULL otherwise.  A segment with seg_cnt <= 0 or seg_m <= 0, or one that does not fit n_rows / idx_len, touches no
+ * memory. */
+int sv_stack_farthest_point_sampling_ragged(const float* xyz, int64_t n_rows, const int32_t* order, const int32_t* seg_start, const int32_t* seg_cnt,
+                                            const int32_t* seg_m, const int32_t* seg_out_start, int num_segments, int max_n, float* temp, int32_t* idx,
+                                            int64_t idx_len, void* stream);
 /* ball_query_wrapper(B, M, radius, nsample, new_xyz, new_xyz_batch_cnt, xyz, xyz_batch_cnt, idx) (src/ball_query.cpp:31-47,
  * kernel ball_query_gpu.cu:16-66): idx (M,nsample) scene-local indices of the first nsample points with d^2 < r^2 in index
  * order, padded with the first hit; idx[m][0] = -1 for an empty ball. */

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "wave.h"
+#include "fps.h"
 #include "inverse_lists.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -22,18 +23,7 @@
 //   stride class) through a power-of-two tree that keeps the LOWER slot on ties (sampling_gpu.cu:16-21,55-134),
 //   i.e. among equal maxima the winner minimises (bitreverse(k mod T), k div T), T = 2^floor(log2 n) <= 1024.
 // ------------------------------------------------------------------------------------------------
-constexpr int FPS_THREADS = 512;   // 8 waves = 2 per SIMD: 256 VGPRs per lane, so 48 points per thread stay in registers (1024 threads
-                                   // capped the kernel at 128 VGPRs: the 16- and 24-point variants spilled ~700 / ~2500 registers to scratch
-                                   // and a round took 39 us instead of ~2)
-constexpr int FPS_MAXP = 48;       // points per thread held in registers -> n <= 24576 on the register path
-
-__device__ __forceinline__ unsigned long long fps_key(float d, int k, int log2t) {
-  // larger key wins: distance first (non-negative floats order as their bit patterns), then the tie rule
-  const unsigned int lo = (unsigned int)k & ((1u << log2t) - 1u);
-  const unsigned int rev = log2t ? (__brev(lo) >> (32 - log2t)) : 0u;
-  const unsigned int tie = (rev << (31 - log2t)) | ((unsigned int)k >> log2t);   // smaller tie = preferred
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0x7FFFFFFFu - tie);
-}
+// FPS_THREADS, FPS_MAXP and fps_key: fps.h (shared with the ragged per-segment sampler of spc_sampling.hip)
 
 // one workgroup per scene; xyz (n,3) of the scene, idx (m) output (scene-local indices, + start when add_offset)
 template <int P>

@@ -105,7 +105,7 @@ def _vector_pool(kind, reduced, post_msg, groups, **extra):
 
 
 # detector3d/tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml:76-140, 160-179 (values as data): the vector-pool SA_LAYERs of the PFE and the
-# ROI_GRID_POOL of the PVRCNNHead.  FILTER_NEIGHBOR_WITH_ROI / RADIUS_OF_NEIGHBOR_WITH_ROI are the yaml's; nothing built reads them yet.
+# ROI_GRID_POOL of the PVRCNNHead.  FILTER_NEIGHBOR_WITH_ROI / RADIUS_OF_NEIGHBOR_WITH_ROI: VoxelSetAbstraction's RoI neighbour filter.
 PVRCNNPP_SA_LAYER = dict(
     raw_points=_vector_pool('local_interpolation', 2, 32, [((2, 2, 2), 0.2, -1, 32), ((3, 3, 3), 0.4, -1, 32)],
                             FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=2.4),
@@ -280,3 +280,39 @@ def pointrcnn_model_cfg(**kw):
     backbone, point_head, roi_head = pointrcnn_cfg(**kw)
     pp = dict(SECOND_POST_PROCESSING, NMS_CONFIG=dict(SECOND_POST_PROCESSING['NMS_CONFIG'], NMS_THRESH=0.1))
     return dict(NAME='PointRCNN', BACKBONE_3D=backbone, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)
+
+
+# detector3d/tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml:1-256 (values as data): PV-RCNN++ -- CenterHead proposals, SPC keypoints, vector-pool
+# aggregation in the PFE and in the RoI grid pooling.  Range and voxel size of cfgs/dataset_configs/waymo_dataset.yaml are DA_RANGE / DA_VOXEL.
+WAYMO_CLASS_NAMES = ['Vehicle', 'Pedestrian', 'Cyclist']
+PVRCNNPP_CENTER_HEAD = dict(
+    NAME='CenterHead', CLASS_AGNOSTIC=False, CLASS_NAMES_EACH_HEAD=[['Vehicle', 'Pedestrian', 'Cyclist']],
+    SHARED_CONV_CHANNEL=64, USE_BIAS_BEFORE_NORM=True, NUM_HM_CONV=2,
+    SEPARATE_HEAD_CFG=dict(HEAD_ORDER=['center', 'center_z', 'dim', 'rot'],
+                           HEAD_DICT=dict(center=dict(out_channels=2, num_conv=2), center_z=dict(out_channels=1, num_conv=2),
+                                          dim=dict(out_channels=3, num_conv=2), rot=dict(out_channels=2, num_conv=2))),
+    TARGET_ASSIGNER_CONFIG=dict(FEATURE_MAP_STRIDE=8, NUM_MAX_OBJS=500, GAUSSIAN_OVERLAP=0.1, MIN_RADIUS=2),
+    LOSS_CONFIG=dict(LOSS_WEIGHTS=dict(cls_weight=1.0, loc_weight=2.0, code_weights=[1.0] * 8)),
+    POST_PROCESSING=dict(SCORE_THRESH=0.1, POST_CENTER_LIMIT_RANGE=[-75.2, -75.2, -2, 75.2, 75.2, 4], MAX_OBJ_PER_SAMPLE=500,
+                         NMS_CONFIG=dict(NMS_TYPE='nms_gpu', NMS_THRESH=0.7, NMS_PRE_MAXSIZE=4096, NMS_POST_MAXSIZE=500)))
+
+
+def pvrcnnpp_cfg(num_keypoints=4096, features_source=('bev', 'x_conv3', 'x_conv4', 'raw_points'), roi_per_image=128, nms_post_train=512,
+                 nms_pre_train=9000, dp_ratio=0.3):
+    """PFE / POINT_HEAD / ROI_HEAD sections of waymo_models/pv_rcnn_plusplus.yaml:72-241; the size keywords as in pvrcnn_cfg."""
+    pfe = dict(NAME='VoxelSetAbstraction', POINT_SOURCE='raw_points', NUM_KEYPOINTS=num_keypoints, NUM_OUTPUT_FEATURES=90, SAMPLE_METHOD='SPC',
+               SPC_SAMPLING=dict(NUM_SECTORS=6, SAMPLE_RADIUS_WITH_ROI=1.6), FEATURES_SOURCE=list(features_source),
+               SA_LAYER={k: dict(v) for k, v in PVRCNNPP_SA_LAYER.items()})
+    _, point_head, roi_head = pvrcnn_cfg(roi_per_image=roi_per_image, nms_post_train=nms_post_train, nms_pre_train=nms_pre_train, dp_ratio=dp_ratio)
+    roi_head['NMS_CONFIG']['TEST']['SCORE_THRESH'] = 0.1
+    roi_head['ROI_GRID_POOL'] = dict(PVRCNNPP_ROI_GRID_POOL)
+    return pfe, point_head, roi_head
+
+
+def pvrcnnpp_model_cfg(dynamic_vfe=False, **kw):
+    pfe, point_head, roi_head = pvrcnnpp_cfg(**kw)
+    pp = dict(RECALL_THRESH_LIST=[0.3, 0.5, 0.7], SCORE_THRESH=0.1, OUTPUT_RAW_SCORE=False, EVAL_METRIC='waymo',
+              NMS_CONFIG=dict(MULTI_CLASSES_NMS=False, NMS_TYPE='nms_gpu', NMS_THRESH=0.7, NMS_PRE_MAXSIZE=4096, NMS_POST_MAXSIZE=500))
+    return dict(NAME='PVRCNNPlusPlus', VFE=dict(NAME='DynMeanVFE' if dynamic_vfe else 'MeanVFE'), BACKBONE_3D=dict(NAME='VoxelBackBone8x'),
+                MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=SECOND_BACKBONE_2D, DENSE_HEAD=PVRCNNPP_CENTER_HEAD,
+                PFE=pfe, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)

@@ -4,6 +4,7 @@ from .detector3d_template import Detector3DTemplate
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
+from .pv_rcnn_plusplus import PVRCNNPlusPlus
 from .second_net import SECONDNet
 from .second_net_iou import SECONDNetIoU
 from .voxel_rcnn import VoxelRCNN
@@ -19,6 +20,7 @@ __all__ = {
     'VoxelRCNN': VoxelRCNN,
     'PartA2Net': PartA2Net,
     'PointRCNN': PointRCNN,
+    'PVRCNNPlusPlus': PVRCNNPlusPlus,
 }
 
 

@@ -203,6 +203,59 @@ def stack_farthest_point_sampling_async(points, xyz_batch_cnt, npoint, max_n):
     return FpsHandle(idx, err, stream, lambda: launch(1))
 
 
+def spc_select(xyz, xyz_batch_cnt, rois, radius, num_sectors, max_n=None):
+    """sample_points_with_roi + the sector expression of sector_fps for every scene in one launch (seevcn extension; voxel_set_abstraction.py:45-75,
+    88-90).  xyz (N, 3) stacked, rois (B, M, 7 + C) -> sector (N,) int32: -1 not selected | 0..num_sectors; num_sectors == 0: 0 selected | -1.
+    max_n: an upper bound of the largest scene known on the host (None: N)."""
+    lib = _lib.load()
+    _lib.require_cuda(xyz, rois)
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and rois.dim() == 3
+    starts, cnt = _starts(xyz_batch_cnt)
+    rois = rois.contiguous().float()
+    assert rois.shape[0] == cnt.shape[0], "one set of RoIs per scene"
+    sector = torch.empty((xyz.shape[0],), dtype=torch.int32, device=xyz.device)
+    rc = lib.sv_spc_select(_lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), cnt.shape[0], int(xyz.shape[0] if max_n is None else max_n), _lib.ptr(rois),
+                           rois.shape[1], rois.shape[2], float(radius), int(num_sectors), _lib.ptr(sector), _lib.stream())
+    _lib.check(rc, "sv_spc_select")
+    return sector
+
+
+def spc_partition(sector, xyz, xyz_batch_cnt, num_keypoints, num_sectors):
+    """The stable (scene, sector) row lists, quotas and output offsets of sector_fps (voxel_set_abstraction.py:91-113) for every scene in one launch
+    -> (order (N,), tables (5, B * max(S, 1)) int32 rows seg_start / seg_cnt / seg_m / seg_out_start / kp_cnt -- kp_cnt fills the first B entries of
+    its row).  Nothing is read back."""
+    lib = _lib.load()
+    _lib.require_cuda(sector)
+    assert sector.dtype == torch.int32 and sector.is_contiguous()
+    starts, cnt = _starts(xyz_batch_cnt)
+    B, nseg = cnt.shape[0], cnt.shape[0] * max(int(num_sectors), 1)
+    order = torch.empty((sector.shape[0],), dtype=torch.int32, device=sector.device)
+    tables = torch.empty((5, nseg), dtype=torch.int32, device=sector.device)      # the kernel writes every entry it defines
+    rc = lib.sv_spc_partition(_lib.ptr(sector), _lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), B, int(num_keypoints), int(num_sectors), _lib.ptr(order),
+                              _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.ptr(tables[2]), _lib.ptr(tables[3]), _lib.ptr(tables[4]), _lib.stream())
+    _lib.check(rc, "sv_spc_partition")
+    return order, tables
+
+
+def stack_farthest_point_sampling_ragged(xyz, order, seg_start, seg_cnt, seg_m, seg_out_start, idx, max_n=None):
+    """One workgroup per segment of the device tables; GLOBAL rows into idx (int32, caller-allocated) at seg_out_start (stack_farthest_point_sampling_
+    wrapper, src/sampling.cpp, with the counts left on the device).  order None: segment g is the rows seg_start[g] ... of xyz.  max_n: an upper bound
+    of the largest segment known on the host (None: N)."""
+    lib = _lib.load()
+    _lib.require_cuda(xyz, idx)
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and idx.dtype == torch.int32
+    for t in (order, seg_start, seg_cnt, seg_m, seg_out_start):
+        assert t is None or t.dtype == torch.int32
+    N = xyz.shape[0]
+    max_n = N if max_n is None else min(int(max_n), N)
+    temp = torch.empty((N,), dtype=torch.float32, device=xyz.device) if max_n > 24576 else None
+    rc = lib.sv_stack_farthest_point_sampling_ragged(_lib.ptr(xyz), N, _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(seg_cnt), _lib.ptr(seg_m),
+                                                     _lib.ptr(seg_out_start), seg_cnt.shape[0], max_n, _lib.ptr(temp), _lib.ptr(idx), idx.numel(),
+                                                     _lib.stream())
+    _lib.check(rc, "sv_stack_farthest_point_sampling_ragged")
+    return idx
+
+
 def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, point_indices, idx):
     """src/voxel_query.cpp: new_coords (M, 4) int32 [b, z, y, x], point_indices (B, R1, R2, R3) int32, idx (M, nsample) int32 zero-filled by the caller."""
     lib = _lib.load()

@@ -1,5 +1,7 @@
 """Autograd functions / modules with the reference's names and call signatures
 (detector3d/pcdet/ops/pointnet2/pointnet2_stack/pointnet2_utils.py:8-188, 264-453)."""
+import numbers
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -174,7 +176,44 @@ class FarthestPointSampling(Function):
 
 
 farthest_point_sample = furthest_point_sample = FarthestPointSampling.apply
-stack_farthest_point_sample = pointnet2.stack_farthest_point_sampling
+
+
+class StackFarthestPointSampling(Function):
+    @staticmethod
+    def forward(ctx, xyz, xyz_batch_cnt, npoint):
+        """xyz (N1 + N2 + ..., 3), xyz_batch_cnt [N1, N2, ...], npoint int | list | tensor [M1, M2, ...] -> (M1 + M2 + ...) int32 GLOBAL rows
+        (reference pointnet2_utils.py:191-227).  One launch over the device counts; the output is sized from a host npoint, or -- a device tensor
+        being what the reference's sector_fps hands over -- from one read of its sum."""
+        assert xyz.is_contiguous() and xyz.shape[1] == 3
+        batch_size = xyz_batch_cnt.shape[0]
+        dev = xyz.device
+        if not torch.is_tensor(npoint):
+            if isinstance(npoint, numbers.Integral):
+                npoint = [int(npoint)] * batch_size
+            total = int(sum(npoint))
+            npoint = torch.tensor(npoint, dtype=torch.int32).to(dev, non_blocking=True)
+        else:
+            npoint = npoint.to(device=dev, dtype=torch.int32).contiguous()
+            total = int(npoint.sum().item())
+        assert npoint.shape[0] == batch_size
+        cnt = xyz_batch_cnt.to(device=dev, dtype=torch.int32).contiguous()
+        start = (torch.cumsum(cnt, 0, dtype=torch.int32) - cnt).contiguous()
+        out_start = (torch.cumsum(npoint, 0, dtype=torch.int32) - npoint).contiguous()
+        output = torch.empty((total,), dtype=torch.int32, device=dev)
+        pointnet2.stack_farthest_point_sampling_ragged(xyz, None, start, cnt, npoint, out_start, output)
+        return output
+
+    @staticmethod
+    def backward(xyz, a=None):
+        return None, None, None
+
+
+def stack_farthest_point_sample(points, xyz_batch_cnt, npoint, max_n=None, bucketed=True):
+    """An int npoint: the (batch, npoint) table of the seevcn extension (pointnet2_stack_cuda.stack_farthest_point_sampling, what VoxelSetAbstraction's
+    FPS route uses).  A list or tensor npoint: the reference's StackFarthestPointSampling, flat (sum npoint)."""
+    if isinstance(npoint, numbers.Integral):                       # Python and numpy integers alike
+        return pointnet2.stack_farthest_point_sampling(points, xyz_batch_cnt, npoint, max_n, bucketed)
+    return StackFarthestPointSampling.apply(points, xyz_batch_cnt, npoint)
 
 
 class ThreeInterpolate(Function):
