@@ -697,6 +697,15 @@ int sv_nms(const float* boxes, int n, float thresh, int normal, void* scratch, i
 /* The same, stopping once max_keep boxes are kept: keep[0..*num_out) is the prefix sv_nms would return, *num_out = min(kept, max_keep)
  * (seevcn extension for callers that truncate to NMS_POST_MAXSIZE, model_nms_utils.py:21). */
 int sv_nms_prefix(const float* boxes, int n, float thresh, int normal, int max_keep, void* scratch, int64_t* keep, int32_t* num_out, void* stream);
+/* Class-wise NMS of a whole batch (multi_classes_nms, detector3d/pcdet/models/model_utils/model_nms_utils.py:28-66: one NMS per scene x head x
+ * class) as ONE launch pair: `num_segments` independent box sets, segment s = rows [0, seg_count[s]) of boxes[s] (seg_stride rows of 7 floats,
+ * already in descending score order); rows at or beyond seg_count[s] are padding, never read.  For every segment the result is
+ * sv_nms_prefix(boxes[s], seg_count[s], thresh, normal, max_keep): keep[s] (max_keep slots) holds indices LOCAL to the segment in score order,
+ * num_out[s] = min(survivors, max_keep).  seg_count and num_out are DEVICE arrays; no count is read on the host.  seg_stride <= 4096,
+ * num_segments <= 65535.  scratch: num_segments * seg_stride * ceil(seg_stride / 64) * 8 bytes (the suppression mask words). */
+size_t sv_nms_segments_scratch_bytes(int num_segments, int seg_stride);
+int sv_nms_segments(const float* boxes, const int32_t* seg_count, int num_segments, int seg_stride, float thresh, int normal, int max_keep,
+                    void* scratch, int64_t* keep, int32_t* num_out, void* stream);
 /* points_in_boxes_gpu: boxes (B,T,7), pts (B,M,3) -> out (B,M) int32 index of the first box containing the point or -1 */
 int sv_points_in_boxes(const float* boxes, const float* pts, int batch, int num_boxes, int num_points, int32_t* out, void* stream);
 
@@ -717,6 +726,21 @@ int sv_assign_targets_axis_aligned(const float* anchors, int64_t num_anchors, in
                                    const int32_t* set_offset, const int32_t* set_class, const float* matched_thr,
                                    const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt, float* gt_max_scratch,
                                    int32_t* labels, float* reg_targets, float* reg_weights, void* stream);
+/* The same two for coded boxes and head-major anchors (AnchorHeadMulti; ResidualCoder with code_size 7 + E and encode_angle_by_sincos):
+ * anchors (A, 7+E), box_encodings (B, A, 7+sincos+E) -> out (B, A, 7+E).  sincos = 1: heading = atan2(t[7] + sin(ra), t[6] + cos(ra));
+ * extras = t + anchor extras.  dir_cls_preds may be NULL (no direction classifier).  E = 0, sincos = 0 gives sv_anchor_decode's bits. */
+int sv_anchor_decode_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, const float* box_encodings,
+                           const float* dir_cls_preds, int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out,
+                           void* stream);
+/* anchors (A, 7+E); gt_boxes (B, G, 8+E) [box7, extras, class] zero-padded; reg_targets (B, A, 7+sincos+E) (encode_torch: sincos = 1 codes the
+ * heading as cos(rg) - cos(ra), sin(rg) - sin(ra); extras gt - anchor).  set_major = 0: anchors in sv_assign_targets_axis_aligned's order,
+ * set_offset = prefix of slots per location.  set_major = 1: the multihead order (axis_aligned_target_assigner.py:69), every set's anchors one
+ * contiguous run [size, rot, z, y, x], runs concatenated set by set, set_offset = prefix of ANCHORS per set (anchors_per_location unused).
+ * G <= 256, A < 2^31.  E = 0, sincos = 0, set_major = 0 gives sv_assign_targets_axis_aligned's bits. */
+int sv_assign_targets_axis_aligned_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, int set_major,
+                                         int anchors_per_location, int num_sets, const int32_t* set_offset, const int32_t* set_class,
+                                         const float* matched_thr, const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt,
+                                         float* gt_max_scratch, int32_t* labels, float* reg_targets, float* reg_weights, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Hard voxelisation + pillar features (PointPillars path)

@@ -162,6 +162,8 @@ SIGNATURES = {
     "sv_nms_scratch_bytes": (c_sz, [c_i]),
     "sv_nms": (c_i, [c_p, c_i, c_f, c_i, c_p, c_p, c_p, c_p]),
     "sv_nms_prefix": (c_i, [c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "sv_nms_segments_scratch_bytes": (c_sz, [c_i, c_i]),
+    "sv_nms_segments": (c_i, [c_p, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
     "sv_points_in_boxes": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_voxelize_hard_scratch_bytes": (c_sz, [c_i, c_i64, c_i]),
     "sv_voxelize_hard": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
@@ -229,6 +231,8 @@ SIGNATURES = {
     "sv_run_ops_two_streams": (c_i, [c_p, c_i, c_p, c_p]),
     "sv_anchor_decode": (c_i, [c_p, c_i64, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p]),
     "sv_assign_targets_axis_aligned": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_anchor_decode_coded": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p]),
+    "sv_assign_targets_axis_aligned_coded": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -202,6 +202,178 @@ extern "C" int sv_assign_targets_axis_aligned(const float* anchors, int64_t num_
   return SV_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ coded boxes, head-major anchors
+// The multi-head anchor family (AnchorHeadMulti; nuScenes: ResidualCoder code_size 9 with the heading coded as cos/sin differences) needs
+// boxes of 7 + E numbers, encodings of 7 + sincos + E, and anchors laid out head-major.  With E = 0, sincos = 0, set_major = 0 the entries
+// below evaluate the expressions of k_anchor_decode / k_assign in the same order: the same bits.
+__global__ __launch_bounds__(256) void k_anchor_decode_coded(int64_t total, int64_t A, int E, int sincos, const float* __restrict__ anchors,
+                                                             const float* __restrict__ enc, const float* __restrict__ dir_logits, int num_bins,
+                                                             float dir_offset, float dir_limit_offset, float* __restrict__ out) {
+  const int bw = 7 + E, cw = 7 + sincos + E;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const float* an = anchors + (i % A) * bw;
+    const float* t = enc + i * cw;
+    const float xa = an[0], ya = an[1], za = an[2], dxa = an[3], dya = an[4], dza = an[5], ra = an[6];
+    const float diag = sqrtf(dxa * dxa + dya * dya);
+    float* o = out + i * bw;
+    o[0] = t[0] * diag + xa;
+    o[1] = t[1] * diag + ya;
+    o[2] = t[2] * dza + za;
+    o[3] = expf(t[3]) * dxa;
+    o[4] = expf(t[4]) * dya;
+    o[5] = expf(t[5]) * dza;
+    float rg = sincos ? atan2f(t[7] + sinf(ra), t[6] + cosf(ra)) : t[6] + ra;        // box_coder_utils.py:66-73
+    if (dir_logits) {
+      const float* d = dir_logits + i * num_bins;
+      int lab = 0;
+      float best = d[0];
+      for (int k = 1; k < num_bins; ++k)
+        if (d[k] > best) { best = d[k]; lab = k; }
+      const float period = 2.0f * PI_F / (float)num_bins;
+      const float val = rg - dir_offset;
+      const float rot = val - floorf(val / period + dir_limit_offset) * period;
+      rg = rot + dir_offset + period * (float)lab;
+    }
+    o[6] = rg;
+    for (int k = 0; k < E; ++k) o[7 + k] = t[7 + sincos + k] + an[7 + k];
+  }
+}
+
+extern "C" int sv_anchor_decode_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, const float* box_encodings,
+                                      const float* dir_cls_preds, int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out,
+                                      void* stream) {
+  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && num_extra >= 0 && (sincos == 0 || sincos == 1), "anchor_decode_coded: bad arguments");
+  const int64_t total = num_anchors * batch;
+  if (total == 0) return SV_OK;
+  SV_CHECK_ARG(anchors && box_encodings && out && (!dir_cls_preds || num_dir_bins >= 1), "anchor_decode_coded: null pointer");
+  hipLaunchKernelGGL(k_anchor_decode_coded, dim3(sv_grid_1d(total, 256)), dim3(256), 0, sv_stream(stream), total, num_anchors, num_extra, sincos,
+                     anchors, box_encodings, dir_cls_preds, num_dir_bins, dir_offset, dir_limit_offset, out);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+struct AssignCodedArgs {
+  AssignArgs a;                // anchors (A,7+E); gt (B,G,8+E) [box7, extras, class]; targets (B,A,7+sincos+E)
+  int E, sincos, set_major;    // set_major: set_offset is the prefix of ANCHORS per set (each set one contiguous run), else of slots per location
+};
+
+constexpr int AS_MAX_GT_CODED = 256;                            // 52 B of LDS per box: 13 KiB
+
+// the two passes of k_assign; the extras of a matched box are read from global memory (positives are few), so E is not bounded by LDS
+template <int PASS>
+__global__ __launch_bounds__(256) void k_assign_coded(AssignCodedArgs c) {
+  const AssignArgs& a = c.a;
+  __shared__ AlignedBox sg[AS_MAX_GT_CODED];
+  __shared__ int scls[AS_MAX_GT_CODED];
+  __shared__ float sgmax[AS_MAX_GT_CODED];
+  __shared__ float sraw[AS_MAX_GT_CODED][7];
+  const int b = blockIdx.y;
+  const int bw = 7 + c.E, gw = 8 + c.E, cw = 7 + c.sincos + c.E;
+  for (int g = threadIdx.x; g < a.G; g += blockDim.x) {
+    const float* p = a.gt + ((int64_t)b * a.G + g) * gw;
+    sg[g] = nearest_bev(p);
+    scls[g] = (int)p[gw - 1];
+    for (int k = 0; k < 7; ++k) sraw[g][k] = p[k];
+    if (PASS == 1) {
+      const float m = a.gt_max[(int64_t)b * a.G + g];
+      sgmax[g] = m == 0.f ? -1.f : m;
+    } else {
+      sgmax[g] = 0.f;
+    }
+  }
+  __syncthreads();
+  for (int64_t ai = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ai < a.A; ai += (int64_t)gridDim.x * blockDim.x) {
+    const float* an = a.anchors + ai * bw;
+    const int o_in_set = c.set_major ? (int)ai : (int)(ai % a.per_loc);
+    int s = 0;
+    while (s + 1 < a.num_sets && o_in_set >= a.set_offset[s + 1]) ++s;
+    const int cls = a.set_class[s];
+    const AlignedBox ab = nearest_bev(an);
+    float best = -1.f;
+    int arg = -1;
+    bool force = false;
+    for (int g = 0; g < a.G; ++g) {
+      if (scls[g] != cls) continue;
+      const float v = iou_aligned(ab, sg[g]);
+      if (PASS == 0) {
+        if (v > 0.f) atomicMax(reinterpret_cast<int*>(&sgmax[g]), __float_as_int(v));
+      } else {
+        if (v > best) { best = v; arg = g; }
+        force = force || (v == sgmax[g]);
+      }
+    }
+    if (PASS == 1) {
+      const int64_t o = (int64_t)b * a.A + ai;
+      int label;
+      if (arg < 0) {
+        label = 0;
+      } else {
+        const bool pos = best >= a.matched_thr[s];
+        label = (force || pos) ? cls : (best < a.unmatched_thr[s] ? 0 : -1);
+      }
+      a.labels[o] = label;
+      float* t = a.targets + o * cw;
+      if (label > 0) {
+        // ResidualCoder.encode_torch (box_coder_utils.py:13-46)
+        const float* gtb = sraw[arg];
+        const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
+        const float dxg = fmaxf(gtb[3], 1e-5f), dyg = fmaxf(gtb[4], 1e-5f), dzg = fmaxf(gtb[5], 1e-5f);
+        const float diag = sqrtf(dxa * dxa + dya * dya);
+        t[0] = (gtb[0] - an[0]) / diag;
+        t[1] = (gtb[1] - an[1]) / diag;
+        t[2] = (gtb[2] - an[2]) / dza;
+        t[3] = logf(dxg / dxa);
+        t[4] = logf(dyg / dya);
+        t[5] = logf(dzg / dza);
+        if (c.sincos) {
+          t[6] = cosf(gtb[6]) - cosf(an[6]);
+          t[7] = sinf(gtb[6]) - sinf(an[6]);
+        } else {
+          t[6] = gtb[6] - an[6];
+        }
+        const float* ge = a.gt + ((int64_t)b * a.G + arg) * gw + 7;
+        for (int k = 0; k < c.E; ++k) t[7 + c.sincos + k] = ge[k] - an[7 + k];
+        a.reg_weights[o] = 1.0f;
+      } else {
+        for (int k = 0; k < cw; ++k) t[k] = 0.f;
+        a.reg_weights[o] = 0.f;
+      }
+    }
+  }
+  if (PASS == 0) {
+    __syncthreads();
+    for (int g = threadIdx.x; g < a.G; g += blockDim.x)
+      if (sgmax[g] > 0.f) atomicMax(reinterpret_cast<int*>(&a.gt_max[(int64_t)b * a.G + g]), __float_as_int(sgmax[g]));
+  }
+}
+
+extern "C" int sv_assign_targets_axis_aligned_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, int set_major,
+                                                    int anchors_per_location, int num_sets, const int32_t* set_offset, const int32_t* set_class,
+                                                    const float* matched_thr, const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt,
+                                                    float* gt_max_scratch, int32_t* labels, float* reg_targets, float* reg_weights, void* stream) {
+  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && max_gt >= 0 && num_sets >= 1 && anchors_per_location >= 1 && num_extra >= 0 &&
+                   (sincos == 0 || sincos == 1) && (set_major == 0 || set_major == 1),
+               "assign_targets_coded: bad arguments");
+  SV_CHECK_ARG(max_gt <= AS_MAX_GT_CODED, "assign_targets_coded: at most %d ground-truth boxes per scene", AS_MAX_GT_CODED);
+  SV_CHECK_ARG(num_anchors < ((int64_t)1 << 31), "assign_targets_coded: anchor index exceeds int32");
+  if (num_anchors == 0 || batch == 0) return SV_OK;
+  SV_CHECK_ARG(anchors && set_offset && set_class && matched_thr && unmatched_thr && labels && reg_targets && reg_weights &&
+                   (max_gt == 0 || (gt_boxes && gt_max_scratch)),
+               "assign_targets_coded: null pointer");
+  hipStream_t st = sv_stream(stream);
+  AssignCodedArgs c{{anchors, gt_boxes, num_anchors, batch, max_gt, anchors_per_location, num_sets, set_offset, set_class, matched_thr, unmatched_thr,
+                     gt_max_scratch, labels, reg_targets, reg_weights},
+                    num_extra, sincos, set_major};
+  dim3 grid(sv_grid_1d(num_anchors, 256, 512), batch);
+  if (max_gt > 0) {
+    SV_HIP(hipMemsetAsync(gt_max_scratch, 0, (size_t)batch * max_gt * 4, st));
+    hipLaunchKernelGGL(k_assign_coded<0>, grid, dim3(256), 0, st, c);
+  }
+  hipLaunchKernelGGL(k_assign_coded<1>, grid, dim3(256), 0, st, c);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Bilinear interpolation of BEV features at keypoints (interpolate_from_bev_features + bilinear_interpolate_torch,
 // detector3d/pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:11-42,176-204).  The reference permutes every scene's

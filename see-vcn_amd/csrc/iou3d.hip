@@ -324,6 +324,121 @@ extern "C" int sv_nms_prefix(const float* boxes, int n, float thresh, int normal
   return SV_OK;
 }
 
+// ------------------------------------------------------------------ segmented NMS: S independent box sets in one launch pair
+// Class-wise NMS (model_nms_utils.py:28-66) is one greedy NMS per scene x head x class over at most NMS_PRE_MAXSIZE boxes: dozens of small box
+// sets per batch.  Here they are the segments of one (S, seg_stride, 7) block: the mask grid is (column block, row block, segment), the sweep
+// one single-wave workgroup per segment, all segments at once.  A segment's valid row count is read from device memory by both kernels; rows
+// at or beyond it are padding that neither kernel touches.
+constexpr int NMS_SEG_MAX_WORDS = 64;                          // seg_stride <= 4096: a row of the mask is at most one word per lane
+
+__device__ __forceinline__ int seg_rows(const int32_t* __restrict__ seg_count, int s, int seg_stride) {
+  return min(max(seg_count[s], 0), seg_stride);
+}
+
+// one wave per 64x64 tile of one segment, as k_nms_mask: lane = column box, one ballot word per row
+__global__ __launch_bounds__(64) void k_nms_seg_mask(const int32_t* __restrict__ seg_count, int seg_stride, float thresh, const float* __restrict__ boxes,
+                                                     unsigned long long* __restrict__ mask, int col_blocks, int normal) {
+  const int s = blockIdx.z, rb = blockIdx.y, cb = blockIdx.x;
+  const int n = seg_rows(seg_count, s, seg_stride);
+  if (cb < rb || cb * 64 >= n) return;                         // left of the diagonal, or beyond the segment's rows (cb >= rb here, so this covers rb * 64 >= n)
+  boxes += (int64_t)s * seg_stride * 7;
+  mask += (int64_t)s * seg_stride * col_blocks;
+  const int lane = threadIdx.x;
+  const int col = cb * 64 + lane;
+  const bool col_ok = col < n;
+  float cbox[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) cbox[k] = col_ok ? boxes[(int64_t)col * 7 + k] : 0.f;
+  const RBox c = make_rbox(cbox);
+  const int rows = min(64, n - rb * 64);
+  for (int r = 0; r < rows; ++r) {
+    const int row = rb * 64 + r;
+    float rbox[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) rbox[k] = boxes[(int64_t)row * 7 + k];   // wave-uniform address: one broadcast load
+    bool sup = false;
+    if (col_ok && col > row) sup = (normal ? iou_axis_aligned(rbox, cbox) : iou_bev(make_rbox(rbox), c)) > thresh;
+    const unsigned long long w = __ballot(sup);
+    if (lane == 0) mask[(int64_t)row * col_blocks + cb] = w;
+  }
+}
+
+// greedy sweep of one segment by one wave: the removal bitmap (<= 64 words) in LDS, lane j owns word j.  Per block of 64 boxes the diagonal
+// word of each row decides suppression inside the block (64 serial steps on registers), then the kept rows are OR-ed into the words of the
+// later blocks: 8 rows at a time, loaded unconditionally (row index clamped into the segment, unkept rows masked to 0) so that the 8 loads
+// are in flight together.  Stops at max_keep, reads the upper triangle only and only words below ceil(n / 64).
+__global__ __launch_bounds__(64) void k_nms_seg_sweep(const int32_t* __restrict__ seg_count, int seg_stride, const unsigned long long* __restrict__ mask,
+                                                      int col_blocks, int max_keep, int64_t* __restrict__ keep, int32_t* __restrict__ num_out) {
+  __shared__ unsigned long long remv[NMS_SEG_MAX_WORDS];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int n = seg_rows(seg_count, s, seg_stride);
+  const int nblk = (n + 63) / 64;                               // <= col_blocks <= 64
+  mask += (int64_t)s * seg_stride * col_blocks;
+  keep += (int64_t)s * max_keep;
+  remv[lane] = 0ull;
+  __syncthreads();
+  int kept_total = 0;
+  for (int nb = 0; nb < nblk && kept_total < max_keep; ++nb) {
+    const int rows = min(64, n - nb * 64);
+    unsigned long long cur = remv[nb];
+    const unsigned long long diag = lane < rows ? mask[(int64_t)(nb * 64 + lane) * col_blocks + nb] : 0ull;
+    unsigned long long keptbits = 0ull;
+    for (int r = 0; r < rows; ++r) {
+      const unsigned long long d = __shfl(diag, r, 64);
+      if (!((cur >> r) & 1ull)) {
+        keptbits |= 1ull << r;
+        cur |= d;
+      }
+    }
+    const int slot = kept_total + __popcll(keptbits & ((1ull << lane) - 1ull));
+    if (((keptbits >> lane) & 1ull) && slot < max_keep) keep[slot] = (int64_t)nb * 64 + lane;
+    kept_total += __popcll(keptbits);
+    const int j = nb + 1 + lane;                                // this lane's word of the later blocks
+    if (kept_total < max_keep && j < nblk) {
+      unsigned long long acc = remv[j];
+      const unsigned long long* col = mask + (int64_t)nb * 64 * col_blocks + j;
+      for (int r0 = 0; r0 < rows; r0 += 8) {
+        const unsigned kb8 = (unsigned)(keptbits >> r0) & 0xffu;
+        if (!kb8) continue;
+        unsigned long long v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)min(r0 + u, rows - 1) * col_blocks];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc |= ((kb8 >> u) & 1u) ? v[u] : 0ull;
+      }
+      remv[j] = acc;
+    }
+    __syncthreads();                                            // lane j's word is read as remv[nb] by the whole wave in a later round
+  }
+  if (lane == 0) num_out[s] = min(kept_total, max_keep);
+}
+
+extern "C" size_t sv_nms_segments_scratch_bytes(int num_segments, int seg_stride) {
+  if (num_segments <= 0 || seg_stride <= 0) return 0;
+  return (size_t)num_segments * (size_t)seg_stride * (size_t)((seg_stride + 63) / 64) * sizeof(unsigned long long);
+}
+
+extern "C" int sv_nms_segments(const float* boxes, const int32_t* seg_count, int num_segments, int seg_stride, float thresh, int normal, int max_keep,
+                               void* scratch, int64_t* keep, int32_t* num_out, void* stream) {
+  SV_CHECK_ARG(num_segments >= 0 && seg_stride >= 0 && max_keep >= 0, "nms_segments: bad arguments");
+  if (num_segments == 0) return SV_OK;
+  SV_CHECK_ARG(num_out && seg_count, "nms_segments: null pointer");
+  SV_CHECK_ARG(num_segments <= 65535, "nms_segments: more than 65535 segments");
+  hipStream_t st = sv_stream(stream);
+  if (seg_stride == 0) {
+    SV_HIP(hipMemsetAsync(num_out, 0, (size_t)num_segments * 4, st));
+    return SV_OK;
+  }
+  const int cb = (seg_stride + 63) / 64;
+  SV_CHECK_ARG(cb <= NMS_SEG_MAX_WORDS, "nms_segments: at most %d boxes per segment", NMS_SEG_MAX_WORDS * 64);
+  SV_CHECK_ARG(boxes && scratch && (keep || max_keep == 0), "nms_segments: null pointer");
+  unsigned long long* mask = reinterpret_cast<unsigned long long*>(scratch);
+  hipLaunchKernelGGL(k_nms_seg_mask, dim3(cb, cb, num_segments), dim3(64), 0, st, seg_count, seg_stride, thresh, boxes, mask, cb, normal);
+  hipLaunchKernelGGL(k_nms_seg_sweep, dim3(num_segments), dim3(64), 0, st, seg_count, seg_stride, mask, cb, max_keep, keep, num_out);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 // ------------------------------------------------------------------ points in boxes
 // boxes (B,T,7), pts (B,M,3) -> idx (B,M): first box containing the point, else -1
 __global__ __launch_bounds__(256) void k_points_in_boxes(int T, int M, const float* __restrict__ boxes, const float* __restrict__ pts,

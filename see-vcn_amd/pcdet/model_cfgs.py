@@ -316,3 +316,71 @@ def pvrcnnpp_model_cfg(dynamic_vfe=False, **kw):
     return dict(NAME='PVRCNNPlusPlus', VFE=dict(NAME='DynMeanVFE' if dynamic_vfe else 'MeanVFE'), BACKBONE_3D=dict(NAME='VoxelBackBone8x'),
                 MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=SECOND_BACKBONE_2D, DENSE_HEAD=PVRCNNPP_CENTER_HEAD,
                 PFE=pfe, POINT_HEAD=point_head, ROI_HEAD=roi_head, POST_PROCESSING=pp)
+
+
+# ------------------------------------------------------------------------------------------------ multi-head anchor detectors (AnchorHeadMulti)
+# detector3d/tools/cfgs/nuscenes_models/cbgs_second_multihead.yaml, cbgs_pp_multihead.yaml and kitti_models/second_multihead.yaml, MODEL sections
+# (values as data).  The two nuScenes files share anchors (only feature_map_stride differs), heads, coder and losses.
+def _mh_anchor(name, size, bottom, matched, unmatched, stride):
+    return dict(class_name=name, anchor_sizes=[size], anchor_rotations=[0, 1.57], anchor_bottom_heights=[bottom], align_center=False,
+                feature_map_stride=stride, matched_threshold=matched, unmatched_threshold=unmatched)
+
+
+_NUSC_MH_ANCHORS = [('car', [4.63, 1.97, 1.74], -0.95, 0.6, 0.45), ('truck', [6.93, 2.51, 2.84], -0.6, 0.55, 0.4),
+                    ('construction_vehicle', [6.37, 2.85, 3.19], -0.225, 0.5, 0.35), ('bus', [10.5, 2.94, 3.47], -0.085, 0.55, 0.4),
+                    ('trailer', [12.29, 2.90, 3.87], 0.115, 0.5, 0.35), ('barrier', [0.50, 2.53, 0.98], -1.33, 0.55, 0.4),
+                    ('motorcycle', [2.11, 0.77, 1.47], -1.085, 0.5, 0.3), ('bicycle', [1.70, 0.60, 1.28], -1.18, 0.5, 0.35),
+                    ('pedestrian', [0.73, 0.67, 1.77], -0.935, 0.6, 0.4), ('traffic_cone', [0.41, 0.41, 1.07], -1.285, 0.6, 0.4)]
+_KITTI_MH_ANCHORS = [('Car', [3.9, 1.6, 1.56], -1.6, 0.6, 0.45), ('Pedestrian', [0.8, 0.6, 1.73], -1.6, 0.5, 0.35),
+                     ('Cyclist', [1.76, 0.6, 1.73], -1.6, 0.5, 0.35)]
+_MH_TARGET_ASSIGNER = dict(NAME='AxisAlignedTargetAssigner', POS_FRACTION=-1.0, SAMPLE_SIZE=512, NORM_BY_NUM_EXAMPLES=False, MATCH_HEIGHT=False,
+                           BOX_CODER='ResidualCoder')
+NUSC_PP_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+NUSC_PP_VOXEL = dict(VOXEL_SIZE=[0.2, 0.2, 8.0], MAX_POINTS_PER_VOXEL=20, MAX_NUMBER_OF_VOXELS={'train': 30000, 'test': 30000})
+
+
+def _nusc_multihead_dense_head(stride):
+    return dict(
+        NAME='AnchorHeadMulti', CLASS_AGNOSTIC=False, DIR_OFFSET=0.78539, DIR_LIMIT_OFFSET=0.0, NUM_DIR_BINS=2, USE_MULTIHEAD=True,
+        SEPARATE_MULTIHEAD=True, ANCHOR_GENERATOR_CONFIG=[_mh_anchor(*a, stride) for a in _NUSC_MH_ANCHORS], SHARED_CONV_NUM_FILTER=64,
+        RPN_HEAD_CFGS=[dict(HEAD_CLS_NAME=['car']), dict(HEAD_CLS_NAME=['truck', 'construction_vehicle']), dict(HEAD_CLS_NAME=['bus', 'trailer']),
+                       dict(HEAD_CLS_NAME=['barrier']), dict(HEAD_CLS_NAME=['motorcycle', 'bicycle']),
+                       dict(HEAD_CLS_NAME=['pedestrian', 'traffic_cone'])],
+        SEPARATE_REG_CONFIG=dict(NUM_MIDDLE_CONV=1, NUM_MIDDLE_FILTER=64, REG_LIST=['reg:2', 'height:1', 'size:3', 'angle:2', 'velo:2']),
+        TARGET_ASSIGNER_CONFIG=dict(_MH_TARGET_ASSIGNER, BOX_CODER_CONFIG=dict(code_size=9, encode_angle_by_sincos=True)),
+        LOSS_CONFIG=dict(REG_LOSS_TYPE='WeightedL1Loss',
+                         LOSS_WEIGHTS=dict(pos_cls_weight=1.0, neg_cls_weight=2.0, cls_weight=1.0, loc_weight=0.25, dir_weight=0.2,
+                                           code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2])))
+
+
+def _mh_post_processing(thresh, pre, post, **extra):
+    return dict(RECALL_THRESH_LIST=[0.3, 0.5, 0.7], **extra, SCORE_THRESH=0.1, OUTPUT_RAW_SCORE=False, EVAL_METRIC='kitti',
+                NMS_CONFIG=dict(MULTI_CLASSES_NMS=True, NMS_TYPE='nms_gpu', NMS_THRESH=thresh, NMS_PRE_MAXSIZE=pre, NMS_POST_MAXSIZE=post))
+
+
+def second_multihead_model_cfg(dataset='nuscenes'):
+    """MODEL section of nuscenes_models/cbgs_second_multihead.yaml ('nuscenes': 10 classes in 6 heads, 9-d boxes with the sin/cos heading
+    code, no direction classifier) or kitti_models/second_multihead.yaml ('kitti': 3 single-class heads, 7-d boxes, direction classifier)."""
+    if dataset == 'nuscenes':
+        return dict(NAME='SECONDNet', VFE=dict(NAME='MeanVFE'), BACKBONE_3D=dict(NAME='VoxelResBackBone8x'),
+                    MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=dict(SECOND_BACKBONE_2D),
+                    DENSE_HEAD=_nusc_multihead_dense_head(8), POST_PROCESSING=_mh_post_processing(0.2, 1000, 83))
+    assert dataset == 'kitti', dataset
+    head = dict(
+        NAME='AnchorHeadMulti', CLASS_AGNOSTIC=False, USE_DIRECTION_CLASSIFIER=True, DIR_OFFSET=0.78539, DIR_LIMIT_OFFSET=0.0, NUM_DIR_BINS=2,
+        USE_MULTIHEAD=True, SEPARATE_MULTIHEAD=True, ANCHOR_GENERATOR_CONFIG=[_mh_anchor(*a, 8) for a in _KITTI_MH_ANCHORS],
+        SHARED_CONV_NUM_FILTER=64, RPN_HEAD_CFGS=[dict(HEAD_CLS_NAME=['Car']), dict(HEAD_CLS_NAME=['Pedestrian']), dict(HEAD_CLS_NAME=['Cyclist'])],
+        TARGET_ASSIGNER_CONFIG=dict(_MH_TARGET_ASSIGNER),
+        LOSS_CONFIG=dict(LOSS_WEIGHTS=dict(cls_weight=1.0, loc_weight=2.0, dir_weight=0.2, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0])))
+    return dict(NAME='SECONDNet', VFE=dict(NAME='MeanVFE'), BACKBONE_3D=dict(NAME='VoxelBackBone8x'),
+                MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=dict(SECOND_BACKBONE_2D), DENSE_HEAD=head,
+                POST_PROCESSING=_mh_post_processing(0.1, 4096, 500, MULTI_CLASSES_NMS=True))
+
+
+def pp_multihead_model_cfg():
+    """MODEL section of nuscenes_models/cbgs_pp_multihead.yaml (pillars of NUSC_PP_VOXEL over NUSC_PP_RANGE, a BEV backbone whose first
+    up-sampling level is a stride-2 convolution, anchors at feature_map_stride 4)."""
+    return dict(NAME='PointPillar', VFE=dict(PP_VFE), MAP_TO_BEV=dict(PP_MAP_TO_BEV),
+                BACKBONE_2D=dict(NAME='BaseBEVBackbone', LAYER_NUMS=[3, 5, 5], LAYER_STRIDES=[2, 2, 2], NUM_FILTERS=[64, 128, 256],
+                                 UPSAMPLE_STRIDES=[0.5, 1, 2], NUM_UPSAMPLE_FILTERS=[128, 128, 128]),
+                DENSE_HEAD=_nusc_multihead_dense_head(4), POST_PROCESSING=_mh_post_processing(0.2, 1000, 83))

@@ -90,6 +90,9 @@ class BaseBEVBackbone(nn.Module):
 
     def forward(self, data_dict):
         spatial_features = data_dict['spatial_features']
+        if len(self.blocks) == 0 and len(self.deblocks) == 0:        # a config without LAYER_NUMS (SingleHead of AnchorHeadMulti): the map itself,
+            data_dict['spatial_features_2d'] = spatial_features     # in the format it came in -- no channels_last copy, no parameter re-layout
+            return data_dict
         ups = []
         x = spatial_features
         nhwc = x.is_cuda and (BEV_FORMAT == "nhwc" or (BEV_FORMAT == "auto" and x.shape[0] >= 8))

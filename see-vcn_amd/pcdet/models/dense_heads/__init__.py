@@ -1,3 +1,4 @@
+from .anchor_head_multi import AnchorHeadMulti
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
@@ -9,6 +10,7 @@ from .point_intra_part_head import PointIntraPartOffsetHead
 __all__ = {
     'AnchorHeadTemplate': AnchorHeadTemplate,
     'AnchorHeadSingle': AnchorHeadSingle,
+    'AnchorHeadMulti': AnchorHeadMulti,
     'PointHeadSimple': PointHeadSimple,
     'CenterHead': CenterHead,
     'PointIntraPartOffsetHead': PointIntraPartOffsetHead,

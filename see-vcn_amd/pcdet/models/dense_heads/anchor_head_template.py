@@ -20,7 +20,6 @@ class AnchorHeadTemplate(nn.Module):
         self.class_names = class_names
         self.predict_boxes_when_training = predict_boxes_when_training
         self.use_multihead = cfg_get(model_cfg, 'USE_MULTIHEAD', False)
-        assert not self.use_multihead, "AnchorHeadMulti is outside the built path"
         anchor_target_cfg = cfg_get(model_cfg, 'TARGET_ASSIGNER_CONFIG')
         self.box_coder = getattr(box_coder_utils, cfg_get(anchor_target_cfg, 'BOX_CODER'))(
             num_dir_bins=cfg_get(anchor_target_cfg, 'NUM_DIR_BINS', 6), **(cfg_get(anchor_target_cfg, 'BOX_CODER_CONFIG', {}) or {}))
@@ -60,8 +59,22 @@ class AnchorHeadTemplate(nn.Module):
             self.anchors = [a.to(device) for a in self.anchors]
             self._flat_anchors = None
         if self._flat_anchors is None:
-            self._flat_anchors = torch.cat(self.anchors, dim=-3).reshape(-1, self.anchors[0].shape[-1]).contiguous()
+            if self.use_multihead:                                   # every class's anchors one run [size, rot, z, y, x] (reference :240-241)
+                flat = torch.cat([a.permute(3, 4, 0, 1, 2, 5).reshape(-1, a.shape[-1]) for a in self.anchors], dim=0)
+            else:
+                flat = torch.cat(self.anchors, dim=-3).reshape(-1, self.anchors[0].shape[-1])
+            # with the sin/cos heading code the reference's anchors carry code_size columns, one zero column more than a box: the kernels take 7 + E
+            self._flat_anchors = flat[:, :flat.shape[-1] - self._sincos].contiguous().float()
         return self._flat_anchors
+
+    @property
+    def _sincos(self):
+        return int(bool(getattr(self.box_coder, 'encode_angle_by_sincos', False)))
+
+    @property
+    def _coded(self):
+        """boxes wider than 7, a sin/cos heading code or head-major anchors: the *_coded kernels; else the 7-d entries, arguments unchanged"""
+        return bool(self.use_multihead or self.anchors[0].shape[-1] != 7 or self._sincos)
 
     def assign_targets(self, gt_boxes):
         self._anchors_on(gt_boxes.device)
@@ -117,7 +130,8 @@ class AnchorHeadTemplate(nn.Module):
         positives = box_cls_labels > 0
         reg_weights = positives.float()
         reg_weights = reg_weights / torch.clamp(positives.sum(1, keepdim=True).float(), min=1.0)
-        anchors = self._anchors_on(box_preds.device).view(1, -1, self.anchors[0].shape[-1]).repeat(batch_size, 1, 1)
+        anchors = self._anchors_on(box_preds.device)
+        anchors = anchors.view(1, -1, anchors.shape[-1]).repeat(batch_size, 1, 1)
         box_preds = box_preds.view(batch_size, -1, box_preds.shape[-1] // self.num_anchors_per_location)
         box_preds_sin, reg_targets_sin = self.add_sin_difference(box_preds, box_reg_targets)
         loss_w = cfg_get(self.model_cfg, 'LOSS_CONFIG')['LOSS_WEIGHTS']
@@ -145,24 +159,38 @@ class AnchorHeadTemplate(nn.Module):
 
     @torch.no_grad()
     def generate_predicted_boxes(self, batch_size, cls_preds, box_preds, dir_cls_preds=None):
-        """cls_preds (N,H,W,C1), box_preds (N,H,W,C2), dir_cls_preds (N,H,W,C3) -> (B,num_boxes,num_classes), (B,num_boxes,7)
-        through the fused decode kernel sv_anchor_decode."""
+        """cls_preds (N,H,W,C1), box_preds (N,H,W,C2), dir_cls_preds (N,H,W,C3) -- or, from a multihead, (N,A_head,C) per head as lists
+        -> (B,num_boxes,num_classes) (the list itself when it is one), (B,num_boxes,7+E) through the fused decode kernel sv_anchor_decode
+        (sv_anchor_decode_coded for coded boxes and head-major anchors)."""
         lib = _lib.load()
-        _lib.require_cuda(box_preds)
-        anchors = self._anchors_on(box_preds.device)
-        assert anchors.shape[-1] == 7, "fused decode handles 7-d boxes"
+        first = box_preds[0] if isinstance(box_preds, list) else box_preds
+        _lib.require_cuda(first)
+        anchors = self._anchors_on(first.device)
         num_anchors = anchors.shape[0]
-        batch_cls_preds = cls_preds.view(batch_size, num_anchors, -1).float()
+        batch_cls_preds = cls_preds if isinstance(cls_preds, list) else cls_preds.view(batch_size, num_anchors, -1).float()
+        if isinstance(box_preds, list):
+            box_preds = torch.cat(box_preds, dim=1)
         enc = box_preds.reshape(batch_size, num_anchors, -1).contiguous().float()
-        out = torch.empty_like(enc)
         dirp = nb = None
         if dir_cls_preds is not None:
             nb = cfg_get(self.model_cfg, 'NUM_DIR_BINS')
+            if isinstance(dir_cls_preds, list):
+                dir_cls_preds = torch.cat(dir_cls_preds, dim=1)
             dirp = dir_cls_preds.reshape(batch_size, num_anchors, -1).contiguous().float()
-        rc = lib.sv_anchor_decode(_lib.ptr(anchors), num_anchors, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0),
-                                  float(cfg_get(self.model_cfg, 'DIR_OFFSET', 0.0)), float(cfg_get(self.model_cfg, 'DIR_LIMIT_OFFSET', 0.0)),
-                                  _lib.ptr(out), _lib.stream())
-        _lib.check(rc, "sv_anchor_decode")
+        dir_offset, dir_limit = float(cfg_get(self.model_cfg, 'DIR_OFFSET', 0.0)), float(cfg_get(self.model_cfg, 'DIR_LIMIT_OFFSET', 0.0))
+        if not self._coded:
+            out = torch.empty_like(enc)
+            rc = lib.sv_anchor_decode(_lib.ptr(anchors), num_anchors, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0), dir_offset, dir_limit,
+                                      _lib.ptr(out), _lib.stream())
+            _lib.check(rc, "sv_anchor_decode")
+            return batch_cls_preds, out
+        extra = anchors.shape[-1] - 7
+        sincos = self._sincos
+        assert enc.shape[-1] == 7 + sincos + extra, "box_preds width does not match the box coder"
+        out = torch.empty((batch_size, num_anchors, 7 + extra), dtype=torch.float32, device=enc.device)
+        rc = lib.sv_anchor_decode_coded(_lib.ptr(anchors), num_anchors, extra, sincos, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0),
+                                        dir_offset, dir_limit, _lib.ptr(out), _lib.stream())
+        _lib.check(rc, "sv_anchor_decode_coded")
         return batch_cls_preds, out
 
     def forward(self, **kwargs):

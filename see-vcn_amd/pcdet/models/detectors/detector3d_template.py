@@ -184,11 +184,12 @@ class Detector3DTemplate(nn.Module):
         return {'loss': loss}, tb_dict, disp_dict
 
     def post_processing(self, batch_dict):
-        """Per scene: sigmoid scores, max over classes, class-agnostic NMS, recall bookkeeping
-        (reference detector3d_template.py:178-284, MULTI_CLASSES_NMS False branch)."""
+        """Per scene: sigmoid scores, max over classes, class-agnostic NMS, recall bookkeeping (reference detector3d_template.py:178-284);
+        with MULTI_CLASSES_NMS the class-wise NMS of the whole batch in one segmented call (_post_processing_multi_classes)."""
         pp = cfg_get(self.model_cfg, 'POST_PROCESSING')
         nms_cfg = cfg_get(pp, 'NMS_CONFIG')
-        assert not cfg_get(nms_cfg, 'MULTI_CLASSES_NMS', False), "multi-class NMS is outside the built path"
+        if cfg_get(nms_cfg, 'MULTI_CLASSES_NMS', False):
+            return self._post_processing_multi_classes(batch_dict, pp, nms_cfg)
         recall_dict, pred_dicts = {}, []
         for index in range(batch_dict['batch_size']):
             if batch_dict.get('batch_index', None) is not None:
@@ -214,6 +215,42 @@ class Detector3DTemplate(nn.Module):
             recall_dict = self.generate_recall_record(box_preds=final_boxes if 'rois' not in batch_dict else box_preds, recall_dict=recall_dict, batch_index=index, data_dict=batch_dict,
                                                       thresh_list=cfg_get(pp, 'RECALL_THRESH_LIST'))
             pred_dicts.append({'pred_boxes': final_boxes, 'pred_scores': selected_scores, 'pred_labels': label_preds[selected]})
+        return pred_dicts, recall_dict
+
+    def _post_processing_multi_classes(self, batch_dict, pp, nms_cfg):
+        """MULTI_CLASSES_NMS branch (reference :224-249): a list of per-head scores with multihead_label_mapping, or one tensor with the mapping
+        arange(1, num_class) the reference writes.  Dense (B, A, .) predictions go through multi_classes_nms_batch; stacked ones (batch_index)
+        scene by scene through multi_classes_nms."""
+        cls_all = batch_dict['batch_cls_preds']
+        if isinstance(cls_all, list):
+            mapping = batch_dict['multihead_label_mapping']
+        else:
+            cls_all = [cls_all]
+            mapping = [torch.arange(1, self.num_class, device=cls_all[0].device)]
+        normalized, thresh = batch_dict['cls_preds_normalized'], cfg_get(pp, 'SCORE_THRESH')
+        if batch_dict.get('batch_index', None) is None:
+            assert batch_dict['batch_box_preds'].dim() == 3
+            pred_dicts = model_nms_utils.multi_classes_nms_batch(cls_all, batch_dict['batch_box_preds'], mapping, nms_cfg, score_thresh=thresh,
+                                                                 normalized=normalized)
+        else:
+            pred_dicts = []
+            for index in range(batch_dict['batch_size']):
+                batch_mask = (batch_dict['batch_index'] == index)
+                box_preds = batch_dict['batch_box_preds'][batch_mask]
+                start, scores, labels, boxes = 0, [], [], []
+                for cls, cur_mapping in zip(cls_all, mapping):
+                    cur = cls[batch_mask] if normalized else torch.sigmoid(cls[batch_mask])
+                    assert cur.shape[1] == len(cur_mapping)
+                    s, l, bx = model_nms_utils.multi_classes_nms(cls_scores=cur, box_preds=box_preds[start:start + cur.shape[0]], nms_config=nms_cfg,
+                                                                 score_thresh=thresh)
+                    scores.append(s), labels.append(cur_mapping[l]), boxes.append(bx)
+                    start += cur.shape[0]
+                pred_dicts.append({'pred_boxes': torch.cat(boxes, dim=0), 'pred_scores': torch.cat(scores, dim=0), 'pred_labels': torch.cat(labels, dim=0)})
+        recall_dict = {}
+        for index, d in enumerate(pred_dicts):
+            src = batch_dict['batch_box_preds'][index] if batch_dict.get('batch_index', None) is None else batch_dict['batch_box_preds'][batch_dict['batch_index'] == index]
+            recall_dict = self.generate_recall_record(box_preds=d['pred_boxes'] if 'rois' not in batch_dict else src, recall_dict=recall_dict,
+                                                      batch_index=index, data_dict=batch_dict, thresh_list=cfg_get(pp, 'RECALL_THRESH_LIST'))
         return pred_dicts, recall_dict
 
     @staticmethod

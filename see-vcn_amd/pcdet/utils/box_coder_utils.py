@@ -11,7 +11,8 @@ class ResidualCoder(object):
             self.code_size += 1
 
     def encode_torch(self, boxes, anchors):
-        """boxes (N,7+C) ground truth, anchors (N,7+C) -> residual targets (N, code_size+C)"""
+        """boxes (N,7+C) ground truth, anchors (N,7+C') -> residual targets (N, code_size); extras pair up like the reference's zip (the
+        anchors of a sin/cos coder carry one zero column more than the boxes: anchor_ndim = code_size)"""
         a_dims = torch.clamp_min(anchors[:, 3:6], min=1e-5)
         g_dims = torch.clamp_min(boxes[:, 3:6], min=1e-5)
         diagonal = torch.sqrt(a_dims[:, 0:1] ** 2 + a_dims[:, 1:2] ** 2)
@@ -20,7 +21,8 @@ class ResidualCoder(object):
         dims_t = torch.log(g_dims / a_dims)
         rg, ra = boxes[:, 6:7], anchors[:, 6:7]
         rts = [torch.cos(rg) - torch.cos(ra), torch.sin(rg) - torch.sin(ra)] if self.encode_angle_by_sincos else [rg - ra]
-        extra = boxes[:, 7:] - anchors[:, 7:]
+        n_extra = min(boxes.shape[-1], anchors.shape[-1]) - 7
+        extra = boxes[:, 7:7 + n_extra] - anchors[:, 7:7 + n_extra]
         return torch.cat([xyz_t, dims_t, *rts, extra], dim=-1)
 
     def decode_torch(self, box_encodings, anchors):
@@ -35,10 +37,12 @@ class ResidualCoder(object):
         dzg = torch.exp(box_encodings[..., 5:6]) * dza
         if self.encode_angle_by_sincos:
             rg = torch.atan2(box_encodings[..., 7:8] + torch.sin(ra), box_encodings[..., 6:7] + torch.cos(ra))
-            rest = box_encodings[..., 8:] + anchors[..., 7:]
+            cts = box_encodings[..., 8:]
         else:
             rg = box_encodings[..., 6:7] + ra
-            rest = box_encodings[..., 7:] + anchors[..., 7:]
+            cts = box_encodings[..., 7:]
+        n_extra = min(cts.shape[-1], anchors.shape[-1] - 7)
+        rest = cts[..., :n_extra] + anchors[..., 7:7 + n_extra]
         return torch.cat([xg, yg, zg, dxg, dyg, dzg, rg, rest], dim=-1)
 
 

@@ -128,6 +128,14 @@ class WeightedSmoothL1Loss(nn.Module):
         return loss
 
 
+class WeightedL1Loss(WeightedSmoothL1Loss):
+    """code-wise weighted L1, un-reduced (B, #anchors, #codes)  (loss_utils.py:139-178): nan targets are replaced by the prediction, then code
+    weights, then anchor weights.  It is the smooth-L1 above at beta = 0 (`beta < 1e-5` selects |diff| there and in sv_weighted_smooth_l1_loss)."""
+
+    def __init__(self, code_weights: list = None):
+        super().__init__(beta=0.0, code_weights=code_weights)
+
+
 class WeightedCrossEntropyLoss(nn.Module):
     """anchor-weighted softmax cross entropy on one-hot targets, un-reduced (B, #anchors)  (loss_utils.py:181-206)"""
 
