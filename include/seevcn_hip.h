@@ -1097,6 +1097,44 @@ int sv_isolate_largest_cluster(const float* points, int row_stride, const int32_
  * sv_voxel_query_stack. */
 int sv_points_in_boxes_matrix(const float* boxes, const float* pts, int num_boxes, int num_points, int32_t* out, void* stream);
 
+/* ---- Focal sparse convolution (detector3d/pcdet/models/backbones_3d/focal_sparse_conv/): the data-dependent dilation of the active set that the
+ * reference writes as per-scene Python loops.  s (n, 27) fp32 = sigmoid(imps) as torch computed it: column 26 the voxel importance mv, column
+ * o < 26 the importance of kernel_offsets[o] (focal_sparse_conv.py:43-44).  coords (n, 4) int32 [b, z, y, x]; rows of a scene need not be contiguous.
+ * Cells are keyed by the true linear key ((b*Z + z)*Y + y)*X + x, not by the reference's z*max(y)*max(x) + y*max(x) + x (focal_sparse_utils.py:48,
+ * :71), which merges distinct voxels once one has y = 0 or x = 0; the two agree wherever that key is injective.  A scene without voxels contributes
+ * nothing (the reference raises).
+ *
+ * Foreground flags fore (n) uint8 -- split_voxels, focal_sparse_utils.py:112-118.  topk != 0: per scene the int(n_b * threshold) rows of largest mv
+ * (product in float64), equal values taken lower row first (the reference's unstable sort leaves that open), by an 8-bit radix select with the scene
+ * sizes counted on the device; topk == 0: mv > (float)threshold.  scratch: sv_focal_select_scratch_bytes(batch) (top-k only); batch <= 1024. */
+size_t sv_focal_select_scratch_bytes(int batch);
+int sv_focal_select(const float* s, const int32_t* coords, int64_t n, int batch, int topk, double threshold, void* scratch, uint8_t* fore,
+                    void* stream);
+/* Output set -- split_voxels, focal_sparse_utils.py:120-142, check_repeat :56-86 and combine_out, focal_sparse_conv.py:171-197: the input cells and,
+ * for every foreground row j and offset o with s[j, o] >= (float)threshold, the cell coords[j] + offset[o] when 0 < c < dim on all three axes
+ * (:130-131: `> 0`, so a candidate never has a coordinate 0), each once in ascending key order.  out_coords (capacity, 4): rows at or past capacity
+ * are not written; *num_out (device) = size of the set, which the caller compares with capacity; row_of_in (n) = output row of every input row (-1:
+ * coordinate outside the grid, or past capacity).  index_ws: sv_index_persistent_bytes(batch * Z * Y * X), all zero on entry, its words and chunk
+ * counts zero again on return; scratch: sv_focal_expand_scratch_bytes(batch * Z * Y * X). */
+size_t sv_focal_expand_scratch_bytes(int64_t ncells);
+int sv_focal_expand(const int32_t* coords, const float* s, const uint8_t* fore, int64_t n, int batch, const int32_t* shape_host, double threshold,
+                    void* index_ws, void* scratch, int32_t* out_coords, int32_t* row_of_in, int64_t capacity, int32_t* num_out, void* stream);
+/* Output features -- the mask multiply (focal_sparse_utils.py:109-110), check_repeat's mean of mask_kernel (:82-85), focal_sparse_conv.py:213-214 and the
+ * index_add_ of combine_out: out (num_out, channels), zero-filled here, then out[row_of_in[i]] = f[i] * (mv[i] if mask_multi) * w[i] with
+ * w[i] = (1 + sum s[j, o]) / (1 + c_i) over the c_i kept candidates landing on a foreground i -- a gather through nbr (27, n), the k = 3 submanifold
+ * table of the INPUT set (sv_rulebook_subm*), offsets in ascending o, fp32 -- and 1 for background rows or under skip_mask_kernel.  w (n) and
+ * cnt (n) = c_i are kept for the backward. */
+int sv_focal_place(const float* f, const float* s, const int32_t* coords, const uint8_t* fore, const int32_t* nbr, const int32_t* row_of_in,
+                   int64_t n, int channels, int mask_multi, int skip_mask_kernel, double threshold, int64_t num_out, float* w, int32_t* cnt,
+                   float* out, void* stream);
+/* Its gradients (autograd through the same lines; the selection is constant): grad_f (n, channels) = g[row_of_in[i]] * (mv[i]) * w[i];
+ * grad_s (n, 27): column o < 26 = t_i for the foreground row i the kept candidate (j, o) lands on, t_i = (g[row_of_in[i]] . f[i]) * (mv[i]) / (1 + c_i),
+ * column 26 = w[j] * (g[row_of_in[j]] . f[j]) under mask_multi, 0 elsewhere.  A gather through the same table: no atomics, bit-identical run to run.
+ * dots (n) fp32: scratch. */
+int sv_focal_backward(const float* g, const float* f, const float* s, const int32_t* coords, const uint8_t* fore, const int32_t* nbr,
+                      const int32_t* row_of_in, const float* w, const int32_t* cnt, int64_t n, int channels, int mask_multi, int skip_mask_kernel,
+                      double threshold, float* dots, float* grad_f, float* grad_s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

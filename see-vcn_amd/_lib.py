@@ -233,6 +233,12 @@ SIGNATURES = {
     "sv_assign_targets_axis_aligned": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_anchor_decode_coded": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p]),
     "sv_assign_targets_axis_aligned_coded": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_focal_select_scratch_bytes": (c_sz, [c_i]),
+    "sv_focal_select": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_d, c_p, c_p, c_p]),
+    "sv_focal_expand_scratch_bytes": (c_sz, [c_i64]),
+    "sv_focal_expand": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_d, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
+    "sv_focal_place": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_d, c_i64, c_p, c_p, c_p, c_p]),
+    "sv_focal_backward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -116,3 +116,5 @@ __device__ __forceinline__ int32_t sv_index_lookup(const SvIndexView& ix, int64_
 // host-side launch helpers implemented in coord_index.hip
 int sv_index_scan_launch(const SvIndexView& ix, int32_t* total_out, void* scan_tmp, hipStream_t st);
 size_t sv_index_scan_tmp_bytes(int64_t ncells);
+// after the chunk scan: words[w].y of every occupied chunk, so that sv_index_lookup answers (rulebook.hip)
+int sv_index_prefix_launch(const SvIndexView& ix, hipStream_t st);

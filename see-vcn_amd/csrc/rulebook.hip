@@ -66,7 +66,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_index_prefix(SvIndexView ix, int
   }
 }
 
-static int launch_index_prefix(const SvIndexView& ix, hipStream_t st) {
+int sv_index_prefix_launch(const SvIndexView& ix, hipStream_t st) {
   const int64_t nchunks = sv_index_nchunks(ix.ncells);
   const int grid = sv_grid_1d((nchunks + 63) / 64 * 64, RB_THREADS);
   hipLaunchKernelGGL(k_index_prefix, dim3(grid), dim3(RB_THREADS), 0, st, ix, nchunks);
@@ -179,7 +179,7 @@ extern "C" int sv_rulebook_subm(const int32_t* coords, int64_t n, int batch, con
   hipLaunchKernelGGL(k_subm_mark, dim3(grid), dim3(RB_THREADS), 0, st, c4, n, g, ix);
   rc = sv_index_scan_launch(ix, total, scan_tmp, st);
   if (rc) return rc;
-  rc = launch_index_prefix(ix, st);
+  rc = sv_index_prefix_launch(ix, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_subm_perm, dim3(grid), dim3(RB_THREADS), 0, st, c4, n, g, ix, perm);
   hipLaunchKernelGGL(k_subm_query, dim3(sv_grid_1d(n * g.K, RB_THREADS, 256 * 16)), dim3(RB_THREADS), 0, st, c4, n, g, ix, perm, nbr);
@@ -550,7 +550,7 @@ extern "C" int sv_rulebook_sparse(const int32_t* coords, int64_t n_in, int batch
   hipLaunchKernelGGL(k_sparse_phase<0>, dim3(grid), dim3(RB_THREADS), 0, st, c4, n_in, g, ix, nbr_in, oc4, capacity);
   rc = sv_index_scan_launch(ix, num_out, scan_tmp, st);
   if (rc) return rc;
-  rc = launch_index_prefix(ix, st);
+  rc = sv_index_prefix_launch(ix, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_sparse_phase<1>, dim3(grid), dim3(RB_THREADS), 0, st, c4, n_in, g, ix, nbr_in, oc4, capacity);
   hipLaunchKernelGGL(k_sparse_phase<2>, dim3(grid), dim3(RB_THREADS), 0, st, c4, n_in, g, ix, nbr_in, oc4, capacity);

@@ -154,6 +154,16 @@ def voxelrcnn_model_cfg(dynamic_vfe=False, **kw):
                 MAP_TO_BEV=dict(NAME='HeightCompression', NUM_BEV_FEATURES=256), BACKBONE_2D=VOXELRCNN_BACKBONE_2D, DENSE_HEAD=head,
                 ROI_HEAD=voxelrcnn_cfg(**kw), POST_PROCESSING=pp)
 
+
+def voxelrcnn_focal_model_cfg(dynamic_vfe=False, backbone=None, **kw):
+    """MODEL section of kitti_models/voxel_rcnn_car_focal_multimodal.yaml (:37-187): voxel_rcnn_car.yaml with BACKBONE_3D VoxelBackBone8xFocal, restated with
+    USE_IMG: False (the image branch is not built; the yaml's IMG_PRETRAIN belongs to it).  backbone: further BACKBONE_3D keys (TOPK, THRESHOLD,
+    MASK_MULTI, SKIP_MASK_KERNEL, ENLARGE_VOXEL_CHANNELS, last_pad); the yaml leaves them at the class defaults."""
+    cfg = voxelrcnn_model_cfg(dynamic_vfe=dynamic_vfe, **kw)
+    cfg['BACKBONE_3D'] = dict(NAME='VoxelBackBone8xFocal', USE_IMG=False, **(backbone or {}))
+    return cfg
+
+
 # detector3d/tools/cfgs/kitti_models/PartA2.yaml:31-170 (values as data)
 def parta2_cfg(pool_size=12, max_points_per_voxel=128, num_features=128, roi_per_image=128, nms_post_train=512, nms_pre_train=9000, dp_ratio=0.3,
                shared_fc=(256, 256, 256)):

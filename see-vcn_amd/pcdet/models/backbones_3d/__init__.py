@@ -1,5 +1,6 @@
 from .pointnet2_backbone import PointNet2MSG
 from .spconv_backbone import VoxelBackBone8x, VoxelResBackBone8x
+from .spconv_backbone_focal import VoxelBackBone8xFocal
 from .spconv_unet import UNetV2
 
 # same registry shape as the reference (backbones_3d/__init__.py:6-13)
@@ -8,4 +9,5 @@ __all__ = {
     'VoxelResBackBone8x': VoxelResBackBone8x,
     'UNetV2': UNetV2,
     'PointNet2MSG': PointNet2MSG,
+    'VoxelBackBone8xFocal': VoxelBackBone8xFocal,
 }

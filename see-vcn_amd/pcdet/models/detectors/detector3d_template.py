@@ -175,6 +175,17 @@ class Detector3DTemplate(nn.Module):
         common_utils.materialize_tb(tb_dict)                               # ... and become Python floats with ONE device -> host read
         return total, tb_dict, {}
 
+    def add_backbone_3d_loss(self, loss, tb_dict):
+        """loss + backbone_3d.get_loss() when the 3-D backbone has a loss of its own (VoxelBackBone8xFocal's loss_box_of_pts; reference
+        detectors/voxel_rcnn.py:33, pv_rcnn.py:32); any other backbone leaves both as they are."""
+        backbone = getattr(self, 'backbone_3d', None)
+        if backbone is None or not hasattr(backbone, 'get_loss'):
+            return loss, tb_dict
+        with common_utils.deferred_tb():
+            term, tb_dict = backbone.get_loss(tb_dict)
+        common_utils.materialize_tb(tb_dict)
+        return loss + term, tb_dict
+
     def forward(self, batch_dict):
         """train: ({'loss': loss}, tb_dict, disp_dict); eval: post_processing(batch_dict) = (pred_dicts, recall_dict)"""
         batch_dict = self.run_modules(batch_dict)

@@ -10,3 +10,8 @@ class PVRCNN(Detector3DTemplate):
     def __init__(self, model_cfg, num_class, dataset):
         super().__init__(model_cfg=model_cfg, num_class=num_class, dataset=dataset)
         self.module_list = self.build_networks()
+
+    def get_training_loss(self):
+        loss, tb_dict, disp_dict = super().get_training_loss()
+        loss, tb_dict = self.add_backbone_3d_loss(loss, tb_dict)          # VoxelBackBone8xFocal only (reference detectors/pv_rcnn.py:32)
+        return loss, tb_dict, disp_dict

@@ -307,13 +307,16 @@ def build_subm_rulebook(indices, batch_size, spatial_shape, ksize, dilation=(1, 
         _lib.check(rc, "sv_rulebook_subm_cellmap")
         rb = Rulebook(nbr, None, indices, list(spatial_shape), n, n, True, list(ksize))
         rb.rows_out, rb.masks_out = rows, masks
+        rb.dilation = [int(d) for d in dilation]
         return rb
     ws = _lib.workspace.persistent(f"rb_index_{tuple(spatial_shape)}_{batch_size}", lib.sv_index_persistent_bytes(ncells), dev)
     scratch = _lib.workspace.scratch("rb_scratch", lib.sv_rulebook_scratch_bytes(n, ncells), dev)
     rc = lib.sv_rulebook_subm(_lib.ptr(indices), n, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(dilation),
                               _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(nbr), _lib.stream())
     _lib.check(rc, "sv_rulebook_subm")
-    return Rulebook(nbr, None, indices, list(spatial_shape), n, n, True, list(ksize))
+    rb = Rulebook(nbr, None, indices, list(spatial_shape), n, n, True, list(ksize))
+    rb.dilation = [int(d) for d in dilation]          # recorded by this builder only: a table may be shared between keys when kernel and dilation agree
+    return rb
 
 
 def build_sparse_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, dilation=(1, 1, 1)):
