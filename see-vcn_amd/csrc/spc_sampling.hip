@@ -4,12 +4,11 @@
 //   detector3d/pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:45-75    sample_points_with_roi: an (N, M) distance matrix, min, mask
 //   detector3d/pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:78-121   sector_fps: atan2 sectors, one boolean mask + .sum().item() per
 //                                                                             sector, host-built count tensors, one ragged FPS launch
-//   detector3d/pcdet/ops/pointnet2/pointnet2_stack/src/sampling_gpu.cu:188-319 the ragged FPS kernel (1024 threads, temp in HBM every round)
-// Here: k_spc_select (mask + sector per point, RoIs in LDS), k_spc_partition (stable rows per (scene, sector), quotas, output offsets; one
-// workgroup per scene, no atomics) and k_fps_ragged (one workgroup per segment, points gathered through the row list into registers).
+// Here: k_spc_select (mask + sector per point, RoIs in LDS) and k_spc_partition (stable rows per (scene, sector), quotas, output offsets; one
+// workgroup per scene, no atomics); the third launch is k_fps_ragged (fps.hip: one workgroup per segment, points gathered through the row list
+// into registers).
 #include "common.h"
 #include "wave.h"
-#include "fps.h"
 
 constexpr int SPC_SELECT_THREADS = 256;
 constexpr int SPC_PART_THREADS = 1024;
@@ -166,140 +165,6 @@ __global__ __launch_bounds__(SPC_PART_THREADS) void k_spc_partition(const int32_
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Ragged farthest point sampling: one workgroup per segment, n / m / offsets from the device tables.  Same distance expression, running
-// minimum and key as k_fps_reg / k_fps_stream (pointnet2.hip); the reference's stacked kernel always reduces over 1024 slots
-// (sampling_gpu.cu:340), so the tie key is fps_key with log2t = 10 for every n.  Picks are kept as positions in the segment during the
-// rounds and turned into global rows through `order` at the end, so the row list is off the rounds' critical path.
-// ------------------------------------------------------------------------------------------------
-constexpr int FPS_RAGGED_LOG2T = 10;
-
-template <int P>
-__device__ __forceinline__ void fps_segment_reg(const float* __restrict__ xyz, const int32_t* __restrict__ ord, int first, int n, int m,
-                                                int32_t* __restrict__ idx) {
-  constexpr int NW = FPS_THREADS / 64;
-  __shared__ unsigned long long skey[2][NW];
-  __shared__ float sxyz[2][NW][3];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  float px[P], py[P], pz[P], pt[P];
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    const int k = tid + i * FPS_THREADS;
-    const bool ok = k < n;
-    const int64_t row = ok ? (ord ? ord[k] : first + k) : 0;
-    px[i] = ok ? xyz[row * 3] : 0.f;
-    py[i] = ok ? xyz[row * 3 + 1] : 0.f;
-    pz[i] = ok ? xyz[row * 3 + 2] : 0.f;
-    pt[i] = 1e10f;
-  }
-  if (tid == 0) idx[0] = 0;
-  const int64_t row0 = ord ? ord[0] : first;
-  float x1 = xyz[row0 * 3], y1 = xyz[row0 * 3 + 1], z1 = xyz[row0 * 3 + 2];   // first pick is the segment's first row (sampling_gpu.cu:224-225)
-  for (int j = 1; j < m; ++j) {
-    const int par = j & 1;
-    float bd = -1.f, bx = 0.f, by = 0.f, bz = 0.f;
-    int bk = -1;
-    int tid_r = tid;
-    asm volatile("" : "+v"(tid_r));                // opaque per round: keeps hipcc from hoisting P point indices / tie keys into registers
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      const int k = tid_r + i * FPS_THREADS;
-      const float d = (px[i] - x1) * (px[i] - x1) + (py[i] - y1) * (py[i] - y1) + (pz[i] - z1) * (pz[i] - z1);   // sampling_gpu.cu:243
-      const float d2 = fminf(d, pt[i]);
-      pt[i] = d2;
-      bool up = k < n && d2 > bd;
-      if (k < n && d2 == bd) up = fps_key(d2, k, FPS_RAGGED_LOG2T) > fps_key(bd, bk, FPS_RAGGED_LOG2T);
-      bd = up ? d2 : bd;
-      bk = up ? k : bk;
-      bx = up ? px[i] : bx; by = up ? py[i] : by; bz = up ? pz[i] : bz;
-    }
-    const unsigned long long best = bk >= 0 ? fps_key(bd, bk, FPS_RAGGED_LOG2T) : 0ull;
-    const unsigned long long wbest = sv_wave_reduce_max(best);
-    if (best == wbest && best != 0ull) {
-      skey[par][wid] = wbest;
-      sxyz[par][wid][0] = bx; sxyz[par][wid][1] = by; sxyz[par][wid][2] = bz;
-    } else if (wbest == 0ull && lane == 0) {
-      skey[par][wid] = 0ull;
-    }
-    __syncthreads();                                            // the only barrier of the round (slots alternate by parity)
-    const int sl = lane & (NW - 1);
-    const unsigned long long mine = skey[par][sl];
-    const unsigned long long w = sv_wave_reduce_max(mine);
-    const int src = sv_wave_ballot_first(mine == w);
-    x1 = __shfl(sxyz[par][sl][0], src, 64);
-    y1 = __shfl(sxyz[par][sl][1], src, 64);
-    z1 = __shfl(sxyz[par][sl][2], src, 64);
-    if (tid == 0) idx[j] = fps_key_index(w, FPS_RAGGED_LOG2T);
-  }
-}
-
-// segments past the register file: temp (one float per row of the segment, at its position in `order`) lives in HBM
-__device__ __forceinline__ void fps_segment_stream(const float* __restrict__ xyz, const int32_t* __restrict__ ord, int first, int n, int m,
-                                                   float* __restrict__ temp, int32_t* __restrict__ idx) {
-  __shared__ unsigned long long slot[2][FPS_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  for (int k = tid; k < n; k += FPS_THREADS) temp[k] = 1e10f;
-  if (tid == 0) idx[0] = 0;
-  int old = 0;
-  __syncthreads();
-  for (int j = 1; j < m; ++j) {
-    const int par = j & 1;
-    const int64_t ro = ord ? ord[old] : first + old;
-    const float x1 = xyz[ro * 3], y1 = xyz[ro * 3 + 1], z1 = xyz[ro * 3 + 2];
-    unsigned long long best = 0ull;
-    for (int k = tid; k < n; k += FPS_THREADS) {
-      const int64_t row = ord ? ord[k] : first + k;
-      const float x2 = xyz[row * 3], y2 = xyz[row * 3 + 1], z2 = xyz[row * 3 + 2];
-      const float d = (x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1) + (z2 - z1) * (z2 - z1);
-      const float d2 = fminf(d, temp[k]);
-      temp[k] = d2;
-      const unsigned long long key = fps_key(d2, k, FPS_RAGGED_LOG2T);
-      best = key > best ? key : best;
-    }
-    best = sv_wave_reduce_max(best);
-    if (lane == 0) slot[par][wid] = best;
-    __syncthreads();
-    unsigned long long w = slot[par][lane & (FPS_THREADS / 64 - 1)];
-    w = sv_wave_reduce_max(w);
-    old = fps_key_index(w, FPS_RAGGED_LOG2T);
-    if (tid == 0) idx[j] = old;
-  }
-}
-
-// MAXP: the largest register-resident instantiation this kernel carries (the host picks it from its upper bound of a segment's size); the branch on
-// the segment's own n is workgroup-uniform, so a 3 000-point segment pays for 8 points per thread and round, not for 48.  Three tiers (8, 32, 48): a
-// kernel is allocated for its largest instantiation, and the 48-point one does not fit 256 VGPRs without scratch (as k_fps_reg<48>), so bounds
-// up to 16 384 points get a kernel of their own that carries nothing above 32.
-template <int MAXP, bool STREAM>
-__global__ __launch_bounds__(FPS_THREADS) void k_fps_ragged(const float* __restrict__ xyz, const int32_t* __restrict__ order,
-                                                            const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_cnt,
-                                                            const int32_t* __restrict__ seg_m, const int32_t* __restrict__ seg_out_start,
-                                                            int64_t n_rows, int64_t idx_len, float* __restrict__ temp, int32_t* __restrict__ idx_all) {
-  const int g = blockIdx.x;
-  const int n = seg_cnt[g], m = seg_m[g];
-  if (n <= 0 || m <= 0) return;                                    // nothing of such a segment is read or written
-  const int first = seg_start[g], out = seg_out_start[g];
-  // tables that do not fit the buffers they index write nothing
-  if (first < 0 || (int64_t)first + n > n_rows || out < 0 || (int64_t)out + m > idx_len) return;
-  const int32_t* ord = order ? order + first : nullptr;
-  int32_t* idx = idx_all + out;
-  bool ran = true;                                                 // workgroup-uniform
-  if (n <= 2 * FPS_THREADS) fps_segment_reg<2>(xyz, ord, first, n, m, idx);
-  else if (n <= 4 * FPS_THREADS) fps_segment_reg<4>(xyz, ord, first, n, m, idx);
-  else if (n <= 8 * FPS_THREADS) fps_segment_reg<8>(xyz, ord, first, n, m, idx);
-  else if (MAXP >= 32 && n <= 16 * FPS_THREADS) fps_segment_reg<(MAXP >= 32 ? 16 : 2)>(xyz, ord, first, n, m, idx);
-  else if (MAXP >= 32 && n <= 32 * FPS_THREADS) fps_segment_reg<(MAXP >= 32 ? 32 : 2)>(xyz, ord, first, n, m, idx);
-  else if (MAXP >= FPS_MAXP && n <= FPS_MAXP * FPS_THREADS) fps_segment_reg<(MAXP >= FPS_MAXP ? FPS_MAXP : 2)>(xyz, ord, first, n, m, idx);
-  else if (STREAM) fps_segment_stream(xyz, ord, first, n, m, temp + first, idx);
-  else ran = false;                                                // a segment above the host's bound: left unwritten
-  if (!ran) return;
-  __syncthreads();                                                 // tid 0's positions are visible to the workgroup
-  for (int j = threadIdx.x; j < m; j += FPS_THREADS) {
-    const int k = idx[j];
-    idx[j] = ord ? ord[k] : first + k;
-  }
-}
-
 extern "C" int sv_spc_select(const float* xyz, const int32_t* xyz_batch_start, const int32_t* xyz_batch_cnt, int batch, int max_n,
                              const float* rois, int num_rois, int roi_stride, float radius, int num_sectors, int32_t* sector, void* stream) {
   SV_CHECK_ARG(batch >= 0 && max_n >= 0 && num_rois >= 0 && num_rois <= SPC_MAX_ROIS && roi_stride >= 6, "spc_select: bad arguments");
@@ -326,29 +191,6 @@ extern "C" int sv_spc_partition(const int32_t* sector, const float* xyz, const i
   const float sector_size = num_sectors > 0 ? (float)(3.141592653589793 * 2 / num_sectors) : 1.f;
   hipLaunchKernelGGL(k_spc_partition, dim3(batch), dim3(SPC_PART_THREADS), 0, sv_stream(stream), sector, xyz, xyz_batch_start, xyz_batch_cnt,
                      num_keypoints, num_sectors, sector_size, num_keypoints + num_sectors, order, seg_start, seg_cnt, seg_m, seg_out_start, kp_cnt);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-extern "C" int sv_stack_farthest_point_sampling_ragged(const float* xyz, int64_t n_rows, const int32_t* order, const int32_t* seg_start,
-                                                       const int32_t* seg_cnt, const int32_t* seg_m, const int32_t* seg_out_start,
-                                                       int num_segments, int max_n, float* temp, int32_t* idx, int64_t idx_len, void* stream) {
-  SV_CHECK_ARG(num_segments >= 0 && max_n >= 0 && n_rows >= 0 && n_rows < (1ll << 31) && idx_len >= 0, "stack_farthest_point_sampling_ragged: bad arguments");
-  if (num_segments == 0 || max_n == 0 || idx_len == 0) return SV_OK;
-  SV_CHECK_ARG(xyz && seg_start && seg_cnt && seg_m && seg_out_start && idx, "stack_farthest_point_sampling_ragged: null pointer");
-  dim3 grid(num_segments), block(FPS_THREADS);
-  hipStream_t st = sv_stream(stream);
-  if (max_n <= 8 * FPS_THREADS)
-    hipLaunchKernelGGL((k_fps_ragged<8, false>), grid, block, 0, st, xyz, order, seg_start, seg_cnt, seg_m, seg_out_start, n_rows, idx_len, temp, idx);
-  else if (max_n <= 32 * FPS_THREADS)
-    hipLaunchKernelGGL((k_fps_ragged<32, false>), grid, block, 0, st, xyz, order, seg_start, seg_cnt, seg_m, seg_out_start, n_rows, idx_len, temp, idx);
-  else if (max_n <= FPS_MAXP * FPS_THREADS)
-    hipLaunchKernelGGL((k_fps_ragged<FPS_MAXP, false>), grid, block, 0, st, xyz, order, seg_start, seg_cnt, seg_m, seg_out_start, n_rows, idx_len, temp, idx);
-  else {
-    SV_CHECK_ARG(temp, "stack_farthest_point_sampling_ragged: segments of more than %d points need the temp buffer (n_rows floats)",
-                 FPS_MAXP * FPS_THREADS);
-    hipLaunchKernelGGL((k_fps_ragged<FPS_MAXP, true>), grid, block, 0, st, xyz, order, seg_start, seg_cnt, seg_m, seg_out_start, n_rows, idx_len, temp, idx);
-  }
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

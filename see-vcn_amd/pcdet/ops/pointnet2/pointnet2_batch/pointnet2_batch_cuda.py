@@ -36,11 +36,8 @@ def gather_points_grad_wrapper(b, c, n, npoints, grad_out, idx, grad_points):
 
 
 def farthest_point_sampling_wrapper(b, n, m, points, temp, idx):
-    _lib.require_cuda(points, idx)
-    from ..pointnet2_stack.pointnet2_stack_cuda import fps_bucketed
-    if fps_bucketed(points, None, None, b, n, n, m, idx):
-        return 1
-    return _call("sv_farthest_point_sampling", _lib.ptr(points), int(b), int(n), int(m), _lib.ptr(temp), _lib.ptr(idx))
+    from ..pointnet2_stack import pointnet2_stack_cuda
+    return pointnet2_stack_cuda.farthest_point_sampling_wrapper(b, n, m, points, temp, idx)
 
 
 def three_nn_wrapper(b, n, m, unknown, known, dist2, idx):

@@ -121,13 +121,24 @@ def fps_bucketed(points, starts, cnt, batch, fixed_n, max_n, m, idx):
 
 
 def farthest_point_sampling_wrapper(b, n, m, points, temp, idx):
+    """The fixed-layout call, (b, n, 3) -> (b, m), of both pointnet2 wrappers and vcn.utils.misc.fps.  temp None: the (b, n) buffer of the exhaustive
+    kernels is allocated here, only when they run."""
     lib = _lib.load()
     _lib.require_cuda(points, idx)
     if fps_bucketed(points, None, None, b, n, n, m, idx):
         return 1
+    if temp is None:
+        temp = torch.empty((int(b), int(n)), dtype=torch.float32, device=points.device)
     rc = lib.sv_farthest_point_sampling(_lib.ptr(points), int(b), int(n), int(m), _lib.ptr(temp), _lib.ptr(idx), _lib.stream())
     _lib.check(rc, "sv_farthest_point_sampling")
     return 1
+
+
+def _exhaustive_scratch(lib, points, batch, max_n):
+    """(temp past the register path, records + error word of several workgroups per scene: the library decides whether it uses them; same indices)"""
+    temp = torch.empty((points.shape[0],), dtype=torch.float32, device=points.device) if max_n > 24576 else None
+    scratch = torch.empty((int(lib.sv_fps_multi_scratch_bytes(batch)),), dtype=torch.uint8, device=points.device)
+    return temp, scratch
 
 
 def stack_farthest_point_sampling(points, xyz_batch_cnt, npoint, max_n=None, bucketed=True):
@@ -142,10 +153,7 @@ def stack_farthest_point_sampling(points, xyz_batch_cnt, npoint, max_n=None, buc
     idx = torch.empty((batch, npoint), dtype=torch.int32, device=points.device)
     if bucketed and fps_bucketed(points, starts, cnt, batch, 0, max_n, npoint, idx):
         return idx
-    temp = torch.empty((points.shape[0],), dtype=torch.float32, device=points.device) if max_n > 24576 else None
-    # several workgroups per scene where that applies (sv_stack_farthest_point_sampling_multi decides; same indices either way)
-    nbytes = int(lib.sv_fps_multi_scratch_bytes(batch))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=points.device)
+    temp, scratch = _exhaustive_scratch(lib, points, batch, max_n)
     rc = lib.sv_stack_farthest_point_sampling_multi(_lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), batch, int(max_n), int(npoint),
                                                     _lib.ptr(temp), _lib.ptr(scratch), _lib.ptr(idx), _lib.stream())
     _lib.check(rc, "sv_stack_farthest_point_sampling_multi")
@@ -187,9 +195,7 @@ def stack_farthest_point_sampling_async(points, xyz_batch_cnt, npoint, max_n):
     idx = torch.empty((batch, npoint), dtype=torch.int32, device=points.device)
     if fps_bucketed(points, starts, cnt, batch, 0, max_n, npoint, idx):
         return FpsHandle(idx, None, torch.cuda.current_stream(), None)
-    temp = torch.empty((points.shape[0],), dtype=torch.float32, device=points.device) if max_n > 24576 else None
-    nbytes = int(lib.sv_fps_multi_scratch_bytes(batch))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=points.device)
+    temp, scratch = _exhaustive_scratch(lib, points, batch, max_n)
     off = int(lib.sv_fps_multi_error_offset(batch))
     err = scratch[off:off + 4].view(torch.int32)
     stream = torch.cuda.current_stream()

@@ -83,7 +83,42 @@ def test_hip_stack_fps_matches_per_scene(cuda, hip_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("counts,m", [([20000, 4097], 1024), ([65536], 300), ([5000, 5000, 5000, 5000], 2048)])
+def test_hip_exhaustive_fps_every_instantiation(cuda, hip_lib):
+    """The C entries themselves (no bucket path, no multi scratch): the first scene size of every tier above the 4-point one -- k_fps_reg<8>, <16>,
+    <32>, <40>, <48> and, with a temp buffer, k_fps_stream -- with a scene whose second half repeats its first (exact ties every round), and a ragged
+    batch with an empty scene (global rows, k_fps_reg<16>).  Same picks as the oracle."""
+    from seevcn_amd import _lib
+    m = 48
+    for n in (2049, 4097, 8193, 16385, 20481, 24577):
+        rng = np.random.default_rng(n)
+        xyz = rng.normal(size=(2, n, 3)).astype(np.float32) * 10
+        xyz[1, n // 2:] = xyz[1, : n - n // 2]
+        pts = torch.from_numpy(xyz).to(cuda)
+        temp = torch.empty((2, n), dtype=torch.float32, device=cuda) if n > 24576 else None
+        idx = torch.full((2, m), -1, dtype=torch.int32, device=cuda)
+        _lib.check(hip_lib.sv_farthest_point_sampling(_lib.ptr(pts), 2, n, m, _lib.ptr(temp), _lib.ptr(idx), _lib.stream()), "sv_farthest_point_sampling")
+        out = idx.cpu().numpy()
+        for b in range(2):
+            ref = op2.farthest_point_sampling(xyz[b], m)
+            assert np.array_equal(out[b], ref), (n, b, np.nonzero(out[b] != ref)[0][:5])
+    counts = [2049, 600, 0, 4097]
+    rng = np.random.default_rng(7)
+    xyz = rng.normal(size=(sum(counts), 3)).astype(np.float32) * 10
+    xyz[1024:2049] = xyz[:1025]                                                # duplicates inside scene 0
+    cnt = np.array(counts, np.int32)
+    starts = (np.cumsum(cnt) - cnt).astype(np.int32)
+    pts, st, ct = (torch.from_numpy(a).to(cuda) for a in (xyz, starts, cnt))
+    idx = torch.full((len(counts), m), -1, dtype=torch.int32, device=cuda)
+    _lib.check(hip_lib.sv_stack_farthest_point_sampling(_lib.ptr(pts), _lib.ptr(st), _lib.ptr(ct), len(counts), max(counts), m, None, _lib.ptr(idx),
+                                                        _lib.stream()), "sv_stack_farthest_point_sampling")
+    out = idx.cpu().numpy()
+    for b, (s, c) in enumerate(zip(starts, counts)):
+        ref = op2.farthest_point_sampling(xyz[s:s + c], m) + s if c else np.full(m, -1)      # an empty scene's row is not written
+        assert np.array_equal(out[b], ref), (b, np.nonzero(out[b] != ref)[0][:5])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("counts,m", [([20000, 4097], 1024), ([65536], 300), ([5000, 5000, 5000, 5000], 2048), ([9000, 8193], 96)])
 def test_hip_stack_fps_several_workgroups_per_scene_index_exact(cuda, hip_lib, counts, m):
     """Scenes of >= 4096 points take the 16-workgroups-per-scene kernel (records exchanged every round): same picks as the oracle,
     including exact duplicates that tie on distance (tie rule of sampling_gpu.cu:16-21 lives in the key)."""

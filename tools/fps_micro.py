@@ -27,7 +27,10 @@ def main():
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     for kind in ("sweep", "gauss"):
-        for counts, m in (([17000] * 4, 4096), ([20000] * 4, 4096), ([17000] * 4, 2048), ([60000] * 2, 4096), ([17000] * 16, 2048), ([5000] * 4, 2048)):
+        # the last two reach the one-workgroup register kernels: 24 scenes are too many workgroups for several per scene (k_fps_reg<40>), 1500 points
+        # are below the bucket kernel's minimum (k_fps_reg<4> in both columns)
+        for counts, m in (([17000] * 4, 4096), ([20000] * 4, 4096), ([17000] * 4, 2048), ([60000] * 2, 4096), ([17000] * 16, 2048), ([5000] * 4, 2048),
+                          ([17000] * 24, 2048), ([1500] * 4, 512)):
             xyz = torch.from_numpy(np.concatenate([cloud(kind, c, rng) for c in counts])).to(dev)
             cnt = torch.tensor(counts, dtype=torch.int32, device=dev)
             line = f"{kind:5s} scenes {len(counts):2d} x {counts[0]} pts -> {m}:"
