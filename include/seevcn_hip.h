@@ -1135,6 +1135,45 @@ int sv_focal_backward(const float* g, const float* f, const float* s, const int3
                       const int32_t* row_of_in, const float* w, const int32_t* cnt, int64_t n, int channels, int mask_multi, int skip_mask_kernel,
                       double threshold, float* dots, float* grad_f, float* grad_s, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * KITTI AP evaluation (detector3d/pcdet/datasets/kitti/kitti_object_eval_python/eval.py, rotate_iou.py).  All arrays are device memory.  Frame f
+ * owns detections [dt_off[f], dt_off[f+1]) and ground truths [gt_off[f], gt_off[f+1]); its (n_dt_f, n_gt_f) overlap block starts at
+ * overlaps[ov_off[f]].  A combination c is (class, difficulty, min-overlap row): min_overlaps[c] >= 0, and combo_cd[c] names the row of the
+ * ignored_dt (rows, total_dt) / ignored_gt (rows, total_gt) int8 tables (values -1, 0, 1 of clean_data, eval.py:30-83) it uses.  The entries
+ * refuse empty work (zero frames, combinations, detections, ground truths or pairs): the caller skips the launch.
+ * ---------------------------------------------------------------------------------------------- */
+/* the most detections one frame may hold in sv_kitti_match_scores / sv_kitti_match_stats (the caller refuses more before any launch) */
+int sv_kitti_eval_max_detections(void);
+/* Ragged overlaps, one launch: segment s owns rows [row_off[s], row_off[s+1]) and columns [col_off[s], col_off[s+1]) and only its (rows, cols)
+ * block is computed, at out[out_off[s]]; total_pairs = out_off[num_segments].  metric 0: image_box_overlap (eval.py:86-113) on boxes of 4 floats,
+ * criterion -1, 0, 1; metric 1: devRotateIoUEval(col, row) (rotate_iou.py:17-260, fp32, formula for formula) on (x, z, l, w, ry), criterion -1, 0,
+ * 1, 2; metric 2: d3_box_overlap (eval.py:121-154) on (x, y, z, l, h, w, ry).  The intersection polygon holds 8 points; a candidate past that is
+ * dropped (the reference writes past its array).  One segment gives the dense (N, K) matrix of rotate_iou_gpu_eval. */
+int sv_kitti_overlaps(const float* row_boxes, const float* col_boxes, const int64_t* row_off, const int64_t* col_off, const int64_t* out_off,
+                      int num_segments, int64_t total_pairs, int metric, int criterion, float* out, void* stream);
+/* Pass 1 of compute_statistics_jit (compute_fp=False, eval.py:192-242), one wave per (frame, combination): per ground truth the unassigned, non -1
+ * detection with overlap > min_overlap and the highest score, lowest index on ties.  tp_scores (num_combos, total_gt): the caller fills it with
+ * -inf; the true-positive scores of frame f land at [c, gt_off[f] + 0, 1, ...]; tp_count (num_combos), zero on entry, gets their number. */
+int sv_kitti_match_scores(const float* overlaps, const int64_t* dt_off, const int64_t* gt_off, const int64_t* ov_off, int num_frames,
+                          const double* dt_scores, const int8_t* ignored_dt, const int8_t* ignored_gt, const int32_t* combo_cd,
+                          const double* min_overlaps, int num_combos, int64_t total_dt, int64_t total_gt, double* tp_scores, int32_t* tp_count,
+                          void* stream);
+/* get_thresholds (eval.py:9-27), one lane per combination, fp64, on rows of scores sorted in DESCENDING order of which the first counts[c] are
+ * real; num_valid_gt[c] is the combination's total_num_valid_gt.  thresholds (num_combos, 41), num_thresholds (num_combos). */
+int sv_kitti_thresholds(const double* sorted_scores, int64_t row_stride, const int32_t* counts, const int32_t* num_valid_gt, int num_combos,
+                        double* thresholds, int32_t* num_thresholds, void* stream);
+/* Pass 2 (compute_fp=True, eval.py:178-275 as fused_compute_statistics calls it), one wave per (frame, combination, threshold), then the table:
+ * table (num_combos, 41, 4) fp64 = tp, fp, fn, similarity summed over the frames, rows at or past num_thresholds[c] zero.  counts (num_combos, 41, 3)
+ * int32 zero on entry.  metric 0 subtracts the DontCare "stuff" (dt_bbox (total_dt, 4), dc_boxes with per-frame dc_off; may be NULL otherwise).
+ * compute_aos: gt_alpha / dt_alpha fp64 and sim_part (num_frames, num_combos, 41) fp64 scratch; the similarity of a frame is summed in
+ * ground-truth order and the frames in ascending order by one thread -- no float atomics, equal bits run to run. */
+int sv_kitti_match_stats(const float* overlaps, const int64_t* dt_off, const int64_t* gt_off, const int64_t* ov_off, int num_frames,
+                         const double* dt_scores, const int8_t* ignored_dt, const int8_t* ignored_gt, const int32_t* combo_cd,
+                         const double* min_overlaps, int num_combos, int64_t total_dt, int64_t total_gt, const double* thresholds,
+                         const int32_t* num_thresholds, int metric, int compute_aos, const float* dt_bbox, const float* dc_boxes,
+                         const int64_t* dc_off, const double* gt_alpha, const double* dt_alpha, int32_t* counts, double* sim_part, double* table,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
