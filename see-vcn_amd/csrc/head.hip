@@ -15,23 +15,48 @@
 
 constexpr float PI_F = 3.14159265358979323846f;
 
+// ------------------------------------------------------------------------------------------------ box codes
+// The decode and assignment kernels are written once, on a box code: anchors and boxes of 7 + E numbers, encodings of 7 + sincos + E (sincos: the
+// heading coded as cos/sin differences, ResidualCoder with encode_angle_by_sincos), ground truth rows [box7, extras, class].  PlainCode is the
+// 7-number family with slot-major anchors; its members are compile-time zeros, so its instantiations carry none of the wide code's work.
+// WideCode is the multi-head family (AnchorHeadMulti; nuScenes: code_size 9, sincos, head-major anchors).  Both instantiations evaluate every
+// output's expression in the same order, so a WideCode{0, 0, 0} launch gives the bits of the PlainCode one (-ffp-contract=off).
+constexpr int AS_MAX_GT = 128;
+constexpr int AS_MAX_GT_CODED = 256;                            // 52 B of LDS per box: 13 KiB
+
+struct PlainCode {
+  static constexpr int E = 0, sincos = 0, set_major = 0;
+  static constexpr int MAX_GT = AS_MAX_GT;
+  static constexpr bool INT32_ANCHORS = false;
+  bool ok() const { return true; }
+};
+struct WideCode {
+  int E, sincos;
+  int set_major;               // set_offset is the prefix of ANCHORS per set (each set one contiguous run), else of slots per location
+  static constexpr int MAX_GT = AS_MAX_GT_CODED;
+  static constexpr bool INT32_ANCHORS = true;                   // set_major compares the anchor index itself with the int32 prefix
+  bool ok() const { return E >= 0 && (sincos == 0 || sincos == 1) && (set_major == 0 || set_major == 1); }
+};
+
 // ------------------------------------------------------------------------------------------------ decode
+template <class Code>
 __global__ __launch_bounds__(256) void k_anchor_decode(int64_t total, int64_t A, const float* __restrict__ anchors, const float* __restrict__ enc,
                                                        const float* __restrict__ dir_logits, int num_bins, float dir_offset,
-                                                       float dir_limit_offset, float* __restrict__ out) {
+                                                       float dir_limit_offset, float* __restrict__ out, Code code) {
+  const int bw = 7 + code.E, cw = 7 + code.sincos + code.E;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const float* an = anchors + (i % A) * 7;
-    const float* t = enc + i * 7;
+    const float* an = anchors + (i % A) * bw;
+    const float* t = enc + i * cw;
     const float xa = an[0], ya = an[1], za = an[2], dxa = an[3], dya = an[4], dza = an[5], ra = an[6];
     const float diag = sqrtf(dxa * dxa + dya * dya);
-    float* o = out + i * 7;
+    float* o = out + i * bw;
     o[0] = t[0] * diag + xa;
     o[1] = t[1] * diag + ya;
     o[2] = t[2] * dza + za;
     o[3] = expf(t[3]) * dxa;
     o[4] = expf(t[4]) * dya;
     o[5] = expf(t[5]) * dza;
-    float rg = t[6] + ra;
+    float rg = code.sincos ? atan2f(t[7] + sinf(ra), t[6] + cosf(ra)) : t[6] + ra;   // box_coder_utils.py:66-73
     if (dir_logits) {
       const float* d = dir_logits + i * num_bins;
       int lab = 0;
@@ -44,19 +69,34 @@ __global__ __launch_bounds__(256) void k_anchor_decode(int64_t total, int64_t A,
       rg = rot + dir_offset + period * (float)lab;
     }
     o[6] = rg;
+    for (int k = 0; k < code.E; ++k) o[7 + k] = t[7 + code.sincos + k] + an[7 + k];
   }
+}
+
+template <class Code>
+static int anchor_decode(const char* who, Code code, const float* anchors, int64_t num_anchors, const float* box_encodings,
+                         const float* dir_cls_preds, int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out, void* stream) {
+  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && code.ok(), "%s: bad arguments", who);
+  const int64_t total = num_anchors * batch;
+  if (total == 0) return SV_OK;
+  SV_CHECK_ARG(anchors && box_encodings && out && (!dir_cls_preds || num_dir_bins >= 1), "%s: null pointer", who);
+  hipLaunchKernelGGL(k_anchor_decode<Code>, dim3(sv_grid_1d(total, 256)), dim3(256), 0, sv_stream(stream), total, num_anchors, anchors, box_encodings,
+                     dir_cls_preds, num_dir_bins, dir_offset, dir_limit_offset, out, code);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
 }
 
 extern "C" int sv_anchor_decode(const float* anchors, int64_t num_anchors, const float* box_encodings, const float* dir_cls_preds,
                                 int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out, void* stream) {
-  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0, "anchor_decode: bad arguments");
-  const int64_t total = num_anchors * batch;
-  if (total == 0) return SV_OK;
-  SV_CHECK_ARG(anchors && box_encodings && out && (!dir_cls_preds || num_dir_bins >= 1), "anchor_decode: null pointer");
-  hipLaunchKernelGGL(k_anchor_decode, dim3(sv_grid_1d(total, 256)), dim3(256), 0, sv_stream(stream), total, num_anchors, anchors, box_encodings,
-                     dir_cls_preds, num_dir_bins, dir_offset, dir_limit_offset, out);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  return anchor_decode("anchor_decode", PlainCode{}, anchors, num_anchors, box_encodings, dir_cls_preds, batch, num_dir_bins, dir_offset,
+                       dir_limit_offset, out, stream);
+}
+
+extern "C" int sv_anchor_decode_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, const float* box_encodings,
+                                      const float* dir_cls_preds, int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out,
+                                      void* stream) {
+  return anchor_decode("anchor_decode_coded", WideCode{num_extra, sincos, 0}, anchors, num_anchors, box_encodings, dir_cls_preds, batch,
+                       num_dir_bins, dir_offset, dir_limit_offset, out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ target assignment
@@ -79,41 +119,34 @@ __device__ __forceinline__ float iou_aligned(const AlignedBox& a, const AlignedB
 }
 
 struct AssignArgs {
-  const float* anchors;        // (A,7) in output order [(z,y,x), set, size, rot]
-  const float* gt;             // (B,G,8) [box7, class]
+  const float* anchors;        // (A,7+E) in output order [(z,y,x), set, size, rot], or head-major (set_major)
+  const float* gt;             // (B,G,8+E) [box7, extras, class]
   int64_t A;
   int B, G, per_loc, num_sets;
-  const int* set_offset;       // (num_sets+1) prefix of anchors per location per set
+  const int* set_offset;       // (num_sets+1) prefix of anchors per location per set (set_major: of anchors per set)
   const int* set_class;        // (num_sets) 1-based class id matched by the set's anchors
   const float* matched_thr;    // (num_sets)
   const float* unmatched_thr;  // (num_sets)
   float* gt_max;               // (B,G) scratch
   int32_t* labels;             // (B,A)
-  float* targets;              // (B,A,7)
+  float* targets;              // (B,A,7+sincos+E)
   float* reg_weights;          // (B,A)
 };
 
-constexpr int AS_MAX_GT = 128;
-
-__device__ __forceinline__ int anchor_set(const AssignArgs& a, int64_t ai) {
-  const int o = (int)(ai % a.per_loc);
-  int s = 0;
-  while (s + 1 < a.num_sets && o >= a.set_offset[s + 1]) ++s;
-  return s;
-}
-
-// grid.y = scene; GT boxes of the scene staged in LDS
-template <int PASS>
-__global__ __launch_bounds__(256) void k_assign(AssignArgs a) {
-  __shared__ AlignedBox sg[AS_MAX_GT];
-  __shared__ int scls[AS_MAX_GT];
-  __shared__ float sgmax[AS_MAX_GT];
-  __shared__ float sraw[AS_MAX_GT][7];
+// grid.y = scene; GT boxes of the scene staged in LDS.  The extras of a matched box are read from global memory (positives are few), so E is not
+// bounded by LDS.
+template <int PASS, class Code>
+__global__ __launch_bounds__(256) void k_assign(AssignArgs a, Code code) {
+  __shared__ AlignedBox sg[Code::MAX_GT];
+  __shared__ int scls[Code::MAX_GT];
+  __shared__ float sgmax[Code::MAX_GT];
+  __shared__ float sraw[Code::MAX_GT][7];
   const int b = blockIdx.y;
+  const int bw = 7 + code.E, gw = 8 + code.E, cw = 7 + code.sincos + code.E;
   for (int g = threadIdx.x; g < a.G; g += blockDim.x) {
-    const float* p = a.gt + ((int64_t)b * a.G + g) * 8;
+    const float* p = a.gt + ((int64_t)b * a.G + g) * gw;
     sg[g] = nearest_bev(p);
-    scls[g] = (int)p[7];
+    scls[g] = (int)p[gw - 1];
     for (int k = 0; k < 7; ++k) sraw[g][k] = p[k];
     if (PASS == 1) {
       const float m = a.gt_max[(int64_t)b * a.G + g];
@@ -124,8 +157,10 @@ __global__ __launch_bounds__(256) void k_assign(AssignArgs a) {
   }
   __syncthreads();
   for (int64_t ai = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ai < a.A; ai += (int64_t)gridDim.x * blockDim.x) {
-    const float* an = a.anchors + ai * 7;
-    const int s = anchor_set(a, ai);
+    const float* an = a.anchors + ai * bw;
+    const int o_in_set = code.set_major ? (int)ai : (int)(ai % a.per_loc);
+    int s = 0;
+    while (s + 1 < a.num_sets && o_in_set >= a.set_offset[s + 1]) ++s;
     const int cls = a.set_class[s];
     const AlignedBox ab = nearest_bev(an);
     float best = -1.f;
@@ -151,167 +186,6 @@ __global__ __launch_bounds__(256) void k_assign(AssignArgs a) {
         label = (force || pos) ? cls : (best < a.unmatched_thr[s] ? 0 : -1);
       }
       a.labels[o] = label;
-      float* t = a.targets + o * 7;
-      if (label > 0) {
-        // ResidualCoder.encode_torch (box_coder_utils.py:13-46)
-        const float* gtb = sraw[arg];
-        const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-        const float dxg = fmaxf(gtb[3], 1e-5f), dyg = fmaxf(gtb[4], 1e-5f), dzg = fmaxf(gtb[5], 1e-5f);
-        const float diag = sqrtf(dxa * dxa + dya * dya);
-        t[0] = (gtb[0] - an[0]) / diag;
-        t[1] = (gtb[1] - an[1]) / diag;
-        t[2] = (gtb[2] - an[2]) / dza;
-        t[3] = logf(dxg / dxa);
-        t[4] = logf(dyg / dya);
-        t[5] = logf(dzg / dza);
-        t[6] = gtb[6] - an[6];
-        a.reg_weights[o] = 1.0f;
-      } else {
-        for (int k = 0; k < 7; ++k) t[k] = 0.f;
-        a.reg_weights[o] = 0.f;
-      }
-    }
-  }
-  if (PASS == 0) {
-    __syncthreads();
-    for (int g = threadIdx.x; g < a.G; g += blockDim.x)
-      if (sgmax[g] > 0.f) atomicMax(reinterpret_cast<int*>(&a.gt_max[(int64_t)b * a.G + g]), __float_as_int(sgmax[g]));
-  }
-}
-
-extern "C" int sv_assign_targets_axis_aligned(const float* anchors, int64_t num_anchors, int anchors_per_location, int num_sets,
-                                              const int32_t* set_offset, const int32_t* set_class, const float* matched_thr,
-                                              const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt, float* gt_max_scratch,
-                                              int32_t* labels, float* reg_targets, float* reg_weights, void* stream) {
-  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && max_gt >= 0 && num_sets >= 1 && anchors_per_location >= 1, "assign_targets: bad arguments");
-  SV_CHECK_ARG(max_gt <= AS_MAX_GT, "assign_targets: at most %d ground-truth boxes per scene", AS_MAX_GT);
-  if (num_anchors == 0 || batch == 0) return SV_OK;
-  SV_CHECK_ARG(anchors && set_offset && set_class && matched_thr && unmatched_thr && labels && reg_targets && reg_weights &&
-                   (max_gt == 0 || (gt_boxes && gt_max_scratch)),
-               "assign_targets: null pointer");
-  hipStream_t st = sv_stream(stream);
-  AssignArgs a{anchors, gt_boxes, num_anchors, batch, max_gt, anchors_per_location, num_sets, set_offset, set_class, matched_thr, unmatched_thr,
-               gt_max_scratch, labels, reg_targets, reg_weights};
-  dim3 grid(sv_grid_1d(num_anchors, 256, 512), batch);
-  if (max_gt > 0) {
-    SV_HIP(hipMemsetAsync(gt_max_scratch, 0, (size_t)batch * max_gt * 4, st));
-    hipLaunchKernelGGL(k_assign<0>, grid, dim3(256), 0, st, a);
-  }
-  hipLaunchKernelGGL(k_assign<1>, grid, dim3(256), 0, st, a);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ coded boxes, head-major anchors
-// The multi-head anchor family (AnchorHeadMulti; nuScenes: ResidualCoder code_size 9 with the heading coded as cos/sin differences) needs
-// boxes of 7 + E numbers, encodings of 7 + sincos + E, and anchors laid out head-major.  With E = 0, sincos = 0, set_major = 0 the entries
-// below evaluate the expressions of k_anchor_decode / k_assign in the same order: the same bits.
-__global__ __launch_bounds__(256) void k_anchor_decode_coded(int64_t total, int64_t A, int E, int sincos, const float* __restrict__ anchors,
-                                                             const float* __restrict__ enc, const float* __restrict__ dir_logits, int num_bins,
-                                                             float dir_offset, float dir_limit_offset, float* __restrict__ out) {
-  const int bw = 7 + E, cw = 7 + sincos + E;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const float* an = anchors + (i % A) * bw;
-    const float* t = enc + i * cw;
-    const float xa = an[0], ya = an[1], za = an[2], dxa = an[3], dya = an[4], dza = an[5], ra = an[6];
-    const float diag = sqrtf(dxa * dxa + dya * dya);
-    float* o = out + i * bw;
-    o[0] = t[0] * diag + xa;
-    o[1] = t[1] * diag + ya;
-    o[2] = t[2] * dza + za;
-    o[3] = expf(t[3]) * dxa;
-    o[4] = expf(t[4]) * dya;
-    o[5] = expf(t[5]) * dza;
-    float rg = sincos ? atan2f(t[7] + sinf(ra), t[6] + cosf(ra)) : t[6] + ra;        // box_coder_utils.py:66-73
-    if (dir_logits) {
-      const float* d = dir_logits + i * num_bins;
-      int lab = 0;
-      float best = d[0];
-      for (int k = 1; k < num_bins; ++k)
-        if (d[k] > best) { best = d[k]; lab = k; }
-      const float period = 2.0f * PI_F / (float)num_bins;
-      const float val = rg - dir_offset;
-      const float rot = val - floorf(val / period + dir_limit_offset) * period;
-      rg = rot + dir_offset + period * (float)lab;
-    }
-    o[6] = rg;
-    for (int k = 0; k < E; ++k) o[7 + k] = t[7 + sincos + k] + an[7 + k];
-  }
-}
-
-extern "C" int sv_anchor_decode_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, const float* box_encodings,
-                                      const float* dir_cls_preds, int batch, int num_dir_bins, float dir_offset, float dir_limit_offset, float* out,
-                                      void* stream) {
-  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && num_extra >= 0 && (sincos == 0 || sincos == 1), "anchor_decode_coded: bad arguments");
-  const int64_t total = num_anchors * batch;
-  if (total == 0) return SV_OK;
-  SV_CHECK_ARG(anchors && box_encodings && out && (!dir_cls_preds || num_dir_bins >= 1), "anchor_decode_coded: null pointer");
-  hipLaunchKernelGGL(k_anchor_decode_coded, dim3(sv_grid_1d(total, 256)), dim3(256), 0, sv_stream(stream), total, num_anchors, num_extra, sincos,
-                     anchors, box_encodings, dir_cls_preds, num_dir_bins, dir_offset, dir_limit_offset, out);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-struct AssignCodedArgs {
-  AssignArgs a;                // anchors (A,7+E); gt (B,G,8+E) [box7, extras, class]; targets (B,A,7+sincos+E)
-  int E, sincos, set_major;    // set_major: set_offset is the prefix of ANCHORS per set (each set one contiguous run), else of slots per location
-};
-
-constexpr int AS_MAX_GT_CODED = 256;                            // 52 B of LDS per box: 13 KiB
-
-// the two passes of k_assign; the extras of a matched box are read from global memory (positives are few), so E is not bounded by LDS
-template <int PASS>
-__global__ __launch_bounds__(256) void k_assign_coded(AssignCodedArgs c) {
-  const AssignArgs& a = c.a;
-  __shared__ AlignedBox sg[AS_MAX_GT_CODED];
-  __shared__ int scls[AS_MAX_GT_CODED];
-  __shared__ float sgmax[AS_MAX_GT_CODED];
-  __shared__ float sraw[AS_MAX_GT_CODED][7];
-  const int b = blockIdx.y;
-  const int bw = 7 + c.E, gw = 8 + c.E, cw = 7 + c.sincos + c.E;
-  for (int g = threadIdx.x; g < a.G; g += blockDim.x) {
-    const float* p = a.gt + ((int64_t)b * a.G + g) * gw;
-    sg[g] = nearest_bev(p);
-    scls[g] = (int)p[gw - 1];
-    for (int k = 0; k < 7; ++k) sraw[g][k] = p[k];
-    if (PASS == 1) {
-      const float m = a.gt_max[(int64_t)b * a.G + g];
-      sgmax[g] = m == 0.f ? -1.f : m;
-    } else {
-      sgmax[g] = 0.f;
-    }
-  }
-  __syncthreads();
-  for (int64_t ai = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ai < a.A; ai += (int64_t)gridDim.x * blockDim.x) {
-    const float* an = a.anchors + ai * bw;
-    const int o_in_set = c.set_major ? (int)ai : (int)(ai % a.per_loc);
-    int s = 0;
-    while (s + 1 < a.num_sets && o_in_set >= a.set_offset[s + 1]) ++s;
-    const int cls = a.set_class[s];
-    const AlignedBox ab = nearest_bev(an);
-    float best = -1.f;
-    int arg = -1;
-    bool force = false;
-    for (int g = 0; g < a.G; ++g) {
-      if (scls[g] != cls) continue;
-      const float v = iou_aligned(ab, sg[g]);
-      if (PASS == 0) {
-        if (v > 0.f) atomicMax(reinterpret_cast<int*>(&sgmax[g]), __float_as_int(v));
-      } else {
-        if (v > best) { best = v; arg = g; }
-        force = force || (v == sgmax[g]);
-      }
-    }
-    if (PASS == 1) {
-      const int64_t o = (int64_t)b * a.A + ai;
-      int label;
-      if (arg < 0) {
-        label = 0;
-      } else {
-        const bool pos = best >= a.matched_thr[s];
-        label = (force || pos) ? cls : (best < a.unmatched_thr[s] ? 0 : -1);
-      }
-      a.labels[o] = label;
       float* t = a.targets + o * cw;
       if (label > 0) {
         // ResidualCoder.encode_torch (box_coder_utils.py:13-46)
@@ -325,14 +199,14 @@ __global__ __launch_bounds__(256) void k_assign_coded(AssignCodedArgs c) {
         t[3] = logf(dxg / dxa);
         t[4] = logf(dyg / dya);
         t[5] = logf(dzg / dza);
-        if (c.sincos) {
+        if (code.sincos) {
           t[6] = cosf(gtb[6]) - cosf(an[6]);
           t[7] = sinf(gtb[6]) - sinf(an[6]);
         } else {
           t[6] = gtb[6] - an[6];
         }
         const float* ge = a.gt + ((int64_t)b * a.G + arg) * gw + 7;
-        for (int k = 0; k < c.E; ++k) t[7 + c.sincos + k] = ge[k] - an[7 + k];
+        for (int k = 0; k < code.E; ++k) t[7 + code.sincos + k] = ge[k] - an[7 + k];
         a.reg_weights[o] = 1.0f;
       } else {
         for (int k = 0; k < cw; ++k) t[k] = 0.f;
@@ -347,31 +221,46 @@ __global__ __launch_bounds__(256) void k_assign_coded(AssignCodedArgs c) {
   }
 }
 
+template <class Code>
+static int assign_targets(const char* who, Code code, const float* anchors, int64_t num_anchors, int anchors_per_location, int num_sets,
+                          const int32_t* set_offset, const int32_t* set_class, const float* matched_thr, const float* unmatched_thr,
+                          const float* gt_boxes, int batch, int max_gt, float* gt_max_scratch, int32_t* labels, float* reg_targets,
+                          float* reg_weights, void* stream) {
+  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && max_gt >= 0 && num_sets >= 1 && anchors_per_location >= 1 && code.ok(), "%s: bad arguments", who);
+  SV_CHECK_ARG(max_gt <= Code::MAX_GT, "%s: at most %d ground-truth boxes per scene", who, Code::MAX_GT);
+  SV_CHECK_ARG(!Code::INT32_ANCHORS || num_anchors < ((int64_t)1 << 31), "%s: anchor index exceeds int32", who);
+  if (num_anchors == 0 || batch == 0) return SV_OK;
+  SV_CHECK_ARG(anchors && set_offset && set_class && matched_thr && unmatched_thr && labels && reg_targets && reg_weights &&
+                   (max_gt == 0 || (gt_boxes && gt_max_scratch)),
+               "%s: null pointer", who);
+  hipStream_t st = sv_stream(stream);
+  AssignArgs a{anchors, gt_boxes, num_anchors, batch, max_gt, anchors_per_location, num_sets, set_offset, set_class, matched_thr, unmatched_thr,
+               gt_max_scratch, labels, reg_targets, reg_weights};
+  dim3 grid(sv_grid_1d(num_anchors, 256, 512), batch);
+  if (max_gt > 0) {
+    SV_HIP(hipMemsetAsync(gt_max_scratch, 0, (size_t)batch * max_gt * 4, st));
+    hipLaunchKernelGGL((k_assign<0, Code>), grid, dim3(256), 0, st, a, code);
+  }
+  hipLaunchKernelGGL((k_assign<1, Code>), grid, dim3(256), 0, st, a, code);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+extern "C" int sv_assign_targets_axis_aligned(const float* anchors, int64_t num_anchors, int anchors_per_location, int num_sets,
+                                              const int32_t* set_offset, const int32_t* set_class, const float* matched_thr,
+                                              const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt, float* gt_max_scratch,
+                                              int32_t* labels, float* reg_targets, float* reg_weights, void* stream) {
+  return assign_targets("assign_targets", PlainCode{}, anchors, num_anchors, anchors_per_location, num_sets, set_offset, set_class, matched_thr,
+                        unmatched_thr, gt_boxes, batch, max_gt, gt_max_scratch, labels, reg_targets, reg_weights, stream);
+}
+
 extern "C" int sv_assign_targets_axis_aligned_coded(const float* anchors, int64_t num_anchors, int num_extra, int sincos, int set_major,
                                                     int anchors_per_location, int num_sets, const int32_t* set_offset, const int32_t* set_class,
                                                     const float* matched_thr, const float* unmatched_thr, const float* gt_boxes, int batch, int max_gt,
                                                     float* gt_max_scratch, int32_t* labels, float* reg_targets, float* reg_weights, void* stream) {
-  SV_CHECK_ARG(num_anchors >= 0 && batch >= 0 && max_gt >= 0 && num_sets >= 1 && anchors_per_location >= 1 && num_extra >= 0 &&
-                   (sincos == 0 || sincos == 1) && (set_major == 0 || set_major == 1),
-               "assign_targets_coded: bad arguments");
-  SV_CHECK_ARG(max_gt <= AS_MAX_GT_CODED, "assign_targets_coded: at most %d ground-truth boxes per scene", AS_MAX_GT_CODED);
-  SV_CHECK_ARG(num_anchors < ((int64_t)1 << 31), "assign_targets_coded: anchor index exceeds int32");
-  if (num_anchors == 0 || batch == 0) return SV_OK;
-  SV_CHECK_ARG(anchors && set_offset && set_class && matched_thr && unmatched_thr && labels && reg_targets && reg_weights &&
-                   (max_gt == 0 || (gt_boxes && gt_max_scratch)),
-               "assign_targets_coded: null pointer");
-  hipStream_t st = sv_stream(stream);
-  AssignCodedArgs c{{anchors, gt_boxes, num_anchors, batch, max_gt, anchors_per_location, num_sets, set_offset, set_class, matched_thr, unmatched_thr,
-                     gt_max_scratch, labels, reg_targets, reg_weights},
-                    num_extra, sincos, set_major};
-  dim3 grid(sv_grid_1d(num_anchors, 256, 512), batch);
-  if (max_gt > 0) {
-    SV_HIP(hipMemsetAsync(gt_max_scratch, 0, (size_t)batch * max_gt * 4, st));
-    hipLaunchKernelGGL(k_assign_coded<0>, grid, dim3(256), 0, st, c);
-  }
-  hipLaunchKernelGGL(k_assign_coded<1>, grid, dim3(256), 0, st, c);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  return assign_targets("assign_targets_coded", WideCode{num_extra, sincos, set_major}, anchors, num_anchors, anchors_per_location, num_sets,
+                        set_offset, set_class, matched_thr, unmatched_thr, gt_boxes, batch, max_gt, gt_max_scratch, labels, reg_targets, reg_weights,
+                        stream);
 }
 
 // ------------------------------------------------------------------------------------------------

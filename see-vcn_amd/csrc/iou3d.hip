@@ -187,13 +187,9 @@ extern "C" int sv_boxes_iou3d_batch(const float* boxes_a, int num_a, int stride_
 }
 
 // ------------------------------------------------------------------ NMS: suppression masks (upper triangle)
-// one wave per 64x64 tile; lane = column box; each row contributes one ballot word
-// (row blocks rb0 + blockIdx.y of a chunked sweep; `done` non-null and set = an earlier chunk already kept max_keep boxes: nothing to do)
-__global__ __launch_bounds__(64) void k_nms_mask(int n, float thresh, const float* __restrict__ boxes, unsigned long long* __restrict__ mask,
-                                                 int col_blocks, int normal, int rb0, const int32_t* __restrict__ done) {
-  if (done && *done) return;
-  const int rb = rb0 + blockIdx.y, cb = blockIdx.x;
-  if (cb < rb) return;                                       // the sweep never reads words left of the diagonal
+// one wave per 64x64 tile (row block rb, column block cb >= rb) of the n boxes at `boxes`; lane = column box; each row contributes one ballot word
+__device__ __forceinline__ void nms_mask_tile(int n, int rb, int cb, const float* __restrict__ boxes, unsigned long long* __restrict__ mask,
+                                              int col_blocks, float thresh, int normal) {
   const int lane = threadIdx.x;
   const int col = cb * 64 + lane;
   const bool col_ok = col < n;
@@ -214,6 +210,15 @@ __global__ __launch_bounds__(64) void k_nms_mask(int n, float thresh, const floa
   }
 }
 
+// (row blocks rb0 + blockIdx.y of a chunked sweep; `done` non-null and set = an earlier chunk already kept max_keep boxes: nothing to do)
+__global__ __launch_bounds__(64) void k_nms_mask(int n, float thresh, const float* __restrict__ boxes, unsigned long long* __restrict__ mask,
+                                                 int col_blocks, int normal, int rb0, const int32_t* __restrict__ done) {
+  if (done && *done) return;
+  const int rb = rb0 + blockIdx.y, cb = blockIdx.x;
+  if (cb < rb) return;                                       // the sweep never reads words left of the diagonal
+  nms_mask_tile(n, rb, cb, boxes, mask, col_blocks, thresh, normal);
+}
+
 // greedy sweep on the device: one workgroup, removal bitmap in LDS (n <= 65536).  Per block of 64 boxes wave 0 resolves the block against
 // itself (diagonal word of each row, 64 serial steps on registers), then all four waves fold the kept rows into the words of the later
 // blocks (lanes over words: every row read is one coalesced run).  The sweep stops once max_keep boxes are kept: callers that only take the
@@ -221,6 +226,25 @@ __global__ __launch_bounds__(64) void k_nms_mask(int n, float thresh, const floa
 // (9000 proposals at threshold 0.8, 512 wanted: 4.3 ms -> 0.3 ms).
 constexpr int NMS_MAX_WORDS = 1024;
 constexpr int NMS_SWEEP_THREADS = 256;
+
+// One wave resolves block nb (`rows` boxes) against itself.  cur: the block's word of the removal bitmap; diag: this lane's row of the
+// block's diagonal mask word (0 beyond `rows`).  64 serial steps on registers give the kept rows as a bit set, the same in every lane; lane r
+// writes kept row r into keep[] at its rank behind the kept_total boxes kept so far, as long as that is below max_keep.
+__device__ __forceinline__ unsigned long long nms_resolve_block(unsigned long long cur, unsigned long long diag, int nb, int rows, int kept_total,
+                                                                int max_keep, int64_t* __restrict__ keep) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long keptbits = 0ull;
+  for (int r = 0; r < rows; ++r) {
+    const unsigned long long d = __shfl(diag, r, 64);
+    if (!((cur >> r) & 1ull)) {
+      keptbits |= 1ull << r;
+      cur |= d;
+    }
+  }
+  const int slot = kept_total + __popcll(keptbits & ((1ull << lane) - 1ull));
+  if (((keptbits >> lane) & 1ull) && slot < max_keep) keep[slot] = (int64_t)nb * 64 + lane;
+  return keptbits;
+}
 // nb0 .. nb1: the blocks this launch resolves.  A whole sweep is one launch (nb0 = 0, nb1 = col_blocks, state = null); a CHUNKED sweep is
 // a sequence of launches that carry the removal bitmap and the kept count in `state` ([0] kept so far, [1] done flag, then the bitmap
 // words) -- the mask rows of a chunk are computed right before its launch and not at all once max_keep is reached (k_nms_mask checks the
@@ -242,18 +266,8 @@ __global__ __launch_bounds__(NMS_SWEEP_THREADS) void k_nms_sweep(int n, const un
   for (int nb = nb0; nb < nb1 && kept_total < max_keep; ++nb) {
     if (tid < 64) {
       const int rows = min(64, n - nb * 64);
-      unsigned long long cur = remv[nb];
       const unsigned long long diag = lane < rows ? mask[(int64_t)(nb * 64 + lane) * col_blocks + nb] : 0ull;
-      unsigned long long keptbits = 0ull;
-      for (int r = 0; r < rows; ++r) {
-        const unsigned long long d = __shfl(diag, r, 64);
-        if (!((cur >> r) & 1ull)) {
-          keptbits |= 1ull << r;
-          cur |= d;
-        }
-      }
-      const int slot = kept_total + __popcll(keptbits & ((1ull << lane) - 1ull));
-      if (((keptbits >> lane) & 1ull) && slot < max_keep) keep[slot] = (int64_t)nb * 64 + lane;
+      const unsigned long long keptbits = nms_resolve_block(remv[nb], diag, nb, rows, kept_total, max_keep, keep);
       if (lane == 0) s_kept = keptbits;
     }
     __syncthreads();
@@ -343,24 +357,7 @@ __global__ __launch_bounds__(64) void k_nms_seg_mask(const int32_t* __restrict__
   if (cb < rb || cb * 64 >= n) return;                         // left of the diagonal, or beyond the segment's rows (cb >= rb here, so this covers rb * 64 >= n)
   boxes += (int64_t)s * seg_stride * 7;
   mask += (int64_t)s * seg_stride * col_blocks;
-  const int lane = threadIdx.x;
-  const int col = cb * 64 + lane;
-  const bool col_ok = col < n;
-  float cbox[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) cbox[k] = col_ok ? boxes[(int64_t)col * 7 + k] : 0.f;
-  const RBox c = make_rbox(cbox);
-  const int rows = min(64, n - rb * 64);
-  for (int r = 0; r < rows; ++r) {
-    const int row = rb * 64 + r;
-    float rbox[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) rbox[k] = boxes[(int64_t)row * 7 + k];   // wave-uniform address: one broadcast load
-    bool sup = false;
-    if (col_ok && col > row) sup = (normal ? iou_axis_aligned(rbox, cbox) : iou_bev(make_rbox(rbox), c)) > thresh;
-    const unsigned long long w = __ballot(sup);
-    if (lane == 0) mask[(int64_t)row * col_blocks + cb] = w;
-  }
+  nms_mask_tile(n, rb, cb, boxes, mask, col_blocks, thresh, normal);
 }
 
 // greedy sweep of one segment by one wave: the removal bitmap (<= 64 words) in LDS, lane j owns word j.  Per block of 64 boxes the diagonal
@@ -380,18 +377,8 @@ __global__ __launch_bounds__(64) void k_nms_seg_sweep(const int32_t* __restrict_
   int kept_total = 0;
   for (int nb = 0; nb < nblk && kept_total < max_keep; ++nb) {
     const int rows = min(64, n - nb * 64);
-    unsigned long long cur = remv[nb];
     const unsigned long long diag = lane < rows ? mask[(int64_t)(nb * 64 + lane) * col_blocks + nb] : 0ull;
-    unsigned long long keptbits = 0ull;
-    for (int r = 0; r < rows; ++r) {
-      const unsigned long long d = __shfl(diag, r, 64);
-      if (!((cur >> r) & 1ull)) {
-        keptbits |= 1ull << r;
-        cur |= d;
-      }
-    }
-    const int slot = kept_total + __popcll(keptbits & ((1ull << lane) - 1ull));
-    if (((keptbits >> lane) & 1ull) && slot < max_keep) keep[slot] = (int64_t)nb * 64 + lane;
+    const unsigned long long keptbits = nms_resolve_block(remv[nb], diag, nb, rows, kept_total, max_keep, keep);
     kept_total += __popcll(keptbits);
     const int j = nb + 1 + lane;                                // this lane's word of the later blocks
     if (kept_total < max_keep && j < nblk) {
@@ -460,7 +447,7 @@ __global__ __launch_bounds__(256) void k_points_in_boxes(int T, int M, const flo
   for (int k = 0; k < T; ++k) {
     const float* s = sbox + k * 8;
     float lx, ly;
-    if (sv_pt_in_box3d(x, y, z, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], lx, ly)) { found = k; break; }
+    if (sv_pt_in_box3d(x, y, z, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], 1e-5f, lx, ly)) { found = k; break; }
   }
   out[(int64_t)b * M + m] = found;
 }
@@ -483,14 +470,9 @@ __global__ __launch_bounds__(256) void k_points_in_boxes_matrix(int N, int M, co
   if (j >= M) return;
   const float* b = boxes + (size_t)i * 7;
   const float x = pts[(size_t)j * 3], y = pts[(size_t)j * 3 + 1], z = pts[(size_t)j * 3 + 2];
-  int in = 0;
-  if (!(fabsf(z - b[2]) > b[5] / 2.0)) {
-    const float cosa = cosf(-b[6]), sina = sinf(-b[6]);
-    const float sx = x - b[0], sy = y - b[1];
-    const float lx = sx * cosa + sy * (-sina), ly = sx * sina + sy * cosa;
-    in = (fabs(lx) < b[3] / 2.0 + (double)1e-2f && fabs(ly) < b[4] / 2.0 + (double)1e-2f) ? 1 : 0;
-  }
-  out[(size_t)i * M + j] = in;
+  float lx, ly;                                              // no table of boxes here: cosf / sinf only for the points that pass z
+  const bool in = sv_pt_in_box_z(z, b[2], b[5]) && sv_pt_in_box_xy(x, y, b[0], b[1], b[3], b[4], cosf(-b[6]), sinf(-b[6]), 1e-2f, lx, ly);
+  out[(size_t)i * M + j] = in ? 1 : 0;
 }
 
 extern "C" int sv_points_in_boxes_matrix(const float* boxes, const float* pts, int num_boxes, int num_points, int32_t* out, void* stream) {

@@ -8,6 +8,7 @@
 // Index lists come out in ascending point order (numpy boolean indexing / np.argwhere order); all geometry in float64 like
 // numpy / Eigen.  One workgroup per box / instance.
 #include "common.h"
+#include "union_find.h"
 
 #define ISO_THREADS 1024
 #define ISO_WAVES (ISO_THREADS / SV_WAVE)
@@ -249,16 +250,6 @@ struct IsoArgs {
   int64_t max_points;
 };
 
-__device__ __forceinline__ int iso_find(volatile int* parent, int x) {
-  int p = parent[x];
-  while (p != x) {
-    const int g = parent[p];
-    if (g != p) parent[x] = g;       // path halving (parents only ever decrease)
-    x = p, p = g;
-  }
-  return x;
-}
-
 __global__ __launch_bounds__(ISO_THREADS) void k_isolate_cluster(IsoArgs a) {
   __shared__ float s_xyz[ISO_LDS_N * 3];
   __shared__ int s_parent[ISO_LDS_N], s_aux[ISO_LDS_N], s_lab[ISO_LDS_N];
@@ -326,14 +317,8 @@ __global__ __launch_bounds__(ISO_THREADS) void k_isolate_cluster(IsoArgs a) {
     for (int j = i + 1; j < n; ++j) {
       const double dx = (double)xyz[j * 3] - x, dy = (double)xyz[j * 3 + 1] - y, dz = (double)xyz[j * 3 + 2] - z;
       if (dx * dx + dy * dy + dz * dz < eps2 && aux[j] >= a.min_points && parent[j] != my_parent) {
-        int ra = i, rb = j;
-        while (true) {
-          ra = iso_find(parent, ra), rb = iso_find(parent, rb);
-          if (ra == rb) break;
-          if (ra > rb) { const int t = ra; ra = rb; rb = t; }
-          if (atomicCAS(&parent[rb], rb, ra) == rb) break;
-        }
-        my_parent = iso_find(parent, i);
+        sv_uf_union(parent, i, j);
+        my_parent = sv_uf_find(parent, i);
       }
     }
   }
@@ -341,7 +326,7 @@ __global__ __launch_bounds__(ISO_THREADS) void k_isolate_cluster(IsoArgs a) {
   for (int i = tid; i < n; i += ISO_THREADS) {
     int l = -1;
     if (aux[i] >= a.min_points) {
-      l = iso_find(parent, i);
+      l = sv_uf_find(parent, i);
     } else if (aux[i] >= 2) {                 // border candidate: the smallest cluster among the cores within eps
       const double x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
       int best = 0x7fffffff;
@@ -349,7 +334,7 @@ __global__ __launch_bounds__(ISO_THREADS) void k_isolate_cluster(IsoArgs a) {
         if (aux[j] < a.min_points) continue;
         const double dx = (double)xyz[j * 3] - x, dy = (double)xyz[j * 3 + 1] - y, dz = (double)xyz[j * 3 + 2] - z;
         if (dx * dx + dy * dy + dz * dz < eps2) {
-          const int r = iso_find(parent, j);
+          const int r = sv_uf_find(parent, j);
           best = r < best ? r : best;
         }
       }

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "union_find.h"
 #include "wave.h"
 
 #define PP_MAXN 1024     // points per object (resample_num and the network's coarse size)
@@ -336,16 +337,6 @@ struct ClusterArgs {
                         // returns); a HINT: verified on the device, a cloud that does not repeat takes the all-pairs path
 };
 
-__device__ __forceinline__ int uf_find(volatile int* parent, int x) {
-  int p = parent[x];
-  while (p != x) {
-    const int g = parent[p];
-    if (g != p) parent[x] = g;       // path halving (parents only ever decrease)
-    x = p, p = g;
-  }
-  return x;
-}
-
 __global__ __launch_bounds__(PP_THREADS) void k_largest_cluster(ClusterArgs a) {
   __shared__ float s_x[PP_MAXN * 3];
   __shared__ int s_parent[PP_MAXN];
@@ -402,14 +393,8 @@ __global__ __launch_bounds__(PP_THREADS) void k_largest_cluster(ClusterArgs a) {
         has_nbr = true;
         s_core[j] = 1;
         if (pj != my_parent) {
-          int ra = tid, rb = j;
-          while (true) {
-            ra = uf_find(s_parent, ra), rb = uf_find(s_parent, rb);
-            if (ra == rb) break;
-            if (ra > rb) { const int t = ra; ra = rb; rb = t; }
-            if (atomicCAS(&s_parent[rb], rb, ra) == rb) break;
-          }
-          my_parent = uf_find(s_parent, tid);
+          sv_uf_union(s_parent, tid, j);
+          my_parent = sv_uf_find(s_parent, tid);
         }
       }
     }
@@ -418,7 +403,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_largest_cluster(ClusterArgs a) {
   __syncthreads();
   int root = -1;
   if (tid < a.n && (s_core[tid] || a.min_points <= 1)) {
-    root = uf_find(s_parent, tid);
+    root = sv_uf_find(s_parent, tid);
     atomicAdd(&s_cnt[root], 1);
   }
   __syncthreads();

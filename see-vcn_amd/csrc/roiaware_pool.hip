@@ -48,7 +48,7 @@ __global__ __launch_bounds__(RA_THREADS) void k_roiaware_assign(const float* __r
     if (p < hi) {
       const float x = pts[(int64_t)p * 3], y = pts[(int64_t)p * 3 + 1], z = pts[(int64_t)p * 3 + 2];
       float lx = 0.f, ly = 0.f;
-      in = sv_pt_in_box3d(x, y, z, cx, cy, cz, dx, dy, dz, cosa, sina, lx, ly);
+      in = sv_pt_in_box3d(x, y, z, cx, cy, cz, dx, dy, dz, cosa, sina, 1e-5f, lx, ly);
       if (in) {
         const float lz = z - cz;
         int xi = (int)((lx + dx / 2) / x_res), yi = (int)((ly + dy / 2) / y_res), zi = (int)((lz + dz / 2) / z_res);

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(RP_THREADS) void k_roipoint_pool(const float* __res
       in[u] = false;
       if (p < n_pts) {
         float lx, ly;
-        in[u] = sv_pt_in_box3d(pts[(int64_t)p * 3], pts[(int64_t)p * 3 + 1], pts[(int64_t)p * 3 + 2], cx, cy, cz, dx, dy, dz, cosa, sina, lx, ly);
+        in[u] = sv_pt_in_box3d(pts[(int64_t)p * 3], pts[(int64_t)p * 3 + 1], pts[(int64_t)p * 3 + 2], cx, cy, cz, dx, dy, dz, cosa, sina, 1e-5f, lx, ly);
       }
       int total;
       rank[u] = sv_wave_ballot_rank(in[u], &total);
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(RP_THREADS) void k_roipoint_pool(const float* __res
         } else {
           const float z = pts[p * 3 + 2];
           float lx = 0.f, ly = 0.f;
-          (void)sv_pt_in_box3d(pts[p * 3], pts[p * 3 + 1], z, cx, cy, cz, dx, dy, dz, cosa, sina, lx, ly);
+          (void)sv_pt_in_box3d(pts[p * 3], pts[p * 3 + 1], z, cx, cy, cz, dx, dy, dz, cosa, sina, 1e-5f, lx, ly);
           v[u] = j == 0 ? lx : j == 1 ? ly : z - cz;
         }
       }

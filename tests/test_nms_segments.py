@@ -81,6 +81,28 @@ def wide_case():
     return counts, boxes, ref
 
 
+TWIN_SIZES = (1, 64, 65, 130)            # below, at and across a block edge, and a short last block
+
+
+@functools.lru_cache(maxsize=None)
+def twin_case(n):
+    """one score-sorted set of n decided boxes for both NMS families, with the oracle's keep list per `normal`"""
+    boxes = decided_boxes(np.random.default_rng(7000 + n), n, 2.2 * np.sqrt(n) + 4.0)
+    return boxes, {normal: ob.nms(boxes, THRESH, normal=bool(normal)) for normal in (0, 1)}
+
+
+def run_prefix(hip_lib, cuda, boxes, normal, max_keep):
+    import seevcn_amd._lib as L
+    n = len(boxes)
+    b = torch.from_numpy(boxes).to(cuda)
+    keep = torch.full((max_keep,), -7, dtype=torch.int64, device=cuda)
+    num = torch.full((1,), -7, dtype=torch.int32, device=cuda)
+    scratch = torch.empty((hip_lib.sv_nms_scratch_bytes(n),), dtype=torch.uint8, device=cuda)
+    rc = hip_lib.sv_nms_prefix(L.ptr(b), n, THRESH, normal, max_keep, L.ptr(scratch), L.ptr(keep), L.ptr(num), L.stream())
+    L.check(rc, "sv_nms_prefix")
+    return keep.cpu().numpy(), int(num.cpu().numpy()[0])
+
+
 def run_segments(hip_lib, cuda, boxes, counts, normal, max_keep):
     import seevcn_amd._lib as L
     S, stride = boxes.shape[:2]
@@ -111,6 +133,29 @@ def test_cases_are_decided_and_suppress():
     for s, n in enumerate(counts[2:], start=2):
         iou = ob.boxes_iou_bev(boxes[s, :n], boxes[s, :n])
         assert np.abs(iou - THRESH).min() > MARGIN
+    for n in TWIN_SIZES:
+        boxes, ref = twin_case(n)
+        assert np.abs(ob.boxes_iou_bev(boxes, boxes) - THRESH).min() > MARGIN
+        assert min(np.abs(_iou_normal(boxes[i], boxes) - THRESH).min() for i in range(n)) > MARGIN
+        for normal in (0, 1):
+            assert 1 <= len(ref[normal]) <= n and (n < 64 or len(ref[normal]) < n), (n, normal, len(ref[normal]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("keep_two", [False, True])
+@pytest.mark.parametrize("normal", [0, 1])
+@pytest.mark.parametrize("n", TWIN_SIZES)
+def test_hip_nms_prefix_and_one_segment_keep_the_same_boxes(cuda, hip_lib, n, normal, keep_two):
+    """The two NMS families share the mask tile and the in-block resolve: the same score-sorted boxes through sv_nms_prefix and through
+    sv_nms_segments as its only segment (S = 1, seg_stride = n) give the same count and the same keep list, which is the oracle's."""
+    boxes, ref = twin_case(n)
+    max_keep = 2 if keep_two else n
+    keep_p, num_p = run_prefix(hip_lib, cuda, boxes, normal, max_keep)
+    keep_s, num_s = run_segments(hip_lib, cuda, boxes[None], [n], normal, max_keep)
+    assert num_p == num_s[0]
+    assert np.array_equal(keep_p[:num_p], keep_s[0, :num_p])
+    check(keep_s, num_s, [ref[normal]], max_keep)
+    assert (keep_p[num_p:] == -7).all()
 
 
 @pytest.mark.gpu
