@@ -828,6 +828,26 @@ int sv_three_interpolate_batch(int batch, int c, int m, int n, const float* poin
                                void* stream);
 int sv_three_interpolate_grad_batch(int batch, int c, int n, int m, const float* grad_out, const int32_t* idx, const float* weight,
                                     float* grad_points, void* stream);
+/* The three batch gradients with a fixed summation order (opt-in): no float atomics, no zero-fill, every element of grad_points written once.
+ * group / gather: grad_out (B, c, per), per = npoints * nsample (gather: nsample = 1), idx (B, per), grad_points (B, c, n):
+ *   grad_points[b][ch][i] = +0.0f + grad_out[b][ch][j]                     summed in ascending j over the j in [0, per) with idx[b][j] == i
+ * three-interpolate: grad_out (B, c, n), idx / weight (B, n, 3), grad_points (B, c, m):
+ *   grad_points[b][ch][i] = +0.0f + fp32(grad_out[b][ch][p] * weight[b][p][t])   summed in ascending key 3 p + t over the keys with idx[b][p][t] == i
+ * every product and every sum rounded to fp32, no FMA: the very terms the atomic kernels add.  Two slots of one p that name the same row are
+ * two keys like any others.  A row no key names is +0.0f and no element is ever -0.0f.  An index outside [0, n) ([0, m) for interpolation)
+ * names nothing in ANY batch element (the plain entries trust their indices).  batch, c or the row count <= 0: SV_OK, nothing written;
+ * per == 0 (n == 0 for interpolation): +0.0f everywhere.
+ * scratch (uninitialised): the inverse lists of keys = B * per (3 * B * n) over rows = B * n (B * m), 16 + 4 * (2 * rows + 2 * keys) bytes;
+ * keys or rows >= 2^31 are an error, never the atomic route (the scratch function then returns 0). */
+size_t sv_group_points_grad_batch_ordered_scratch_bytes(int batch, int n, int npoints, int nsample);
+int sv_group_points_grad_batch_ordered(int batch, int c, int n, int npoints, int nsample, const float* grad_out, const int32_t* idx,
+                                       void* scratch, float* grad_points, void* stream);
+size_t sv_gather_points_grad_batch_ordered_scratch_bytes(int batch, int n, int npoints);
+int sv_gather_points_grad_batch_ordered(int batch, int c, int n, int npoints, const float* grad_out, const int32_t* idx, void* scratch,
+                                        float* grad_points, void* stream);
+size_t sv_three_interpolate_grad_batch_ordered_scratch_bytes(int batch, int n, int m);
+int sv_three_interpolate_grad_batch_ordered(int batch, int c, int n, int m, const float* grad_out, const int32_t* idx, const float* weight,
+                                            void* scratch, float* grad_points, void* stream);
 
 /* ---- launch-list executor (csrc/sequencer.hip): enqueue a list of this library's operations with ONE call.  An operation is SV_OP_WORDS int64:
  *   [0] code   [1..8] eight small integers i0..i7   [9..12] four sizes / strides n0..n3   [13..16] four doubles (bit patterns) f0..f3

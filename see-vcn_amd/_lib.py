@@ -210,7 +210,13 @@ SIGNATURES = {
     "sv_three_nn_batch": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_three_interpolate_batch": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_three_interpolate_grad_batch": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "sv_chamfer_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_group_points_grad_batch_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "sv_group_points_grad_batch_ordered": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_gather_points_grad_batch_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sv_gather_points_grad_batch_ordered": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_three_interpolate_grad_batch_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sv_three_interpolate_grad_batch_ordered": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_chamfer_forward":(c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "sv_chamfer_backward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "sv_chamfer_backward_ordered_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "sv_chamfer_backward_ordered": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

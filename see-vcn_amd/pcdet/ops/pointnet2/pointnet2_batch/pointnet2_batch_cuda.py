@@ -1,6 +1,10 @@
 """`pointnet2_batch_cuda` with the reference's wrapper names and argument order
-(detector3d/pcdet/ops/pointnet2/pointnet2_batch/src/pointnet2_api.cpp:12-27) over libseevcn_hip.so."""
-from ..... import _lib
+(detector3d/pcdet/ops/pointnet2/pointnet2_batch/src/pointnet2_api.cpp:12-27) over libseevcn_hip.so.
+
+The three gradient wrappers (group_points_grad_wrapper, gather_points_grad_wrapper, three_interpolate_grad_wrapper) add with float atomics by
+default; with seevcn_amd.set_ordered_gradients(True) or torch.use_deterministic_algorithms(True) they call the *_batch_ordered entries, which
+sum every element in ascending key order (include/seevcn_hip.h).  The switch is read when the wrapper is CALLED, i.e. when the backward runs."""
+from ..... import _lib, ordered
 
 
 def _call(name, *args):
@@ -19,8 +23,23 @@ def group_points_wrapper(b, c, n, npoints, nsample, points, idx, out):
     return _call("sv_group_points_batch", int(b), int(c), int(n), int(npoints), int(nsample), _lib.ptr(points), _lib.ptr(idx), _lib.ptr(out))
 
 
+def _call_ordered(name, counter, sizes, args, device):
+    """The order-fixed twin of entry `name`: scratch sized by its *_scratch_bytes(sizes), passed in front of the output pointer."""
+    lib = _lib.load()
+    nbytes = getattr(lib, name + "_scratch_bytes")(*sizes)
+    scratch = _lib.workspace.scratch(counter + "_grad_ordered", nbytes, device)
+    _lib.check(getattr(lib, name)(*args[:-1], _lib.ptr(scratch), args[-1], _lib.stream()), name)
+    ordered.count_call(counter)
+    return 1
+
+
 def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out, idx, grad_points):
+    """grad_points (B,c,n) from grad_out (B,c,npoints,nsample); order-fixed (ascending slot npoints * nsample) when the switch is on"""
     _lib.require_cuda(grad_out, idx, grad_points)
+    if ordered.ordered_gradients():
+        return _call_ordered("sv_group_points_grad_batch_ordered", "group_points_batch", (int(b), int(n), int(npoints), int(nsample)),
+                             (int(b), int(c), int(n), int(npoints), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points)),
+                             grad_out.device)
     return _call("sv_group_points_grad_batch", int(b), int(c), int(n), int(npoints), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx),
                  _lib.ptr(grad_points))
 
@@ -31,7 +50,11 @@ def gather_points_wrapper(b, c, n, npoints, points, idx, out):
 
 
 def gather_points_grad_wrapper(b, c, n, npoints, grad_out, idx, grad_points):
+    """grad_points (B,c,n) from grad_out (B,c,npoints); order-fixed (ascending slot) when the switch is on"""
     _lib.require_cuda(grad_out, idx, grad_points)
+    if ordered.ordered_gradients():
+        return _call_ordered("sv_gather_points_grad_batch_ordered", "gather_points_batch", (int(b), int(n), int(npoints)),
+                             (int(b), int(c), int(n), int(npoints), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points)), grad_out.device)
     return _call("sv_gather_points_grad_batch", int(b), int(c), int(n), int(npoints), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points))
 
 
@@ -51,6 +74,11 @@ def three_interpolate_wrapper(b, c, m, n, points, idx, weight, out):
 
 
 def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_points):
+    """grad_points (B,c,m) from grad_out (B,c,n); order-fixed (ascending key 3 p + t) when the switch is on"""
     _lib.require_cuda(grad_out, idx, weight, grad_points)
+    if ordered.ordered_gradients():
+        return _call_ordered("sv_three_interpolate_grad_batch_ordered", "three_interpolate_batch", (int(b), int(n), int(m)),
+                             (int(b), int(c), int(n), int(m), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_points)),
+                             grad_out.device)
     return _call("sv_three_interpolate_grad_batch", int(b), int(c), int(n), int(m), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight),
                  _lib.ptr(grad_points))

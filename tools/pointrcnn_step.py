@@ -2,9 +2,10 @@
 with the device time split per module: forward hooks record events in front of and behind every entry of the detector's module_list and every
 set-abstraction / feature-propagation module under it; the backward pass is one span.  Median over the timed steps behind a warm-up.  The record
 is there to show where the time goes (the SA MLPs run as torch Conv2d + BatchNorm2d on MIOpen), not to meet a target.  Needs a GPU (--rehearse:
-build the inputs and the model on the CPU, print the module list, stop).
+build the inputs and the model on the CPU, print the module list, stop).  --ordered: the same steps with seevcn_amd.set_ordered_gradients(True),
+i.e. the grouping and interpolation gradients of every SA / FP module on the order-fixed entries; the calls they took are printed.
 
-    python tools/pointrcnn_step.py [--out profiles/pointrcnn_step.txt] [--steps 5] [--warmup 2]
+    python tools/pointrcnn_step.py [--out profiles/pointrcnn_step.txt] [--steps 5] [--warmup 2] [--ordered]
 """
 import argparse
 import os
@@ -81,13 +82,16 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rehearse", action="store_true")
+    ap.add_argument("--ordered", action="store_true", help="take the order-fixed gradient route (set_ordered_gradients(True))")
     a = ap.parse_args()
+    import seevcn_amd
+    seevcn_amd.set_ordered_gradients(a.ordered)
     from seevcn_amd.pcdet.models import detectors
     pts, gt = make_inputs()
     net = detectors.build_detector(C.pointrcnn_model_cfg(), num_class=3, dataset=C.SyntheticDatasetInfo(num_point_features=4))
     net.load_state_dict(seeded_state_dict(net, seed=6))
     lines = [f"PointRCNN (pointrcnn.yaml), {SCENES} scenes x {POINTS} points, {sum(p.numel() for p in net.parameters())} parameters; "
-             f"modules {[type(m).__name__ for m in net.module_list]}"]
+             f"modules {[type(m).__name__ for m in net.module_list]}; gradients: {'order-fixed (--ordered)' if a.ordered else 'default (float atomics)'}"]
     if a.rehearse or not torch.cuda.is_available():
         print("\n".join(lines))
         if not a.rehearse:
@@ -128,6 +132,8 @@ def main():
                 results[mode].append(got)
         if mode == "train":
             lines.append("train step losses: " + ", ".join(f"{k} {float(v):.4f}" for k, v in tb.items()))
+            calls = {k: v for k, v in seevcn_amd.ordered_gradient_calls().items() if v}
+            lines.append(f"order-fixed gradient calls over the {a.warmup + a.steps} train steps: {calls if calls else 'none'}")
     for mode, runs in results.items():
         lines.append(f"--- {mode}: median of {len(runs)} steps behind {a.warmup} warm-up steps (ms: median, min .. max)")
         names = []
