@@ -1194,6 +1194,43 @@ int sv_kitti_match_stats(const float* overlaps, const int64_t* dt_off, const int
                          const int64_t* dc_off, const double* gt_alpha, const double* dt_alpha, int32_t* counts, double* sim_part, double* table,
                          void* stream);
 
+/* CaDDN's frustum sampling grid, FrustumGridGenerator.forward (detector3d/pcdet/models/backbones_3d/vfe/image_vfe_modules/f2v/
+ * frustum_grid_generator.py:79-145 with transform_utils.py:14-91): out (B, X, Y, Z, 3) = normalised (image column, image row, depth bin) of every
+ * voxel centre.  Per voxel in fp32: (x + .5, y + .5, z + .5, 1); T = lidar_to_cam @ grid_to_lidar formed once per scene; from-homogeneous with
+ * scale = |z| > 1e-8 ? 1 / (z + 1e-8) : 1; cam_to_img; depth = z' - P[2][3]; bin_depths (mode 0 UD, 1 LID, 2 SID); coords / ((W_img, H_img,
+ * num_bins) - 1) * 2 - 1; non-finite components become -2.  lidar_to_cam (B, 4, 4), cam_to_img (B, 3, 4), image_shape (B, 2) int32 [H, W] on the
+ * device: its maximum over the batch is taken there, nothing is read on the host.  pc_range_host: 6 floats on the host. */
+int sv_frustum_grid(const float* lidar_to_cam, const float* cam_to_img, const int32_t* image_shape, int batch, int X, int Y, int Z,
+                    const float* pc_range_host, int mode, double depth_min, double depth_max, int num_bins, float* out, void* stream);
+/* FrustumToVoxel.forward fused with DepthFFN.create_frustum_features (f2v/frustum_to_voxel.py:29-54, f2v/sampler.py:26-37,
+ * ffn/depth_ffn.py: frustum_features = depth_probs[:, :-1] * image_features, then the 5-D grid_sample(bilinear, zeros, align_corners=True)).
+ * image_features (B, H, W, C) and depth_probs (B, H, W, D + 1) are the storages of channels_last (B, C, H, W) / (B, D + 1, H, W) tensors; the last
+ * depth bin is never read; D is the discretisation's num_bins.  out has the storage order (B, Y, X, C, Z) -- the reference's (B, C, Z, Y, X) tensor
+ * is a permuted view of it -- and every element is written.  Per voxel, with the coordinates of sv_frustum_grid unnormalised as
+ * ((g + 1) / 2) * (size - 1), pixel taps t = 0..3 = (y0,x0), (y0,x1), (y1,x0), (y1,x1) with w_t = wy * wx, and depth taps d0, d0 + 1:
+ *     a_t = w_t * (wd0 * p[d0, pix_t] + wd1 * p[d1, pix_t]),    out[c] = ((((0 + a_0 f[pix_0, c]) + a_1 f[pix_1, c]) + a_2 ...) + a_3 ...)
+ * where a tap outside the map or the depth range is left out.  Nothing of size C*D*H*W or X*Y*Z*3 is allocated.  16-byte reads along C when
+ * C % 4 == 0 and image_features is 16-byte aligned, else one float a lane.  Needs B*H*W < 2^31, 4*B*X*Y*Z < 2^31, Z <= 512.
+ *
+ * Gradient (none w.r.t. the calibration): no float atomics, a fixed order, every element of grad_features (B, H, W, C) and grad_probs
+ * (B, H, W, D + 1) written exactly once, neither cleared beforehand.  grad_out is in out's storage order.  Key 4 * v + t, with
+ * v = ((b * Y + y) * X + x) * Z + z, names the pixel of tap t of voxel v; keys of taps outside the map, and of voxels with both depth taps
+ * outside, do not exist.  One wave per pixel walks the pixel's keys in ascending order (sv_inv_lists_build):
+ *     grad_features[pix, c] = +0.0f + sum of a_t * g[v, c]                                           in ascending key
+ *     grad_probs[pix, d]    = +0.0f + sum of (w_t * wd) * dot(v)   over the keys whose d0 or d1 is d,   in ascending key (d0 before d1 within a key)
+ *     dot(v) = sum over c of g[v, c] * f[pix, c]: lane l adds its channels l, l + 64 in ascending order, then the wave's xor butterfly 32 -> 1;
+ *     for C > 128 the walk repeats per block of 128 channels and each block's dot is added on its own, blocks ascending.
+ * grad_probs[pix, D] = +0.0f.  Every product and sum is rounded to fp32.  scratch: sv_frustum_to_voxel_grad_scratch_bytes bytes (0: the sizes
+ * exceed the guards above), uninitialised: the per-scene matrices, then the inverse lists.  Needs D <= 4095. */
+int sv_frustum_to_voxel(const float* image_features, const float* depth_probs, const float* lidar_to_cam, const float* cam_to_img,
+                        const int32_t* image_shape, int batch, int C, int D, int H, int W, int X, int Y, int Z, const float* pc_range_host,
+                        int mode, double depth_min, double depth_max, float* out, void* stream);
+size_t sv_frustum_to_voxel_grad_scratch_bytes(int batch, int H, int W, int X, int Y, int Z);
+int sv_frustum_to_voxel_grad(const float* image_features, const float* depth_probs, const float* lidar_to_cam, const float* cam_to_img,
+                             const int32_t* image_shape, const float* grad_out, int batch, int C, int D, int H, int W, int X, int Y, int Z,
+                             const float* pc_range_host, int mode, double depth_min, double depth_max, void* scratch, float* grad_features,
+                             float* grad_probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,10 @@ SIGNATURES = {
     "sv_kitti_thresholds": (c_i, [c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_p]),
     "sv_kitti_match_stats": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
                                    c_p, c_p, c_p, c_p]),
+    "sv_frustum_grid": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_d, c_d, c_i, c_p, c_p]),
+    "sv_frustum_to_voxel": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_d, c_d, c_p, c_p]),
+    "sv_frustum_to_voxel_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "sv_frustum_to_voxel_grad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

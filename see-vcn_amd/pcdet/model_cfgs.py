@@ -394,3 +394,27 @@ def pp_multihead_model_cfg():
                 BACKBONE_2D=dict(NAME='BaseBEVBackbone', LAYER_NUMS=[3, 5, 5], LAYER_STRIDES=[2, 2, 2], NUM_FILTERS=[64, 128, 256],
                                  UPSAMPLE_STRIDES=[0.5, 1, 2], NUM_UPSAMPLE_FILTERS=[128, 128, 128]),
                 DENSE_HEAD=_nusc_multihead_dense_head(4), POST_PROCESSING=_mh_post_processing(0.2, 1000, 83))
+
+
+# detector3d/tools/cfgs/kitti_models/CaDDN.yaml:5-156 (values as data)
+CADDN_RANGE = [2, -30.08, -3.0, 46.8, 30.08, 1.0]
+CADDN_VOXEL = [0.16, 0.16, 0.16]
+CADDN_DEPTH_DOWNSAMPLE_FACTOR = 4
+CADDN_PRETRAINED_PATH = '../checkpoints/deeplabv3_resnet101_coco-586e9e4e.pth'
+
+
+def caddn_model_cfg(backbone_name='ResNet101', pretrained_path=CADDN_PRETRAINED_PATH, feat_channels=64, num_bins=80, depth_min=2.0, depth_max=46.8,
+                    disc_mode='LID', layer_nums=(10, 10, 10), sampler_mode='bilinear'):
+    """MODEL section of kitti_models/CaDDN.yaml.  The keywords scale the model down for tests (a ResNet50 without a checkpoint, fewer channels,
+    bins and BEV layers); the defaults are the YAML's.  The dataset supplies grid_size, point_cloud_range and depth_downsample_factor."""
+    vfe = dict(
+        NAME='ImageVFE',
+        FFN=dict(NAME='DepthFFN',
+                 DDN=dict(NAME='DDNDeepLabV3', BACKBONE_NAME=backbone_name, ARGS=dict(feat_extract_layer='layer1', pretrained_path=pretrained_path)),
+                 CHANNEL_REDUCE=dict(in_channels=256, out_channels=feat_channels, kernel_size=1, stride=1, bias=False),
+                 DISCRETIZE=dict(mode=disc_mode, num_bins=num_bins, depth_min=depth_min, depth_max=depth_max),
+                 LOSS=dict(NAME='DDNLoss', ARGS=dict(weight=3.0, alpha=0.25, gamma=2.0, fg_weight=13, bg_weight=1))),
+        F2V=dict(NAME='FrustumToVoxel', SAMPLER=dict(mode=sampler_mode, padding_mode='zeros')))
+    return dict(NAME='CaDDN', VFE=vfe,
+                MAP_TO_BEV=dict(NAME='Conv2DCollapse', NUM_BEV_FEATURES=feat_channels, ARGS=dict(kernel_size=1, stride=1, bias=False)),
+                BACKBONE_2D=dict(PP_BACKBONE_2D, LAYER_NUMS=list(layer_nums)), DENSE_HEAD=PP_DENSE_HEAD, POST_PROCESSING=SECOND_POST_PROCESSING)

@@ -1,5 +1,6 @@
 from .dynamic_mean_vfe import DynamicMeanVFE
 from .dynamic_pillar_vfe import DynamicPillarVFE
+from .image_vfe import ImageVFE
 from .mean_vfe import MeanVFE
 from .pillar_vfe import PillarVFE
 from .vfe_template import VFETemplate
@@ -11,4 +12,5 @@ __all__ = {
     'PillarVFE': PillarVFE,
     'DynMeanVFE': DynamicMeanVFE,
     'DynPillarVFE': DynamicPillarVFE,
+    'ImageVFE': ImageVFE,
 }

@@ -1,4 +1,5 @@
 from .PartA2_net import PartA2Net
+from .caddn import CaDDN
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .point_rcnn import PointRCNN
@@ -21,6 +22,7 @@ __all__ = {
     'PartA2Net': PartA2Net,
     'PointRCNN': PointRCNN,
     'PVRCNNPlusPlus': PVRCNNPlusPlus,
+    'CaDDN': CaDDN,
 }
 
 

@@ -197,3 +197,23 @@ class RegLossCenterNet(nn.Module):
         loss = torch.abs(pred * m - target * m).transpose(2, 0)
         loss = torch.sum(torch.sum(loss, dim=2), dim=1)
         return loss / torch.clamp_min(num, min=1.0)
+
+
+def compute_fg_mask(gt_boxes2d, shape, downsample_factor=1, device=torch.device("cpu")):
+    """Foreground mask (B, H, W) of the 2-D boxes gt_boxes2d (B, N, 4) [u1, v1, u2, v2] on an image downsampled by downsample_factor (reference
+    loss_utils.py:235-261): fg_mask[b, v1:v2, u1:u2] = True with floor'd upper-left and ceil'd lower-right corners.  The reference divides the
+    caller's boxes in place and loops over them with a host read per box; here the boxes are copied and all of them are tested against the pixel
+    grid at once.  Slice bounds behave as Python's: a negative bound counts from the end, then both are clamped to the axis."""
+    B, H, W = shape
+    boxes = gt_boxes2d.to(device) / downsample_factor
+    lo = torch.floor(boxes[:, :, :2]).long()
+    hi = torch.ceil(boxes[:, :, 2:]).long()
+
+    def bound(a, size):
+        return torch.where(a < 0, a + size, a).clamp(0, size)[:, :, None]
+
+    cols = torch.arange(W, device=device).view(1, 1, W)
+    rows = torch.arange(H, device=device).view(1, 1, H)
+    in_u = (cols >= bound(lo[:, :, 0], W)) & (cols < bound(hi[:, :, 0], W))      # (B, N, W)
+    in_v = (rows >= bound(lo[:, :, 1], H)) & (rows < bound(hi[:, :, 1], H))      # (B, N, H)
+    return (in_v[:, :, :, None] & in_u[:, :, None, :]).any(dim=1)
