@@ -757,9 +757,11 @@ int sv_voxelize_hard(const float* points, int point_stride, int xyz_offset, int 
                      const float* pc_range_host, const float* voxel_size_host, const int32_t* grid_size_host, int max_points,
                      int max_voxels, void* scratch, float* voxels, int32_t* coords, int32_t* num_points_per_voxel,
                      int32_t* num_voxels, void* stream);
-/* PillarVFE.forward feature decoration (backbones_3d/vfe/pillar_vfe.py:94-118): (V,mp,C) -> (V,mp,C+6[+1]) */
+/* PillarVFE.forward feature decoration (backbones_3d/vfe/pillar_vfe.py:94-118): (V,mp,C) -> (V,mp,C+6[+1]).  voxel_size_host (3) and
+ * pc_range_host (>= 3) are the configured values as doubles: the pillar-centre offsets voxel/2 + range start are formed in double, as the
+ * reference's python does, and rounded to fp32 once. */
 int sv_pillar_decorate(const float* voxels, const int32_t* num_points, const int32_t* coords, int64_t num_voxels, int max_points,
-                       int num_features, const float* voxel_size_host, const float* pc_range_host, int use_absolute_xyz,
+                       int num_features, const double* voxel_size_host, const double* pc_range_host, int use_absolute_xyz,
                        int with_distance, float* out, void* stream);
 
 /* interpolate_from_bev_features (detector3d/pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:11-42,176-204):

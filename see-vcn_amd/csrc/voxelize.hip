@@ -487,15 +487,16 @@ __global__ __launch_bounds__(256) void k_pillar_decorate(const float* __restrict
 }
 
 extern "C" int sv_pillar_decorate(const float* voxels, const int32_t* num_points, const int32_t* coords, int64_t num_voxels, int max_points,
-                                  int num_features, const float* voxel_size_host, const float* pc_range_host, int use_absolute_xyz,
+                                  int num_features, const double* voxel_size_host, const double* pc_range_host, int use_absolute_xyz,
                                   int with_distance, float* out, void* stream) {
   SV_CHECK_ARG(num_voxels >= 0 && max_points >= 1 && num_features >= 3, "pillar_decorate: bad arguments");
   if (num_voxels == 0) return SV_OK;
   SV_CHECK_ARG(voxels && num_points && coords && out, "pillar_decorate: null pointer");
-  const float vx = voxel_size_host[0], vy = voxel_size_host[1], vz = voxel_size_host[2];
-  // offsets are computed in double by the reference's python (voxel/2 + range) and used as python floats
-  const float ox = (float)((double)vx / 2 + pc_range_host[0]), oy = (float)((double)vy / 2 + pc_range_host[1]),
-              oz = (float)((double)vz / 2 + pc_range_host[2]);
+  // the reference's python holds the configured voxel size and range as doubles: the offsets are voxel/2 + range in double (pillar_vfe.py:79-81)
+  // and meet the fp32 tensors rounded once.  From fp32-rounded inputs the sum can round the other way (0.2/2 - 51.2: one ulp off).
+  const float vx = (float)voxel_size_host[0], vy = (float)voxel_size_host[1], vz = (float)voxel_size_host[2];
+  const float ox = (float)(voxel_size_host[0] / 2 + pc_range_host[0]), oy = (float)(voxel_size_host[1] / 2 + pc_range_host[1]),
+              oz = (float)(voxel_size_host[2] / 2 + pc_range_host[2]);
   hipLaunchKernelGGL(k_pillar_decorate, dim3(sv_grid_1d(num_voxels * max_points, 256)), dim3(256), 0, sv_stream(stream), voxels, num_points,
                      coords, num_voxels, max_points, num_features, vx, vy, vz, ox, oy, oz, use_absolute_xyz, with_distance, out);
   SV_LAUNCH_CHECK();

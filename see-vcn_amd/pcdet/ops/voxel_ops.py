@@ -101,8 +101,9 @@ def pillar_decorate(voxels, voxel_num_points, coords, voxel_size, pc_range, use_
     V, mp, C = voxels.shape
     co = (C if use_absolute_xyz else C - 3) + 6 + (1 if with_distance else 0)
     out = torch.empty((V, mp, co), dtype=torch.float32, device=voxels.device)
-    vs = _lib.host_array(ctypes.c_float, [float(np.float32(x)) for x in voxel_size])
-    rg = _lib.host_array(ctypes.c_float, [float(np.float32(x)) for x in pc_range])
+    # as doubles: the pillar-centre offset voxel/2 + range start is formed in double and rounded to fp32 once (pillar_vfe.py:79-81)
+    vs = _lib.host_array(ctypes.c_double, [float(x) for x in voxel_size])
+    rg = _lib.host_array(ctypes.c_double, [float(x) for x in pc_range])
     rc = lib.sv_pillar_decorate(_lib.ptr(voxels) if V else None, _lib.ptr(nump) if V else None, _lib.ptr(coords) if V else None, V, mp, C, vs, rg,
                                 int(use_absolute_xyz), int(with_distance), _lib.ptr(out) if V else None, _lib.stream())
     _lib.check(rc, "sv_pillar_decorate")
