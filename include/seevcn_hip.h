@@ -1233,6 +1233,67 @@ int sv_frustum_to_voxel_grad(const float* image_features, const float* depth_pro
                              const float* pc_range_host, int mode, double depth_min, double depth_max, void* scratch, float* grad_features,
                              float* grad_probs, void* stream);
 
+/* Training augmentation on the device (csrc/augment.hip).  One layout for every entry: points are rows of C >= 3 floats in one buffer, scene b owns
+ * rows pt_start[b] .. pt_start[b] + pt_cnt[b]; boxes are rows of W >= 7 floats [x, y, z, dx, dy, dz, heading, ...] at box_start[b] .. + box_cnt[b], at
+ * most 256 per scene.  box_cls, one int32 per box row: >= 0 index into class_names, -1 another class (gt_boxes_mask == 0), -2 filtered out.  keep, one
+ * int32 per point row, 0 = dropped.  Starts and counts are device int32; max_scene_points is a host upper bound of pt_cnt that sizes the grid.
+ * No float atomics: equal bits run to run.
+ *
+ * counts[i] = points of its scene (keep != 0; keep may be NULL) inside box row i by the CPU matrix test, margin 1e-2 in x / y and none in z:
+ * points_in_boxes_cpu(...).sum(axis=1) of detector3d/pcdet/datasets/dataset.py:131-133 (the MIN_POINTS_OF_GT filter). */
+int sv_points_in_boxes_count(const float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, const int32_t* keep, int batch,
+                             int max_scene_points, const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, int total_boxes,
+                             int32_t* counts, void* stream);
+/* scale_pre_object, the boxes (detector3d/pcdet/datasets/augmentor/augmentor_utils.py:26-50, 61, 66, 69): one workgroup per scene visits its boxes in
+ * order; a box with box_cls < 0 is skipped (-1 still blocks the others); noises (box rows, num_try <= 64) fp64; try_idx = the first try whose BEV IoU
+ * (s_overlap / fmaxf(sa + sb - s_overlap, 1e-8)) with every other box, at its current size, is exactly 0; one box alone takes try 0.  plan[i] = the
+ * chosen scale, 0 = none.  boxes are updated in place (dx, dy, dz scaled, z lifted by (new_dz - dz) / 2) and later boxes see that. */
+int sv_object_scale_plan(float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls, int batch,
+                         const double* noises, int num_try, double* plan, void* stream);
+/* scale_pre_object, the points (augmentor_utils.py:52-78): one thread per point walks the scene's scaled boxes in order.  boxes_before: the boxes as
+ * sv_object_scale_plan found them.  A point inside box k (margin 1e-2) goes into the box frame, is scaled, goes back and is lifted; columns past z
+ * stay.  Only a scale > 1 drops points: those with in_before XOR in_after against the new box get keep = 0 and meet no later box. */
+int sv_object_scale_points(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int32_t* keep, int batch, int max_scene_points,
+                           const float* boxes_before, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls,
+                           const double* plan, void* stream);
+/* DataBaseSampler.__call__ (detector3d/pcdet/datasets/augmentor/database_sampler.py:438-468), one workgroup per scene.  The database: db_boxes
+ * (K, W) fp32 and db_cls (K) int32.  The scene's candidates: rows cand_start[b] .. cand_start[b + 1] of cand_idx (database rows) and cand_group (the
+ * SAMPLE_GROUPS entry that drew them, ascending).  Groups in order; a candidate is valid when its BEV IoU with every existing box (box_cls >= -1,
+ * and the earlier groups' accepted boxes) and with every other candidate of its group is exactly 0 (max(iou1) + max(iou2) == 0: not greedy).
+ * Accepted boxes are appended behind the scene's box_cnt[b] rows in candidate order (spare rows the caller left: the scene owns box_cap[b] <= 256 rows
+ * in all, and a valid candidate beyond them is not accepted), with box_cls = db_cls; box_cnt[b] grows; accept[i] = 0 / 1 per candidate. */
+int sv_gt_sample_select(float* boxes, int W, const int32_t* box_start, int32_t* box_cnt, const int32_t* box_cap, int32_t* box_cls, int batch,
+                        const float* db_boxes, const int32_t* db_cls, const int32_t* cand_idx, const int32_t* cand_group, const int32_t* cand_start, int total_candidates,
+                        int32_t* accept, void* stream);
+/* add_sampled_boxes_to_scene (database_sampler.py:381-415).  db_points (T, C) fp32 with db_offsets (K + 1) int64.  Candidate i owns rows cand_dest[i]
+ * .. of the point buffer, as many as its object has points (cand_ptoff (candidates + 1): their prefix sum, total_rows in all), at the head of its
+ * scene (head_rows[b] rows, keep == 0 on entry) in candidate order, so that the final stable compaction gives [object points in acceptance order,
+ * surviving scene points].  Accepted: rows = db_points + box3d_lidar[:3] in fp32, keep = 1.  The scene's own points inside any accepted box enlarged
+ * by (extra_x, extra_y, extra_z) (REMOVE_EXTRA_WIDTH; the CPU matrix test, margin 1e-2) get keep = 0.  Nothing accepted: the scene is unchanged. */
+int sv_gt_sample_paste(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, const int32_t* head_rows, int32_t* keep, int batch,
+                       int max_scene_points, const float* db_points, const int64_t* db_offsets, const float* db_boxes, int W, const int32_t* cand_idx,
+                       const int32_t* cand_start, const int32_t* cand_ptoff, const int32_t* cand_dest, const int32_t* accept, int total_candidates,
+                       int total_rows, float extra_x, float extra_y, float extra_z, void* stream);
+/* random_flip_along_x / _y, global_rotation, global_scaling, random_translation_along_x / _y / _z (augmentor_utils.py:82-160, 203-254) in the order
+ * given: ops holds num_ops <= 16 codes of 4 bits, first op lowest (1 flip x, 2 flip y, 3 rotation, 4 scaling, 5 / 6 / 7 translation x / y / z); params
+ * (batch, num_ops) fp64, one value per scene and op (flips: 0 / 1).  Boxes: centres, sizes, heading and for W > 7 the velocity columns 7 / 8; rows
+ * with box_cls == -2 stay; limit_heading applies limit_period(heading, 0.5, 2 pi) afterwards (data_augmentor.py:258-260). */
+int sv_world_transform_points(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int batch, int max_scene_points, int64_t ops,
+                              int num_ops, const double* params, void* stream);
+int sv_world_transform_boxes(float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls, int batch, int64_t ops,
+                             int num_ops, const double* params, int limit_heading, void* stream);
+/* The tail of prepare_data / DataProcessor in one stable compaction.  Points survive with keep != 0 and, pt_range_host (x0, y0, x1, y1 fp64 on the
+ * host, may be NULL) given, inside it with both bounds inclusive (common_utils.py:60-63): out_points rows [b, x, y, z, ...] of C + 1 floats, ordered by
+ * scene and inside a scene as they came; out_start (batch + 1) their starts; out_counts (2 * batch) = points per scene, then boxes per scene.  Boxes
+ * survive with box_cls >= 0 (data_augmentor.py:265-267, dataset.py:152-156) and, min_num_corners > 0, that many corners inside box_range_host (6 fp64:
+ * box_utils.py:93-109): gt_out (batch, gt_stride, W + 1), in order, box_cls + 1 in the last column, zero padded.  keep is overwritten with the final
+ * flags; box_keep (one int32 per box row, may be NULL) receives the boxes' flags.  scratch: sv_augment_compact_scratch_bytes bytes, uninitialised. */
+size_t sv_augment_compact_scratch_bytes(int batch, int max_scene_points);
+int sv_augment_compact(const float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int32_t* keep, int batch, int max_scene_points,
+                       const double* pt_range_host, const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt,
+                       const int32_t* box_cls, const double* box_range_host, int min_num_corners, void* scratch, float* out_points,
+                       int32_t* out_start, int32_t* out_counts, float* gt_out, int gt_stride, int32_t* box_keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

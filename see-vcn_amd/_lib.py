@@ -255,6 +255,15 @@ SIGNATURES = {
     "sv_frustum_to_voxel": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_d, c_d, c_p, c_p]),
     "sv_frustum_to_voxel_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "sv_frustum_to_voxel_grad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p]),
+    "sv_points_in_boxes_count": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p]),
+    "sv_object_scale_plan": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "sv_object_scale_points": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_gt_sample_select": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "sv_gt_sample_paste": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_p]),
+    "sv_world_transform_points": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p]),
+    "sv_world_transform_boxes": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_i, c_p]),
+    "sv_augment_compact_scratch_bytes": (c_sz, [c_i, c_i]),
+    "sv_augment_compact": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
 }
 
 _lib = None

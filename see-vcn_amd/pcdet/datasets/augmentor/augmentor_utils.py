@@ -1,0 +1,252 @@
+"""Training augmentation on the device (reference: datasets/augmentor/augmentor_utils.py, numpy on dataloader workers) on csrc/augment.hip.
+
+The functions keep the reference's names and take a `DeviceBatch` -- every scene of the batch in one stacked point buffer and one stacked box
+buffer -- plus the random draws, which the caller makes on the host in the reference's order (data_augmentor.draw_params).  Points are never
+removed between stages: a dropped point gets keep = 0 and `compact` removes it at the very end, which preserves order and so gives the same
+result as the reference's compaction after every stage.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .... import _lib as L
+
+# library calls and blocking device -> host reads since the last reset_counters(); neither depends on the batch size or the number of boxes
+COUNTERS = {"library_calls": 0, "host_reads": 0}
+
+MAX_BOXES_PER_SCENE = 256
+MAX_NUM_TRY = 64
+OPS = {"flip_x": 1, "flip_y": 2, "rotation": 3, "scaling": 4, "translation_x": 5, "translation_y": 6, "translation_z": 7}
+
+_ws = L.Workspace()
+
+
+def reset_counters():
+    COUNTERS["library_calls"] = 0
+    COUNTERS["host_reads"] = 0
+
+
+def call(name, *args):
+    """One call into the library through the binding layer, counted."""
+    COUNTERS["library_calls"] += 1
+    L.check(getattr(L.load(), name)(*args), name)
+
+
+def read(t):
+    """One blocking device -> host read, counted."""
+    COUNTERS["host_reads"] += 1
+    return t.cpu().numpy()
+
+
+class DeviceBatch:
+    """The scenes of one batch, stacked.  points (P, C) fp32 and keep (P,) int32; boxes (N, W) fp32 and box_cls (N,) int32 (>= 0 index into
+    class_names, -1 another class, -2 filtered out); pt_start / pt_cnt / box_start / box_cnt (B,) int32 on the device.  max_scene_points and
+    max_scene_boxes are host upper bounds.  With point_slots / box_slots (GT sampling) scene b's point rows begin with point_slots[b] spare rows
+    (keep = 0 until an object is pasted there) and its box rows end with box_slots[b] spare rows (box_cls = -2, beyond box_cnt)."""
+
+    def __init__(self, points, boxes, box_cls, pt_sizes, box_sizes, box_slots=None, point_slots=None):
+        L.require_cuda(points, boxes)
+        assert points.dtype == boxes.dtype == torch.float32 and points.dim() == boxes.dim() == 2
+        assert points.shape[1] >= 3 and boxes.shape[1] >= 7
+        pt_sizes, box_rows = np.asarray(pt_sizes, np.int64), np.asarray(box_sizes, np.int64)
+        B = len(pt_sizes)
+        box_slots = np.zeros(B, np.int64) if box_slots is None else np.asarray(box_slots, np.int64)
+        self.point_slots = np.zeros(B, np.int64) if point_slots is None else np.asarray(point_slots, np.int64)
+        box_cls = np.asarray(box_cls, np.int32).reshape(-1)
+        assert len(box_rows) == B >= 1 and pt_sizes.sum() == points.shape[0] and box_rows.sum() == boxes.shape[0] == len(box_cls)
+        if box_rows.max() > MAX_BOXES_PER_SCENE:
+            raise ValueError(f"at most {MAX_BOXES_PER_SCENE} boxes per scene (existing + candidates), got {int(box_rows.max())}")
+        dev = points.device
+        self.batch_size = B
+        self.num_point_features, self.box_width = points.shape[1], boxes.shape[1]
+        self.max_scene_points, self.max_scene_boxes = int(pt_sizes.max()), int(box_rows.max())
+        self.total_points, self.total_boxes = int(points.shape[0]), int(boxes.shape[0])
+        # at least one row each, so that no kernel is handed a null pointer for an empty batch
+        self.points = points.contiguous() if self.total_points else torch.zeros(1, points.shape[1], device=dev)
+        self.boxes = boxes.contiguous() if self.total_boxes else torch.zeros(1, boxes.shape[1], device=dev)
+        self.keep = torch.ones(max(self.total_points, 1), dtype=torch.int32, device=dev)
+        self.pt_offsets, self.box_offsets = np.cumsum(pt_sizes) - pt_sizes, np.cumsum(box_rows) - box_rows
+        self.box_sizes = box_rows - box_slots                     # the boxes that exist on entry
+        host = np.concatenate([self.pt_offsets, pt_sizes, self.box_offsets, self.box_sizes, box_rows, box_cls, [-2]]).astype(np.int32)
+        meta = torch.from_numpy(host).to(dev)                   # one upload for the whole layout
+        self.pt_start, self.pt_cnt, self.box_start, self.box_cnt = meta[:B], meta[B:2 * B], meta[2 * B:3 * B], meta[3 * B:4 * B]
+        self.box_cap, self.box_cls = meta[4 * B:5 * B], meta[5 * B:]   # rows a scene owns (existing + spare), class codes
+
+    @classmethod
+    def from_scenes(cls, points_list, boxes_list, cls_list, point_slots=None, box_slots=None):
+        """points_list[b] (n_b, C), boxes_list[b] (m_b, W) device tensors; cls_list[b] (m_b,) host integers."""
+        B = len(points_list)
+        pts, boxes, codes = list(points_list), list(boxes_list), [np.asarray(c, np.int32).reshape(-1) for c in cls_list]
+        if point_slots is None and box_slots is None:
+            return cls(torch.cat(pts), torch.cat(boxes), np.concatenate(codes), [len(p) for p in pts], [len(b) for b in boxes])
+        point_slots, box_slots = [int(v) for v in point_slots], [int(v) for v in box_slots]
+        dev, C, W = pts[0].device, pts[0].shape[1], boxes[0].shape[1]
+        spare_p = torch.zeros(max(point_slots), C, device=dev)     # one block of zeros, sliced per scene
+        spare_b = torch.zeros(max(box_slots), W, device=dev)
+        inst = cls(torch.cat([t for b in range(B) for t in (spare_p[:point_slots[b]], pts[b])]),
+                   torch.cat([t for b in range(B) for t in (boxes[b], spare_b[:box_slots[b]])]),
+                   np.concatenate([np.concatenate([codes[b], np.full(box_slots[b], -2, np.int32)]) for b in range(B)]),
+                   [len(p) + s for p, s in zip(pts, point_slots)], [len(b) + s for b, s in zip(boxes, box_slots)], box_slots, point_slots)
+        flags = torch.ones(2, max(max(point_slots), max(len(p) for p in pts), 1), dtype=torch.int32, device=dev)
+        flags[0] = 0
+        inst.keep = torch.cat([t for b in range(B) for t in (flags[0, :point_slots[b]], flags[1, :len(pts[b])])] + [flags[1, :1]])
+        return inst
+
+    def _pt_args(self):
+        return L.ptr(self.points), self.num_point_features, L.ptr(self.pt_start), L.ptr(self.pt_cnt)
+
+    def _box_args(self):
+        return L.ptr(self.boxes), self.box_width, L.ptr(self.box_start), L.ptr(self.box_cnt)
+
+
+def _device_f64(values, device):
+    if isinstance(values, torch.Tensor):
+        assert values.dtype == torch.float64 and values.is_cuda
+        return values.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(values, np.float64)).to(device)
+
+
+def points_in_boxes_count(batch):
+    """(N,) int32: the points of its scene inside each box by the CPU matrix test, margin 1e-2 in x / y and none in z (dataset.py:131-133)."""
+    counts = torch.empty(max(batch.total_boxes, 1), dtype=torch.int32, device=batch.points.device)
+    call("sv_points_in_boxes_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(),
+         batch.total_boxes, L.ptr(counts), L.stream())
+    return counts[:batch.total_boxes]
+
+
+def filter_boxes_by_min_points(batch, min_points, counts=None):
+    """MIN_POINTS_OF_GT (dataset.py:135-137) without a host read: boxes below the limit stop existing (box_cls = -2)."""
+    counts = points_in_boxes_count(batch) if counts is None else counts
+    cls = batch.box_cls[:batch.total_boxes]
+    cls.copy_(torch.where(counts >= int(min_points), cls, torch.full_like(cls, -2)))
+    return counts
+
+
+def scale_pre_object(batch, scale_noises):
+    """augmentor_utils.py:10-80 for every scene of the batch.  scale_noises (N, num_try) fp64: row i holds the tries of box row i (rows of boxes
+    that are skipped are not read).  Returns the plan (N,) fp64 on the device: the chosen scale per box, 0 = none."""
+    dev = batch.points.device
+    noises = _device_f64(scale_noises, dev)
+    if batch.total_boxes == 0:
+        return torch.zeros(0, dtype=torch.float64, device=dev)
+    assert noises.dim() == 2 and noises.shape[0] == batch.total_boxes
+    num_try = int(noises.shape[1])
+    if not 1 <= num_try <= MAX_NUM_TRY:
+        raise ValueError(f"num_try must be in 1..{MAX_NUM_TRY}, got {num_try}")
+    before = batch.boxes.clone()
+    plan = torch.empty(batch.total_boxes, dtype=torch.float64, device=dev)
+    call("sv_object_scale_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, L.ptr(noises), num_try, L.ptr(plan), L.stream())
+    call("sv_object_scale_points", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, L.ptr(before), batch.box_width,
+         L.ptr(batch.box_start), L.ptr(batch.box_cnt), L.ptr(batch.box_cls), L.ptr(plan), L.stream())
+    return plan
+
+
+def world_transform(batch, ops, params, limit_heading=False):
+    """`ops`: names from OPS in the order they apply; params (B, len(ops)) fp64, one value per scene and op.  One launch over the points and one over
+    the boxes, whatever the number of ops; limit_heading adds limit_period(heading, 0.5, 2 pi) (data_augmentor.py:258-260)."""
+    if len(ops) > 16:
+        raise ValueError("at most 16 world transforms in one call")
+    code = 0
+    for i, name in enumerate(ops):
+        code |= OPS[name] << (4 * i)
+    dev = batch.points.device
+    p = _device_f64(np.zeros((batch.batch_size, 1)) if len(ops) == 0 else params, dev)
+    assert len(ops) == 0 or tuple(p.shape) == (batch.batch_size, len(ops))
+    if len(ops):
+        call("sv_world_transform_points", *batch._pt_args(), batch.batch_size, batch.max_scene_points, code, len(ops), L.ptr(p), L.stream())
+    if len(ops) or limit_heading:
+        call("sv_world_transform_boxes", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, code, len(ops), L.ptr(p), int(limit_heading),
+             L.stream())
+
+
+def _per_scene(batch, values):
+    return np.asarray(values, np.float64).reshape(batch.batch_size, 1)
+
+
+def random_flip_along_x(batch, enable):
+    """augmentor_utils.py:82-99; enable: one bool per scene (the draw)."""
+    world_transform(batch, ["flip_x"], _per_scene(batch, enable))
+
+
+def random_flip_along_y(batch, enable):
+    """augmentor_utils.py:102-119."""
+    world_transform(batch, ["flip_y"], _per_scene(batch, enable))
+
+
+def global_rotation(batch, noise_rotation):
+    """augmentor_utils.py:122-142; noise_rotation: one angle per scene."""
+    world_transform(batch, ["rotation"], _per_scene(batch, noise_rotation))
+
+
+def global_scaling(batch, noise_scale):
+    """augmentor_utils.py:145-160; noise_scale: one factor per scene (the caller skips the call when the range is narrower than 1e-3)."""
+    world_transform(batch, ["scaling"], _per_scene(batch, noise_scale))
+
+
+def random_translation_along_x(batch, offset):
+    """augmentor_utils.py:203-219."""
+    world_transform(batch, ["translation_x"], _per_scene(batch, offset))
+
+
+def random_translation_along_y(batch, offset):
+    """augmentor_utils.py:222-238."""
+    world_transform(batch, ["translation_y"], _per_scene(batch, offset))
+
+
+def random_translation_along_z(batch, offset):
+    """augmentor_utils.py:241-254."""
+    world_transform(batch, ["translation_z"], _per_scene(batch, offset))
+
+
+def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
+    """sv_augment_compact without the host read: (out_points, out_meta, gt, box_keep).  batch.keep holds the points' final flags afterwards."""
+    dev, B, C, W = batch.points.device, batch.batch_size, batch.num_point_features, batch.box_width
+    out_points = torch.empty(max(batch.total_points, 1), C + 1, dtype=torch.float32, device=dev)
+    out_meta = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)
+    gt_stride = batch.max_scene_boxes
+    gt = torch.empty(B, max(gt_stride, 1), W + 1, dtype=torch.float32, device=dev)
+    box_keep = torch.zeros(max(batch.total_boxes, 1), dtype=torch.int32, device=dev)
+    scratch = _ws.scratch("augment_compact", max(int(L.load().sv_augment_compact_scratch_bytes(B, batch.max_scene_points)), 4), dev)
+    pr = None if point_range is None else L.host_array(ctypes.c_double, [float(point_range[i]) for i in (0, 1, 3, 4)])
+    br = None if not min_num_corners else L.host_array(ctypes.c_double, [float(v) for v in list(box_range)[:6]])
+    call("sv_augment_compact", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, pr, *batch._box_args(), L.ptr(batch.box_cls), br,
+         int(min_num_corners), L.ptr(scratch), L.ptr(out_points), L.ptr(out_meta[:B + 1]), L.ptr(out_meta[B + 1:]), L.ptr(gt), gt_stride,
+         L.ptr(box_keep), L.stream())
+    return out_points, out_meta, gt, box_keep
+
+
+def compact(batch, point_range=None, box_range=None, min_num_corners=0, shuffle=None):
+    """The tail of prepare_data and DataProcessor: the gt_boxes_mask / class filter with the class column (data_augmentor.py:265-267,
+    dataset.py:152-157), mask_points_by_range (x / y, both bounds inclusive), mask_boxes_outside_range_numpy (min_num_corners > 0) and one stable
+    compaction, with ONE host read for the B point counts and B box counts.  shuffle: None, or a list of one permutation per scene of its
+    surviving points (shuffle_points with explicit draws), or True for device-generated ones.
+
+    Returns points (P, 1 + C) [b, x, y, z, ...], scene_start (B + 1) / scene_cnt (B) int32 on the device, gt_boxes (B, max_gt, W + 1),
+    points_per_scene / boxes_per_scene (host) and empty_scenes (scenes that ended with no box)."""
+    B = batch.batch_size
+    out_points, out_meta, gt, _ = launch_compact(batch, point_range, box_range, min_num_corners)
+    counts = read(out_meta[B + 1:])
+    points_per_scene, boxes_per_scene = counts[:B].astype(np.int64), counts[B:].astype(np.int64)
+    points = out_points[:int(points_per_scene.sum())]
+    if shuffle is not None and shuffle is not False:
+        points = points[_shuffle_index(shuffle, points_per_scene, points.device)]
+    return {"points": points, "scene_start": out_meta[:B + 1], "scene_cnt": out_meta[B + 1:2 * B + 1],
+            "gt_boxes": gt[:, :int(boxes_per_scene.max())].contiguous(), "points_per_scene": points_per_scene,
+            "boxes_per_scene": boxes_per_scene, "batch_size": B, "empty_scenes": [int(b) for b in np.nonzero(boxes_per_scene == 0)[0]]}
+
+
+def _shuffle_index(shuffle, points_per_scene, dev):
+    """shuffle_points (data_processor.py:93-103): a gather index that permutes every scene's rows among themselves."""
+    starts = np.cumsum(points_per_scene) - points_per_scene
+    if shuffle is True:
+        total = int(points_per_scene.sum())
+        scene = torch.repeat_interleave(torch.arange(len(points_per_scene), device=dev), torch.from_numpy(points_per_scene).to(dev), output_size=total)
+        return torch.argsort(scene.double() + torch.rand(total, dtype=torch.float64, device=dev))
+    idx = []
+    for b, perm in enumerate(shuffle):
+        perm = np.asarray(perm, np.int64)
+        if sorted(perm.tolist()) != list(range(int(points_per_scene[b]))):
+            raise ValueError(f"scene {b}: not a permutation of its {int(points_per_scene[b])} surviving points")
+        idx.append(perm + starts[b])
+    return torch.from_numpy(np.concatenate(idx) if idx else np.zeros(0, np.int64)).to(dev)

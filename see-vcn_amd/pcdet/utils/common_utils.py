@@ -164,3 +164,12 @@ def materialize_tb(*dicts):
         for (d, k), v in zip(keys, vals):
             d[k] = v
     return dicts[0] if len(dicts) == 1 else dicts
+
+
+def mask_points_by_range(points, limit_range):
+    """common_utils.py:60-63 on the device: points (N, 3 + C) fp32 -> (N,) bool, x and y only, both bounds inclusive; the fp32 coordinate is
+    compared against the limit as float64, as numpy does with a list of Python floats.  No host read."""
+    from ..datasets.augmentor import augmentor_utils as A
+    batch = A.DeviceBatch(points, points.new_zeros(0, 7), [], [len(points)], [0])
+    A.launch_compact(batch, limit_range, None, 0)
+    return batch.keep[:len(points)].bool()
