@@ -1294,6 +1294,45 @@ int sv_augment_compact(const float* points, int C, const int32_t* pt_start, cons
                        const int32_t* box_cls, const double* box_range_host, int min_num_corners, void* scratch, float* out_points,
                        int32_t* out_start, int32_t* out_counts, float* gt_out, int gt_stride, int32_t* box_keep, void* stream);
 
+/* Mesh ray casting for the VCN's "VC" training data (csrc/raycast.hip); replaces open3d.t.geometry.RaycastingScene (Embree, CPU) in
+ * see/surface_completion/models/vcn/vc_shapenet/dataset_functions.py:265-342 and raycast_surface_from_meshes.py:16-52.  The arithmetic is stated in
+ * tests/raycast_reference.py: Moeller-Trumbore without culling in fp32, one rounding per operation; a triangle is hit when det != 0 && u >= 0 &&
+ * v >= 0 && u + v <= 1 && t >= 0; the result is the smallest t, ties to the lowest (geometry, primitive); a miss is t = +inf and ids -1.  The
+ * hierarchy skips only triangles that test would reject (padded boxes: DESIGN.md section 3 "VC ray casting"), so results equal brute force.
+ *
+ * The hierarchy (scene.add_triangles, :266-306): tris (T, 3, 3) fp32 in scene order (geometry-major), T <= 2^24.  sv_bvh_keys writes
+ * keys[i] = Morton code of triangle i's centroid << 32 | i and status[0] |= 1 when a vertex is not finite (status: 2 int32, cleared here; the caller
+ * refuses such a scene); the caller sorts the keys ascending; sv_bvh_build makes nodes (max(T - 1, 1), 16) and leaves (T, 12) 4-byte words: a radix
+ * tree over the sorted keys, every node in parallel, boxes united bottom-up behind one integer counter per node.  A root-to-leaf path holds at most
+ * 54 internal nodes (30 Morton + 24 index bits).  scratch: sv_bvh_scratch_bytes(T) bytes for both (0: T out of range), uninitialised. */
+size_t sv_bvh_scratch_bytes(int64_t T);
+int sv_bvh_keys(const float* tris, int64_t T, int64_t* keys, int32_t* status, void* scratch, void* stream);
+int sv_bvh_build(const float* tris, const int32_t* geom_ids, const int32_t* prim_ids, int64_t T, const int64_t* sorted_keys, float* nodes,
+                 float* leaves, void* scratch, void* stream);
+/* scene.cast_rays(rays) (dataset_functions.py:320, raycast_surface_from_meshes.py:27): rays (N, 6) fp32 [origin, direction], directions as given
+ * (not normalised).  t_hit (N) fp32, geometry_ids / primitive_ids (N) int32, primitive_uvs (N, 2) fp32: open3d's keys without the normals.  One
+ * wave per 64 consecutive rays; the traversal stack is 64 entries a lane in LDS and the walk visits every node once at most.  status[1] |= 1 were
+ * the stack ever full (it cannot be: 54 < 64).  T == 0: every ray misses. */
+int sv_cast_rays(const float* nodes, const float* leaves, int64_t T, const float* rays, int64_t N, float* t_hit, int32_t* geometry_ids,
+                 int32_t* primitive_ids, float* primitive_uvs, int32_t* status, void* stream);
+/* create_rays_pinhole + cast_rays for C cameras in one launch (cast_rays_at_point, :310-323; generate_views, :16-32) without a ray tensor.  cams
+ * (C, 12) fp64 on the device: M = R^-1 K^-1 row-major (made on the host) and the eye.  Ray (c, y, x), row-major with y outer: direction
+ * M (x + 0.5, y + 0.5, 1) as three fp64 products summed left to right and rounded once to fp32, origin = the eye rounded.  One wave per 8 x 8 pixel
+ * tile.  Outputs as sv_cast_rays, C * H * W rays.  C <= 65535, C * W * H < 2^31. */
+int sv_cast_pinhole(const float* nodes, const float* leaves, int64_t T, const double* cams, int C, int W, int H, float* t_hit, int32_t* geometry_ids,
+                    int32_t* primitive_ids, float* primitive_uvs, int32_t* status, void* stream);
+/* RaycastingScene.create_rays_pinhole (:311-318): the rays of sv_cast_pinhole as a tensor, out (C, H, W, 6) fp32. */
+int sv_rays_pinhole(const double* cams, int C, int W, int H, float* out, void* stream);
+/* rays[hit][:, :3] + rays[hit][:, 3:] * t_hit[hit] (:321-322) and the crop of raycast_object (:331-334) as one stable compaction per segment.
+ * Segment c owns rays c * W * H .. ; give either the ray tensor (C * W * H, 6) or cams (the other NULL).  hit = t_hit is finite; the point is
+ * o + d * t per component in fp32, two roundings.  points (rows of 3 fp32): segment 0's hit points in ray order, then segment 1's, ...; flags one
+ * int32 per point row: 1 inside the segment's box, boxes (C, 7) [x, y, z, l, w, h, yaw] by the test of csrc/box_test.h with no margin (boxes NULL:
+ * all 0); obj_points: the rows with flag 1, compacted the same way.  counts (2, C) int32: hit points per segment, then in-box points per segment.
+ * points / flags / obj_points hold C * W * H rows.  No float atomics, equal bits run to run.  scratch: sv_ray_hit_points_scratch_bytes bytes. */
+size_t sv_ray_hit_points_scratch_bytes(int C, int W, int H);
+int sv_ray_hit_points(const float* rays, const double* cams, int C, int W, int H, const float* t_hit, const float* boxes, void* scratch,
+                      float* points, int32_t* flags, float* obj_points, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,14 @@ SIGNATURES = {
     "sv_world_transform_boxes": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_i, c_p]),
     "sv_augment_compact_scratch_bytes": (c_sz, [c_i, c_i]),
     "sv_augment_compact": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "sv_bvh_scratch_bytes": (c_sz, [c_i64]),
+    "sv_bvh_keys": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "sv_bvh_build": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "sv_cast_rays": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_cast_pinhole": (c_i, [c_p, c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_rays_pinhole": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    "sv_ray_hit_points_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "sv_ray_hit_points": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None
