@@ -1333,6 +1333,34 @@ size_t sv_ray_hit_points_scratch_bytes(int C, int W, int H);
 int sv_ray_hit_points(const float* rays, const double* cams, int C, int W, int H, const float* t_hit, const float* boxes, void* scratch,
                       float* points, int32_t* flags, float* obj_points, int32_t* counts, void* stream);
 
+/* ---- the VC training transforms (see/surface_completion/models/vcn/datasets/data_transforms.py), csrc/lidar_sim.hip.  Objects are stacked: points
+ * (sum N, 3) fp32, start / cnt (batch) int32 on the device.  No float atomics, equal bits run to run. */
+#define SV_VC_MAX_RINGS 1024
+#define SV_VC_PLAN_WORDS 40
+/* The ring index of LidarSimulation (data_transforms.py:161-164, fixed_bins = 0: bins = 'sqrt') and DownsampleRings (:128-133, fixed_bins = 50):
+ * elevation = arctan2(norm(xy), z) of the float64 rows (utils/misc.py:280-287), np.histogram's equal bins over [min, max] and np.digitize against
+ * the left edges of the non-empty bins, i.e. the 1-based rank of the point's own bin among the non-empty bins.  One workgroup per object.  ring
+ * (sum N) int32; num_rings (batch); ring_cnt (batch, SV_VC_MAX_RINGS) points per ring, 0 beyond num_rings; elevation (sum N) fp64 or NULL.  An
+ * object with cnt < min_in_pts is not looked at (:124, :158): num_rings = 0 and ring = 0.  cnt <= 2^20, so that 'sqrt' gives at most 1024 bins. */
+int sv_vc_rings(const float* points, const int32_t* start, const int32_t* cnt, int batch, int fixed_bins, int min_in_pts, int32_t* ring,
+                int32_t* num_rings, int32_t* ring_cnt, double* elevation, void* stream);
+/* sph2cart(sph_pts[mask][first::step]) (:73, :134-138, :171-194) as an order-preserving copy of rows.  plan (batch, SV_VC_PLAN_WORDS) int32 made on
+ * the host: 0 pass-through (the object's rows as they are), 1 use the ring bitmask, 2 use keep (sum N bytes, RandomPointDropout's mask), 3 first,
+ * 4 step, 5 out_start (row of `out`), 6 out_len, 7 unused, 8..39 the bitmask of chosen rings (bit r - 1 = ring r).  ring / keep may be NULL when no
+ * plan uses them.  Rows beyond out_len are not written. */
+int sv_vc_select(const float* points, const int32_t* start, const int32_t* cnt, int batch, const int32_t* ring, const uint8_t* keep,
+                 const int32_t* plan, float* out, void* stream);
+/* ResamplePoints (:254-262): out (batch, n_points, 3), out[b, j] = points[start_b + index[b, j] % cnt_b]; index (batch, n_points) int32 = the first
+ * n_points of the permutation of the tiled cloud, drawn on the host. */
+int sv_vc_resample(const float* points, const int32_t* start, const int32_t* cnt, int batch, const int32_t* index, int n_points, float* out,
+                   void* stream);
+/* mode 0 Jitter (:214-217): p + noise, noise (total, 3) fp64.  mode 1 AddGNSpherical (:240-243): p * ((r + noise) / r), noise (total) fp64, r == 0
+ * gives (0, 0, noise).  In place, float64 arithmetic rounded once to fp32. */
+int sv_vc_pointwise(float* points, int64_t total, const double* noise, int mode, void* stream);
+/* RandomObjectScaling (:302-316): params (batch, 8) fp64 = enable, box centre (3), heading, scale (3).  Into the box frame (float64 difference,
+ * fp32 rotation of utils/transform.py:33-58), float64 product with the scale, fp32 rotation back, float64 sum with the centre.  In place. */
+int sv_vc_object_scale(float* points, const int32_t* start, const int32_t* cnt, int batch, int max_points, const double* params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

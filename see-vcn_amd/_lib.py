@@ -272,6 +272,11 @@ SIGNATURES = {
     "sv_rays_pinhole": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_ray_hit_points_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "sv_ray_hit_points": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vc_rings": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vc_select": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_vc_resample": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "sv_vc_pointwise": (c_i, [c_p, c_i64, c_p, c_i, c_p]),
+    "sv_vc_object_scale": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
 }
 
 _lib = None
