@@ -1294,6 +1294,35 @@ int sv_augment_compact(const float* points, int C, const int32_t* pt_start, cons
                        const int32_t* box_cls, const double* box_range_host, int min_num_corners, void* scratch, float* out_points,
                        int32_t* out_start, int32_t* out_counts, float* gt_out, int gt_stride, int32_t* box_keep, void* stream);
 
+/* The local augmentors (csrc/augment_local.hip) on the same layout.  steps: num_steps <= 16 codes of 4 bits, first step lowest:
+ *   1 / 2 / 3 random_local_translation_along_x / _y / _z (augmentor_utils.py:257-320)   4 local_rotation (:425-470)   5 local_scaling (:391-422)
+ *   6 / 7 / 8 / 9 local_frustum_dropout_top / _bottom / _left / _right (:473-550)
+ * sv_local_transform_plan: one thread per box row walks the steps.  draws (total_boxes, num_steps) fp64, one value per box row and step (offset,
+ * angle, scale, intensity); rows with box_cls == -2 are skipped and their draws not read, rows with -1 move like the others (the reference loops
+ * over all of gt_boxes).  Per (step, row) it writes 12 floats at plan + (step * total_boxes + row) * 12: the box as that step's get_points_in_box
+ * (:553-570) sees it -- centre, float32(dx / 2.0 + 0.1), float32(dy / 2.0 + 0.1), dz / 2, float32 of the float64 cos(-rz) / sin(-rz) -- the step's
+ * parameter (float32 offset; cosf / sinf of the float32 angle; float32 scale; the float64 threshold (z + dz / 2) - intensity * dz and its kin,
+ * rounded) and a skip flag.  The boxes are advanced in place: centre coordinate += offset and heading += angle as float64 sums rounded, sizes *=
+ * float32(scale).  Local rotation of boxes wider than 8 columns is refused (np.hstack at :465-468 raises in the reference).
+ * sv_local_transform_points: one thread per point walks, per step, the scene's boxes in order (their plan rows staged through LDS) and applies the
+ * step wherever the test (margin 0.1 in x / y, none in z, all three comparisons <=) holds at the point's current position; a dropout clears keep
+ * and ends the point's walk.  Points with keep == 0 on entry are left alone. */
+int sv_local_transform_plan(float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls, int batch, int total_boxes,
+                            int64_t steps, int num_steps, const double* draws, float* plan, void* stream);
+int sv_local_transform_points(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int32_t* keep, int batch, int max_scene_points,
+                              const int32_t* box_start, const int32_t* box_cnt, int total_boxes, int64_t steps, int num_steps, const float* plan,
+                              void* stream);
+/* global_frustum_dropout_top / _bottom / _left / _right (augmentor_utils.py:323-388): dirs holds num_dirs <= 16 codes of 4 bits (1 top, 2 bottom on z;
+ * 3 left, 4 right on y), applied in order, each over the survivors of the last; intensity (batch, num_dirs) fp64.  Per direction the minimum and
+ * maximum of the coordinate over the scene's live points (integer atomics on an order-preserving code: equal bits run to run), the threshold
+ * max - intensity * (max - min) or min + intensity * (max - min) in float64, rounded; points and boxes (box_cls >= -1, by their centre) that fail
+ * the strict < / > get keep = 0 / box_cls = -2.  The reference shortens gt_boxes but not gt_names; here the class goes with the box.  A scene
+ * without live points is left alone.  scratch: sv_world_frustum_dropout_scratch_bytes bytes, uninitialised. */
+size_t sv_world_frustum_dropout_scratch_bytes(int batch, int num_dirs);
+int sv_world_frustum_dropout(const float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int32_t* keep, int batch,
+                             int max_scene_points, const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, int32_t* box_cls,
+                             int total_boxes, int64_t dirs, int num_dirs, const double* intensity, void* scratch, void* stream);
+
 /* Mesh ray casting for the VCN's "VC" training data (csrc/raycast.hip); replaces open3d.t.geometry.RaycastingScene (Embree, CPU) in
  * see/surface_completion/models/vcn/vc_shapenet/dataset_functions.py:265-342 and raycast_surface_from_meshes.py:16-52.  The arithmetic is stated in
  * tests/raycast_reference.py: Moeller-Trumbore without culling in fp32, one rounding per operation; a triangle is hit when det != 0 && u >= 0 &&

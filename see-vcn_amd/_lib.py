@@ -264,6 +264,10 @@ SIGNATURES = {
     "sv_world_transform_boxes": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_i, c_p]),
     "sv_augment_compact_scratch_bytes": (c_sz, [c_i, c_i]),
     "sv_augment_compact": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "sv_local_transform_plan": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p]),
+    "sv_local_transform_points": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i64, c_i, c_p, c_p]),
+    "sv_world_frustum_dropout_scratch_bytes": (c_sz, [c_i, c_i]),
+    "sv_world_frustum_dropout": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_p, c_p]),
     "sv_bvh_scratch_bytes": (c_sz, [c_i64]),
     "sv_bvh_keys": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p]),
     "sv_bvh_build": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),

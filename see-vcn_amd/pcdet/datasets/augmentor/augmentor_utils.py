@@ -199,6 +199,126 @@ def random_translation_along_z(batch, offset):
     world_transform(batch, ["translation_z"], _per_scene(batch, offset))
 
 
+# ------------------------------------------------------------------ local and frustum augmentors (csrc/augment_local.hip)
+LOCAL_STEPS = {"local_translation_x": 1, "local_translation_y": 2, "local_translation_z": 3, "local_rotation": 4, "local_scaling": 5,
+               "local_dropout_top": 6, "local_dropout_bottom": 7, "local_dropout_left": 8, "local_dropout_right": 9}
+WORLD_DROPOUT = {"world_dropout_top": 1, "world_dropout_bottom": 2, "world_dropout_left": 3, "world_dropout_right": 4}
+PLAN_ROW = 12
+
+
+def local_transform(batch, steps, params):
+    """`steps`: names from LOCAL_STEPS in the order they apply; params (N, len(steps)) fp64, one draw per box row and step (rows with box_cls == -2
+    are not read).  Every run of up to 16 steps is one plan call (a thread per box) and one points call (a thread per point walks the boxes in
+    order, step by step), whatever the number of boxes.  get_points_in_box (augmentor_utils.py:553-570) is the test: margin 0.1 in x / y, <=."""
+    if "local_rotation" in steps and batch.box_width > 8:
+        # np.hstack((gt_boxes[idx, 7:9], np.zeros((gt_boxes.shape[0], 1)))) raises ValueError for any N != 1 in the reference
+        raise NotImplementedError("local_rotation on boxes wider than 8 columns (augmentor_utils.py:465-468)")
+    if len(steps) == 0 or batch.total_boxes == 0:
+        return
+    dev, N = batch.points.device, batch.total_boxes
+    p = _device_f64(params, dev)
+    assert tuple(p.shape) == (N, len(steps))
+    for first in range(0, len(steps), 16):
+        run = steps[first:first + 16]
+        code = 0
+        for i, name in enumerate(run):
+            code |= LOCAL_STEPS[name] << (4 * i)
+        draws = p if len(run) == len(steps) else p[:, first:first + 16].contiguous()
+        plan = torch.empty(len(run) * N * PLAN_ROW, dtype=torch.float32, device=dev)
+        call("sv_local_transform_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, N, code, len(run), L.ptr(draws), L.ptr(plan),
+             L.stream())
+        call("sv_local_transform_points", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, L.ptr(batch.box_start),
+             L.ptr(batch.box_cnt), N, code, len(run), L.ptr(plan), L.stream())
+
+
+def _per_box(batch, values):
+    return np.asarray(values, np.float64).reshape(batch.total_boxes, 1)
+
+
+def random_local_translation_along_x(batch, offsets):
+    """augmentor_utils.py:257-277; offsets: one per box row (the draws)."""
+    local_transform(batch, ["local_translation_x"], _per_box(batch, offsets))
+
+
+def random_local_translation_along_y(batch, offsets):
+    """augmentor_utils.py:280-300."""
+    local_transform(batch, ["local_translation_y"], _per_box(batch, offsets))
+
+
+def random_local_translation_along_z(batch, offsets):
+    """augmentor_utils.py:303-320."""
+    local_transform(batch, ["local_translation_z"], _per_box(batch, offsets))
+
+
+def local_rotation(batch, noise_rotation):
+    """augmentor_utils.py:425-470; one angle per box row.  Boxes wider than 8 columns raise, as they do there."""
+    local_transform(batch, ["local_rotation"], _per_box(batch, noise_rotation))
+
+
+def local_scaling(batch, noise_scale):
+    """augmentor_utils.py:391-422; one factor per box row (the caller skips the call when the range is narrower than 1e-3)."""
+    local_transform(batch, ["local_scaling"], _per_box(batch, noise_scale))
+
+
+def local_frustum_dropout_top(batch, intensity):
+    """augmentor_utils.py:473-490; one intensity per box row."""
+    local_transform(batch, ["local_dropout_top"], _per_box(batch, intensity))
+
+
+def local_frustum_dropout_bottom(batch, intensity):
+    """augmentor_utils.py:493-510."""
+    local_transform(batch, ["local_dropout_bottom"], _per_box(batch, intensity))
+
+
+def local_frustum_dropout_left(batch, intensity):
+    """augmentor_utils.py:513-530 (the box's extent along world y)."""
+    local_transform(batch, ["local_dropout_left"], _per_box(batch, intensity))
+
+
+def local_frustum_dropout_right(batch, intensity):
+    """augmentor_utils.py:533-550."""
+    local_transform(batch, ["local_dropout_right"], _per_box(batch, intensity))
+
+
+def world_frustum_dropout(batch, directions, intensity):
+    """`directions`: names from WORLD_DROPOUT in order, each over the survivors of the last; intensity (B, len(directions)) fp64.  One library call.
+    Deviations from augmentor_utils.py:323-388: a dropped box takes its class with it (box_cls = -2; the reference shortens gt_boxes and leaves
+    gt_names / gt_boxes_mask at their old length), and a scene without live points passes through (np.max of an empty array raises there)."""
+    if len(directions) > 16:
+        raise ValueError("at most 16 directions in one call")
+    if len(directions) == 0:
+        return
+    code = 0
+    for i, name in enumerate(directions):
+        code |= WORLD_DROPOUT[name] << (4 * i)
+    dev, B = batch.points.device, batch.batch_size
+    v = _device_f64(intensity, dev)
+    assert tuple(v.shape) == (B, len(directions))
+    scratch = _ws.scratch("world_frustum_dropout", max(int(L.load().sv_world_frustum_dropout_scratch_bytes(B, len(directions))), 4), dev)
+    call("sv_world_frustum_dropout", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
+         batch.total_boxes, code, len(directions), L.ptr(v), L.ptr(scratch), L.stream())
+
+
+def global_frustum_dropout_top(batch, intensity):
+    """augmentor_utils.py:323-337; one intensity per scene."""
+    world_frustum_dropout(batch, ["world_dropout_top"], _per_scene(batch, intensity))
+
+
+def global_frustum_dropout_bottom(batch, intensity):
+    """augmentor_utils.py:340-354."""
+    world_frustum_dropout(batch, ["world_dropout_bottom"], _per_scene(batch, intensity))
+
+
+def global_frustum_dropout_left(batch, intensity):
+    """augmentor_utils.py:357-371."""
+    world_frustum_dropout(batch, ["world_dropout_left"], _per_scene(batch, intensity))
+
+
+def global_frustum_dropout_right(batch, intensity):
+    """augmentor_utils.py:374-388."""
+    world_frustum_dropout(batch, ["world_dropout_right"], _per_scene(batch, intensity))
+
+
 def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
     """sv_augment_compact without the host read: (out_points, out_meta, gt, box_keep).  batch.keep holds the points' final flags afterwards."""
     dev, B, C, W = batch.points.device, batch.batch_size, batch.num_point_features, batch.box_width

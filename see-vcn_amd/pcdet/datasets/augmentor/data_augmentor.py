@@ -4,6 +4,11 @@ datasets/dataset.py:126-172) for scenes that are already on the device.
 `draw_params` makes every random draw on the host, scene by scene and in the reference's call order, from a numpy RandomState;
 `BatchDataAugmentor.forward` uploads them once and runs MIN_POINTS_OF_GT, the augmentors of AUG_CONFIG_LIST, the class filter and the point
 half of DataProcessor as a fixed number of library calls with one host read, and returns the batch_dict the detectors consume.
+
+Staged draws.  The local augmentors draw once per box, counted by the boxes that exist at that point of the queue, and two ops change that count
+on the device: gt_sampling (by its acceptances) and random_world_frustum_dropout (by the boxes it drops).  A queue in which a per-box draw
+follows one of the two is cut behind it into stages: `forward` then takes one RandomState per scene, draws every scene's stream up to the
+boundary, runs the device work, reads the class codes back (one host read per boundary, a number fixed by the queue) and continues every stream.
 """
 import numpy as np
 import torch
@@ -14,7 +19,15 @@ from . import database_sampler
 
 NUM_TRY = 50                                                     # scale_pre_object's default (augmentor_utils.py:10)
 
-BUILT = ("gt_sampling", "random_object_scaling", "random_world_flip", "random_world_rotation", "random_world_scaling", "random_world_translation")
+BUILT = ("gt_sampling", "random_object_scaling", "random_world_flip", "random_world_rotation", "random_world_scaling", "random_world_translation",
+         "random_local_rotation", "random_local_scaling", "random_local_translation", "random_world_frustum_dropout",
+         "random_local_frustum_dropout")
+BOUNDARY = ("gt_sampling", "random_world_frustum_dropout")       # they change the number of boxes on the device
+DIRECTIONS = ("top", "bottom", "left", "right")
+# the keys the local / frustum entries are read by (data_augmentor.py:134-219); the reference has no default for any of them
+REQUIRED = {"random_local_rotation": ("LOCAL_ROT_ANGLE",), "random_local_scaling": ("LOCAL_SCALE_RANGE",),
+            "random_local_translation": ("LOCAL_TRANSLATION_RANGE", "ALONG_AXIS_LIST"),
+            "random_world_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION"), "random_local_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION")}
 
 
 def _queue(augmentor_configs):
@@ -29,11 +42,129 @@ def _queue(augmentor_configs):
             continue
         if name not in BUILT:
             raise NotImplementedError(name)
+        for key in REQUIRED.get(name, ()):
+            if cfg_get(cur, key) is None:                        # refused when the queue is built, not at the first draw
+                raise NotImplementedError(f"{name} without {key}")
         if name == "random_object_scaling" and any(cfg_get(q, "NAME") == "gt_sampling" for q in queue):
             # the reference's gt_sampling pops gt_boxes_mask, which its random_object_scaling then looks up (data_augmentor.py:48)
             raise NotImplementedError("random_object_scaling after gt_sampling")
+        if name == "random_object_scaling" and any(cfg_get(q, "NAME") == "random_world_frustum_dropout" for q in queue):
+            # the reference's dropout shortens gt_boxes but not the gt_boxes_mask that random_object_scaling indexes with
+            raise NotImplementedError("random_object_scaling after random_world_frustum_dropout")
         queue.append(cur)
     return queue
+
+
+def _draws_per_box(cur):
+    """Whether the entry makes a draw per box of the scene."""
+    name = cfg_get(cur, "NAME")
+    if name == "random_local_scaling":
+        r = cfg_get(cur, "LOCAL_SCALE_RANGE")
+        return not r[1] - r[0] < 1e-3
+    return name in ("random_object_scaling", "random_local_rotation", "random_local_translation", "random_local_frustum_dropout")
+
+
+def _stages(queue):
+    """The queue cut behind every gt_sampling / random_world_frustum_dropout that a per-box draw follows; one stage for every queue without."""
+    stages, cur = [], []
+    for i, q in enumerate(queue):
+        if cfg_get(q, "NAME") == "gt_sampling" and stages:
+            # its draw needs the names of the boxes that are left, which only the device knows by then
+            raise NotImplementedError("gt_sampling behind a per-box draw that follows random_world_frustum_dropout")
+        cur.append(q)
+        if cfg_get(q, "NAME") in BOUNDARY and any(_draws_per_box(r) for r in queue[i + 1:]):
+            stages.append(cur)
+            cur = []
+    return stages + [cur]
+
+
+def _entry_names(cur):
+    """The names of the draws one queue entry makes, in order (fixed by the config)."""
+    name = cfg_get(cur, "NAME")
+    if name == "gt_sampling":
+        return ["gt_sampling"]
+    if name == "random_object_scaling":
+        return ["object_scaling"]
+    if name == "random_world_flip":
+        return ["flip_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
+    if name == "random_world_rotation":
+        return ["rotation"]
+    if name == "random_world_scaling":
+        r = cfg_get(cur, "WORLD_SCALE_RANGE")
+        return [] if r[1] - r[0] < 1e-3 else ["scaling"]
+    if name == "random_world_translation":
+        return [] if cfg_get(cur, "NOISE_TRANSLATE_STD") == 0 else ["translation_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
+    if name == "random_local_translation":
+        return ["local_translation_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
+    if name == "random_local_rotation":
+        return ["local_rotation"]
+    if name == "random_local_scaling":
+        return ["local_scaling"] if _draws_per_box(cur) else []
+    if name == "random_world_frustum_dropout":
+        return ["world_dropout_" + d for d in cfg_get(cur, "DIRECTION")]
+    if name == "random_local_frustum_dropout":
+        return ["local_dropout_" + d for d in cfg_get(cur, "DIRECTION")]
+    raise NotImplementedError(name)
+
+
+def _draw_scene(rng, entries, n, sampler=None, gt_names=None):
+    """One scene's draws for a run of queue entries: [(name, value), ...] in draw order; n: the boxes the scene holds at that point."""
+    draws = []
+
+    def per_box(lo, hi):
+        return np.array([rng.uniform(lo, hi) for _ in range(int(n))], np.float64)   # one Python-float draw per box, as the reference's loop makes them
+
+    for cur in entries:
+        name = cfg_get(cur, "NAME")
+        if name == "gt_sampling":
+            draws.append(("gt_sampling", sampler.draw(gt_names, rng)))
+        elif name == "random_object_scaling":
+            s = cfg_get(cur, "SCALE_UNIFORM_NOISE")
+            s = list(s) if isinstance(s, (list, tuple, np.ndarray)) else [-s, s]
+            draws.append(("object_scaling", rng.uniform(s[0], s[1], size=[int(n), NUM_TRY])))
+        elif name == "random_world_flip":
+            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
+                assert axis in ("x", "y")
+                draws.append(("flip_" + axis, bool(rng.choice([False, True], replace=False, p=[0.5, 0.5]))))
+        elif name == "random_world_rotation":
+            r = cfg_get(cur, "WORLD_ROT_ANGLE")
+            r = list(r) if isinstance(r, (list, tuple)) else [-r, r]
+            draws.append(("rotation", rng.uniform(r[0], r[1])))
+        elif name == "random_world_scaling":
+            r = cfg_get(cur, "WORLD_SCALE_RANGE")
+            if not r[1] - r[0] < 1e-3:
+                draws.append(("scaling", rng.uniform(r[0], r[1])))
+        elif name == "random_world_translation":
+            std = cfg_get(cur, "NOISE_TRANSLATE_STD")
+            if std == 0:
+                continue
+            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
+                assert axis in ("x", "y", "z")
+                draws.append(("translation_" + axis, float(rng.normal(0, std, 1)[0])))
+        elif name == "random_local_translation":
+            r = cfg_get(cur, "LOCAL_TRANSLATION_RANGE")
+            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):           # every axis is a whole pass over the boxes
+                assert axis in ("x", "y", "z")
+                draws.append(("local_translation_" + axis, per_box(r[0], r[1])))
+        elif name == "random_local_rotation":
+            r = cfg_get(cur, "LOCAL_ROT_ANGLE")
+            r = list(r) if isinstance(r, (list, tuple)) else [-r, r]
+            draws.append(("local_rotation", per_box(r[0], r[1])))
+        elif name == "random_local_scaling":
+            r = cfg_get(cur, "LOCAL_SCALE_RANGE")
+            if not r[1] - r[0] < 1e-3:
+                draws.append(("local_scaling", per_box(r[0], r[1])))
+        elif name == "random_world_frustum_dropout":
+            r = cfg_get(cur, "INTENSITY_RANGE")
+            for d in cfg_get(cur, "DIRECTION"):
+                assert d in DIRECTIONS
+                draws.append(("world_dropout_" + d, rng.uniform(r[0], r[1])))
+        elif name == "random_local_frustum_dropout":
+            r = cfg_get(cur, "INTENSITY_RANGE")
+            for d in cfg_get(cur, "DIRECTION"):
+                assert d in DIRECTIONS
+                draws.append(("local_dropout_" + d, per_box(r[0], r[1])))
+    return draws
 
 
 def draw_params(rng, augmentor_configs, num_boxes, sampler=None, gt_names=None):
@@ -46,40 +177,22 @@ def draw_params(rng, augmentor_configs, num_boxes, sampler=None, gt_names=None):
       random_world_rotation     uniform(lo, hi)                                                   :130
       random_world_scaling      uniform(lo, hi), nothing when hi - lo < 1e-3                      :153-155
       random_world_translation  normal(0, std, 1) per axis, nothing at all when std == 0          data_augmentor.py:120-122, :211
-    Returns one list per scene of (name, value) in draw order; ops without a draw are left out."""
+      random_local_translation  uniform(lo, hi) per axis, per box                                 augmentor_utils.py:267, :290, :313
+      random_local_rotation     uniform(lo, hi) per box                                           :435
+      random_local_scaling      uniform(lo, hi) per box, nothing at all when hi - lo < 1e-3       :399-404
+      random_world_frustum_dropout   uniform(lo, hi) per direction                                :331, :348, :365, :382
+      random_local_frustum_dropout   uniform(lo, hi) per direction, per box                       :484, :504, :524, :544
+    Returns one list per scene of (name, value) in draw order; ops without a draw are left out; a per-box draw is an (n,) float64 array.
+    A queue in which a per-box draw follows gt_sampling or random_world_frustum_dropout cannot be drawn ahead: ValueError (see forward)."""
     queue = _queue(augmentor_configs)
-    out = []
-    for n in num_boxes:
-        draws = []
-        for cur in queue:
-            name = cfg_get(cur, "NAME")
-            if name == "gt_sampling":
-                draws.append(("gt_sampling", sampler.draw(gt_names[len(out)], rng)))
-            elif name == "random_object_scaling":
-                s = cfg_get(cur, "SCALE_UNIFORM_NOISE")
-                s = list(s) if isinstance(s, (list, tuple, np.ndarray)) else [-s, s]
-                draws.append(("object_scaling", rng.uniform(s[0], s[1], size=[int(n), NUM_TRY])))
-            elif name == "random_world_flip":
-                for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
-                    assert axis in ("x", "y")
-                    draws.append(("flip_" + axis, bool(rng.choice([False, True], replace=False, p=[0.5, 0.5]))))
-            elif name == "random_world_rotation":
-                r = cfg_get(cur, "WORLD_ROT_ANGLE")
-                r = list(r) if isinstance(r, (list, tuple)) else [-r, r]
-                draws.append(("rotation", rng.uniform(r[0], r[1])))
-            elif name == "random_world_scaling":
-                r = cfg_get(cur, "WORLD_SCALE_RANGE")
-                if not r[1] - r[0] < 1e-3:
-                    draws.append(("scaling", rng.uniform(r[0], r[1])))
-            elif name == "random_world_translation":
-                std = cfg_get(cur, "NOISE_TRANSLATE_STD")
-                if std == 0:
-                    continue
-                for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
-                    assert axis in ("x", "y", "z")
-                    draws.append(("translation_" + axis, float(rng.normal(0, std, 1)[0])))
-        out.append(draws)
-    return out
+    if len(_stages(queue)) > 1:
+        raise ValueError("a per-box draw follows gt_sampling or random_world_frustum_dropout: the number of boxes it is sized by is decided on the "
+                         "device, so one shared stream cannot be replayed; give forward() one RandomState per scene")
+    return [_draw_scene(rng, queue, n, sampler, None if gt_names is None else gt_names[b]) for b, n in enumerate(num_boxes)]
+
+
+def _kind(name):
+    return "world" if name in A.OPS else "local" if name in A.LOCAL_STEPS else "drop" if name in A.WORLD_DROPOUT else name
 
 
 class BatchDataAugmentor:
@@ -87,13 +200,20 @@ class BatchDataAugmentor:
 
     scenes: a list of dicts with points (n, C) and gt_boxes (m, W >= 7) fp32 device tensors, gt_names (m,) host strings and optionally
     num_points_in_gt (m,) host integers (as the reference's infos carry them).  Without num_points_in_gt the per-box counts are made on the device
-    and read back once more: the reference sizes its uniform(size=[N, 50]) draw by the number of boxes that pass MIN_POINTS_OF_GT."""
+    and read back once more: the reference sizes its uniform(size=[N, 50]) draw by the number of boxes that pass MIN_POINTS_OF_GT.
+
+    forward(scenes, rng): rng is one RandomState for the batch (scene by scene from one stream) or a list of one per scene; per scene the result
+    then equals the reference run on that sample alone from that state.  A staged queue (module docstring) needs the list, and costs one more
+    host read per boundary.  The local augmentors move every box that exists (box_cls != -2), those of other classes too, as the reference's
+    loops over gt_boxes do; behind a gt_sampling that accepted something, the scene's boxes of other classes are gone, as they are there
+    (database_sampler.py: gt_boxes[gt_boxes_mask]).  random_local_pyramid_aug is not built and raises."""
 
     def __init__(self, root_path, augmentor_configs, class_names, logger=None, min_points_of_gt=1, data_processor=None, db_infos=None,
                  database=None):
         self.root_path, self.class_names, self.logger = root_path, list(class_names), logger
         self.augmentor_configs = augmentor_configs
         self.data_augmentor_queue = _queue(augmentor_configs)
+        self.stages = _stages(self.data_augmentor_queue)
         self.min_points_of_gt = int(min_points_of_gt)
         self.data_processor = data_processor
         self.db_sampler = None
@@ -103,6 +223,77 @@ class BatchDataAugmentor:
 
     def _class_index(self, names):
         return np.array([self.class_names.index(n) if n in self.class_names else -1 for n in names], np.int32)
+
+    def _run_stage(self, batch, draws, rows, codes, candidates, last):
+        """One stage on the device: one upload (the class codes with the first stage, then every draw of the stage), then the queue in order;
+        consecutive world transforms, consecutive local steps and consecutive world dropouts share their launches."""
+        B, N, dev = batch.batch_size, batch.total_boxes, batch.points.device
+        names = [name for name, _ in draws[0]]
+        assert all([name for name, _ in d] == names for d in draws), "every scene makes the same draws"
+        count = {k: sum(_kind(n) == k for n in names) for k in ("world", "local", "drop")}
+        noises = np.zeros((max(N, 1) if "object_scaling" in names else 0, NUM_TRY))
+        world, local, drop = np.zeros((B, count["world"])), np.zeros((N, count["local"])), np.zeros((B, count["drop"]))
+        for b, d in enumerate(draws):
+            col = {"world": 0, "local": 0, "drop": 0}
+            for name, value in d:
+                k = _kind(name)
+                if name == "object_scaling":
+                    assert np.shape(value) == (len(rows[b]), NUM_TRY)
+                    noises[rows[b]] = value                      # row i of the draw belongs to the i-th box that exists
+                elif k == "local":
+                    value = np.asarray(value, np.float64).reshape(-1)
+                    if len(value) != len(rows[b]):
+                        raise ValueError(f"scene {b}: {name} holds {len(value)} draws, the scene has {len(rows[b])} boxes at that point")
+                    local[rows[b], col[k]] = value
+                    col[k] += 1
+                elif k in col:
+                    (world if k == "world" else drop)[b, col[k]] = float(value)
+                    col[k] += 1
+        parts = ([] if codes is None else [codes.astype(np.float64)]) + [noises.reshape(-1), world.reshape(-1), local.reshape(-1), drop.reshape(-1)]
+        up = torch.from_numpy(np.concatenate(parts)).to(dev)
+        at = 0
+        if codes is not None:
+            batch.box_cls[:N].copy_(up[:N].to(torch.int32))
+            at = N
+        noises_d = up[at:at + noises.size].view(noises.shape)[:N]
+        at += noises.size
+        params = {}
+        for k, host in (("world", world), ("local", local), ("drop", drop)):
+            params[k] = up[at:at + host.size].view(host.shape)
+            at += host.size
+        done = {"world": 0, "local": 0, "drop": 0}
+        pending, kind = [], None
+        for name in names + [None]:
+            k = None if name is None else _kind(name)
+            if k in done and (k == kind or not pending):
+                pending.append(name)
+                kind = k
+                continue
+            final = name is None and last
+            if pending:
+                p = params[kind][:, done[kind]:done[kind] + len(pending)].contiguous()
+                done[kind] += len(pending)
+                if kind == "local":
+                    A.local_transform(batch, pending, p)
+                elif kind == "drop":
+                    A.world_frustum_dropout(batch, pending, p)
+                else:
+                    A.world_transform(batch, pending, p, limit_heading=final)
+            if final and kind != "world":
+                A.world_transform(batch, [], None, limit_heading=True)
+            pending, kind = ([name], k) if k in done else ([], None)
+            if name == "object_scaling":
+                A.scale_pre_object(batch, noises_d)
+            elif name == "gt_sampling":
+                before = batch.box_cnt.clone()
+                self.db_sampler(batch, candidates)
+                if not last:
+                    # the reference keeps gt_boxes[gt_boxes_mask] + the sampled boxes wherever something was accepted (database_sampler.py:
+                    # add_sampled_boxes_to_scene): for the per-box ops that follow, that scene's boxes of other classes do not exist
+                    sizes = np.diff(np.append(batch.box_offsets, N))
+                    scene = torch.from_numpy(np.repeat(np.arange(B), sizes)).to(dev)
+                    cls = batch.box_cls[:N]
+                    cls.copy_(torch.where((cls == -1) & (batch.box_cnt > before)[scene], torch.full_like(cls, -2), cls))
 
     def forward(self, scenes, rng=None, draws=None):
         cls = [self._class_index(s["gt_names"]) for s in scenes]
@@ -118,58 +309,56 @@ class BatchDataAugmentor:
         sizes = np.array([len(c) for c in cls], np.int64)
         ends = np.cumsum(sizes)
         present = [present[e - n:e] for e, n in zip(ends, sizes)]
-        if draws is None:
-            names = [np.asarray(s["gt_names"])[p] for s, p in zip(scenes, present)]
-            draws = draw_params(rng if rng is not None else np.random, self.augmentor_configs, [int(p.sum()) for p in present], self.db_sampler, names)
-        B = len(scenes)
-        candidates = [next((v for n, v in d if n == "gt_sampling"), []) for d in draws]
+        B, stages = len(scenes), self.stages
+        per_scene = isinstance(rng, (list, tuple))
+        if per_scene and len(rng) != B:
+            raise ValueError(f"{len(rng)} random states for {B} scenes")
+        if draws is None and len(stages) > 1 and not per_scene:
+            raise ValueError("this queue makes a per-box draw behind gt_sampling or random_world_frustum_dropout, whose number of boxes is decided "
+                             "on the device: scene 1's draws would have to come before it is known how many scene 0 makes, so one shared "
+                             "stream cannot follow the reference; pass rng as a list of one numpy RandomState per scene")
+        given, taken = draws, [0] * B
+        names = [np.asarray(s["gt_names"])[p] for s, p in zip(scenes, present)]
+        num_boxes = [int(p.sum()) for p in present]
+
+        def stage_draws(entries):
+            if given is not None:
+                n = sum(len(_entry_names(cur)) for cur in entries)
+                out = [list(given[b][taken[b]:taken[b] + n]) for b in range(B)]
+                for b in range(B):
+                    taken[b] += n
+                return out
+            if per_scene:
+                return [_draw_scene(rng[b], entries, num_boxes[b], self.db_sampler, names[b]) for b in range(B)]
+            return draw_params(rng if rng is not None else np.random, self.augmentor_configs, num_boxes, self.db_sampler, names)
+
+        first = stage_draws(stages[0]) if len(stages) > 1 or given is None else [list(d) for d in given]
+        candidates = [next((v for n, v in d if n == "gt_sampling"), []) for d in first]
         if any(candidates):
             npts = self.db_sampler.database.counts
             batch = A.DeviceBatch.from_scenes(pts, boxes, cls, [int(sum(npts[i["db_index"]] for _, i in c)) for c in candidates],
                                               [len(c) for c in candidates])
         elif batch is None:
             batch = A.DeviceBatch.from_scenes(pts, boxes, cls)
-        # one upload: the class codes after the filter, then every draw of the batch
         N = batch.total_boxes
-        names = [name for name, _ in draws[0]]
-        assert all([name for name, _ in d] == names for d in draws), "every scene makes the same draws"
-        codes = np.full(N, -2, np.int32)
-        noises = np.zeros((max(N, 1), NUM_TRY))
-        world = [name for name in names if name not in ("object_scaling", "gt_sampling")]
-        params = np.zeros((B, max(len(world), 1)))
-        for b, d in enumerate(draws):
-            first = batch.box_offsets[b]
-            codes[first:first + sizes[b]] = np.where(present[b], cls[b], -2)
-            rows = first + np.nonzero(present[b])[0]
-            col = 0
-            for name, value in d:
-                if name == "object_scaling":
-                    assert value.shape == (len(rows), NUM_TRY)
-                    noises[rows] = value                         # row i of the draw belongs to the i-th box that passed the filter
-                elif name != "gt_sampling":
-                    params[b, col] = float(value)
-                    col += 1
-        dev = batch.points.device
-        up = torch.from_numpy(np.concatenate([codes.astype(np.float64), noises.reshape(-1), params.reshape(-1)])).to(dev)
-        batch.box_cls[:N].copy_(up[:N].to(torch.int32))
-        noises_d = up[N:N + noises.size].view(-1, NUM_TRY)[:N]
-        params_d = up[N + noises.size:].view(B, -1)
-        # the queue in order; consecutive world transforms share one pair of launches
-        pending, done = [], 0
-        for name in names + [None]:
-            if name is not None and name not in ("object_scaling", "gt_sampling"):
-                pending.append(name)
-                continue
-            last = name is None
-            if pending or last:
-                A.world_transform(batch, pending, params_d[:, done:done + len(pending)].contiguous() if pending else None, limit_heading=last)
-                done += len(pending)
-                pending = []
-            if name == "object_scaling":
-                A.scale_pre_object(batch, noises_d)
-            elif name == "gt_sampling":
-                self.db_sampler(batch, candidates)
+        codes = np.full(N, -2, np.int32)                          # the class codes after the filter
+        rows = []
+        for b in range(B):
+            start = batch.box_offsets[b]
+            codes[start:start + sizes[b]] = np.where(present[b], cls[b], -2)
+            rows.append(start + np.nonzero(present[b])[0])
+        all_draws = [list(d) for d in first]
+        self._run_stage(batch, first, rows, codes, candidates, len(stages) == 1)
+        bounds = np.append(batch.box_offsets, N)
+        for s in range(1, len(stages)):
+            now = A.read(batch.box_cls[:N])                      # the boundary: which box rows exist now
+            rows = [bounds[b] + np.nonzero(now[bounds[b]:bounds[b + 1]] != -2)[0] for b in range(B)]
+            num_boxes = [len(r) for r in rows]
+            cur = stage_draws(stages[s])
+            for b in range(B):
+                all_draws[b] += cur[b]
+            self._run_stage(batch, cur, rows, None, candidates, s == len(stages) - 1)
         dp = self.data_processor
         out = A.compact(batch, **(dp.tail_args() if dp is not None else {}))
-        out["draws"] = draws
+        out["draws"] = all_draws
         return out

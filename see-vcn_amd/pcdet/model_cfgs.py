@@ -418,3 +418,25 @@ def caddn_model_cfg(backbone_name='ResNet101', pretrained_path=CADDN_PRETRAINED_
     return dict(NAME='CaDDN', VFE=vfe,
                 MAP_TO_BEV=dict(NAME='Conv2DCollapse', NUM_BEV_FEATURES=feat_channels, ARGS=dict(kernel_size=1, stride=1, bias=False)),
                 BACKBONE_2D=dict(PP_BACKBONE_2D, LAYER_NUMS=list(layer_nums)), DENSE_HEAD=PP_DENSE_HEAD, POST_PROCESSING=SECOND_POST_PROCESSING)
+
+
+def pointpillar_newaugs_augmentor_cfg():
+    """DATA_CONFIG.DATA_AUGMENTOR of detector3d/tools/cfgs/kitti_models/pointpillar_newaugs.yaml:23-70, values copied as data.  The YAML spells the
+    world translation's key WORLD_TRANSLATION_RANGE while the code reads NOISE_TRANSLATE_STD: with that entry enabled the reference raises, and so
+    does BatchDataAugmentor unless the caller adds the key."""
+    return dict(
+        DISABLE_AUG_LIST=['random_world_frustum_dropout', 'random_local_frustum_dropout', 'random_local_translation'],
+        AUG_CONFIG_LIST=[
+            dict(NAME='gt_sampling', USE_ROAD_PLANE=False, DB_INFO_PATH=['kitti_dbinfos_train.pkl'],
+                 PREPARE=dict(filter_by_min_points=['Car:5', 'Pedestrian:5', 'Cyclist:5'], filter_by_difficulty=[-1, 2]),
+                 SAMPLE_GROUPS=['Car:15', 'Pedestrian:15', 'Cyclist:15'], NUM_POINT_FEATURES=4, DATABASE_WITH_FAKELIDAR=False,
+                 REMOVE_EXTRA_WIDTH=[0.0, 0.0, 0.0], LIMIT_WHOLE_SCENE=False),
+            dict(NAME='random_local_rotation', LOCAL_ROT_ANGLE=[-0.15707963267, 0.15707963267]),
+            dict(NAME='random_local_scaling', LOCAL_SCALE_RANGE=[0.95, 1.05]),
+            dict(NAME='random_world_flip', ALONG_AXIS_LIST=['x']),
+            dict(NAME='random_world_rotation', WORLD_ROT_ANGLE=[-0.78539816, 0.78539816]),
+            dict(NAME='random_world_scaling', WORLD_SCALE_RANGE=[0.95, 1.05]),
+            dict(NAME='random_world_translation', WORLD_TRANSLATION_RANGE=[-0.2, 0.2], ALONG_AXIS_LIST=['x', 'y', 'z']),
+            dict(NAME='random_local_translation', LOCAL_TRANSLATION_RANGE=[0.95, 1.05], ALONG_AXIS_LIST=['x', 'y', 'z']),
+            dict(NAME='random_world_frustum_dropout', INTENSITY_RANGE=[0, 0.2], DIRECTION=['top']),
+            dict(NAME='random_local_frustum_dropout', INTENSITY_RANGE=[0, 0.2], DIRECTION=['top'])])

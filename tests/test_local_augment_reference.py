@@ -1,0 +1,205 @@
+"""tests/local_augment_reference.py against the reference's own functions (tests/golden/local_augment.npz, made by
+tests/golden/make_local_augment_golden.py), the generator's claims, and the host half of the local / frustum augmentors: queue, draws, stages."""
+import os
+
+import numpy as np
+import pytest
+
+import augment_reference as R
+import local_augment_reference as LR
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "local_augment.npz")
+KEYS = [k for k in LR.LOCAL_NAMES + LR.WORLD_NAMES] + ["seq_" + k for k in LR.SEQUENTIAL] + ["translation_xyz", "world_all"]
+
+
+def _golden():
+    if not hasattr(_golden, "data"):
+        _golden.data = np.load(GOLDEN)
+    return _golden.data
+
+
+# ---------------------------------------------------------------------------------------------------------- restatement against golden
+@pytest.mark.parametrize("key", KEYS)
+def test_restatement_matches_the_reference_functions(key):
+    g, case = _golden(), LR.golden_cases()[key]
+    assert np.array_equal(case["boxes"], g[key + "/in_boxes"]) and np.array_equal(case["points"], g[key + "/in_points"])
+    assert int(g[key + "/seed"]) == case["draw_seed"] and np.array_equal(g[key + "/ranges"], [[lo, hi] for _, lo, hi in case["specs"]])
+    s = case["final"]
+    out_p, out_b = g[key + "/out_points"], g[key + "/out_boxes"]
+    # the same rows dropped: the survivors' untouched columns (and for a dropout every column) are the golden's, row for row
+    assert int(s.alive.sum()) == len(out_p) and int(s.exists.sum()) == len(out_b)
+    assert np.array_equal(s.pts[s.alive][:, 3:], out_p[:, 3:])
+    # the same rows moved: a point the restatement did not move is bit-identical in the golden and the others are not where they were
+    diff = np.abs(s.pts[s.alive][:, :3].astype(np.float64) - out_p[:, :3])
+    assert (diff <= s.err[s.alive]).all()
+    moved_ref = (out_p[:, :3] != case["points"][s.alive][:, :3]).any(axis=1)
+    moved_mine = (s.pts[s.alive][:, :3] != case["points"][s.alive][:, :3]).any(axis=1)
+    assert np.array_equal(moved_ref, moved_mine)
+    assert (np.abs(s.boxes[s.exists].astype(np.float64) - out_b) <= s.berr[s.exists]).all()
+    if "rotation" not in key:                                    # the reference rotates with a torch matmul; everything else is bit for bit
+        assert np.array_equal(s.pts[s.alive], out_p)
+    if "translation" not in key and "rotation" not in key:       # box += draw is a float64 sum there under value-based casting, float32 under NumPy 2
+        assert np.array_equal(s.boxes[s.exists], out_b)
+    if "dropout" in key or key == "world_all":
+        assert len(out_p) < len(case["points"])
+    else:
+        assert moved_mine.sum() >= 8
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_replayed_draws_consume_the_reference_stream(key):
+    """After the reference's functions ran under np.random.seed(seed), and after the replay of the same draws, the next uniform() is the same."""
+    g, case = _golden(), LR.golden_cases()[key]
+    rs = np.random.RandomState(case["draw_seed"])
+    for name, lo, hi in case["specs"]:
+        for _ in range(len(case["boxes"]) if name in LR.LOCAL_NAMES else 1):
+            rs.uniform(lo, hi)
+    assert rs.uniform() == float(g[key + "/next_uniform"])
+
+
+# ---------------------------------------------------------------------------------------------------------- the generator's claims
+def test_cases_are_robust_and_hit_their_edges():
+    cases = LR.golden_cases()
+    for key, case in cases.items():
+        s = case["final"]
+        assert s.gap.min() >= R.ROBUST and s.box_gap >= R.ROBUST, key
+        assert np.abs(case["boxes"][:, 6]).max() <= np.pi
+    for name in LR.SEQUENTIAL:
+        case = cases["seq_" + name]
+        assert case["final"].moved_decisions >= 8
+        b = case["boxes"]
+        d = np.hypot(b[1::2, 0] - b[0::2, 0], b[1::2, 1] - b[0::2, 1]) - 2.0          # parallel, 2 m wide: face to face
+        assert (d > 0.12 - 1e-4).all() and (d < 0.18 + 1e-4).all() and np.array_equal(b[0::2, 6], b[1::2, 6])
+        # testing every box against the original points gives another result
+        flat = LR.Scene(b, case["points"])
+        name_, values = case["ops"][0]
+        for k in range(len(b)):
+            one = LR.Scene(b, case["points"])
+            one.exists[:] = False
+            one.exists[k] = True
+            LR.local_step(one, name_, values[k:k + 1])
+            moved = (one.pts != case["points"]).any(axis=1)
+            flat.pts[moved] = one.pts[moved]
+        assert ((flat.pts != case["final"].pts).any(axis=1)).sum() >= 8
+    assert cases["translation_xyz"]["differ"] >= 8
+    assert max(np.abs(c["boxes"][:, 6]).max() for c in cases.values()) > 3.0            # headings up to pi
+    w = cases["world_all"]["final"]
+    assert 0 < w.exists.sum() < len(w.exists) and 0 < w.alive.sum() < len(w.alive)
+
+
+def test_in_box_test_is_the_local_one():
+    """Margin 0.1 in x / y, none in z, all three comparisons <=; the project's other test (1e-2, strict) answers differently."""
+    box = np.array([0, 0, 0, 4, 2, 1.5, 0], np.float32)
+    pts = np.array([[2.1, 0, 0], [2.1, 1.1, 0.75], [2.11, 0, 0], [0, 1.05, 0], [0, 0, 0.75], [0, 0, 0.7500001], [2.005, 0, 0]], np.float32)
+    mask = LR.get_points_in_box(pts, box)[0]
+    assert mask.tolist() == [True, True, False, True, True, False, True]
+    assert R.in_box(pts, box)[0].tolist() == [False, False, False, False, True, False, True]
+
+
+def test_world_dropout_edges():
+    boxes = np.zeros((2, 7), np.float32)
+    boxes[:, 2] = [0.5, 2.0]
+    pts = np.zeros((6, 4), np.float32)
+    pts[:, 2] = [2.0, 1.0, 2.0, -1.0, 0.0, 2.0]
+    s = LR.run_ops(boxes, pts, [("world_dropout_top", 0.0)])       # intensity 0: exactly the extreme points go, ties included
+    assert s.alive.tolist() == [False, True, False, True, True, False] and s.exists.tolist() == [True, False]
+    s = LR.run_ops(boxes, pts, [("world_dropout_bottom", 0.0)])
+    assert s.alive.tolist() == [True, True, True, False, True, True] and s.exists.tolist() == [True, True]
+    dead = np.array([False, True, False, True, True, False])
+    s = LR.run_ops(boxes, pts, [("world_dropout_top", 0.0)], alive=dead)               # the maximum over the live points only: 1.0
+    assert s.alive.tolist() == [False, False, False, True, True, False]
+    s = LR.run_ops(boxes, pts, [("world_dropout_top", 0.5)], alive=np.zeros(6, bool))  # an empty scene passes through
+    assert s.exists.all() and not s.alive.any()
+
+
+def test_local_rotation_of_wide_boxes_raises_as_the_reference_does():
+    with pytest.raises(ValueError):
+        LR.run_ops(np.zeros((2, 9), np.float32), np.zeros((3, 4), np.float32), [("local_rotation", [0.1, 0.1])])
+
+
+# ---------------------------------------------------------------------------------------------------------- queue, draws, stages
+LOCAL_CFG = [{"NAME": "random_local_rotation", "LOCAL_ROT_ANGLE": [-0.15707963267, 0.15707963267]},
+             {"NAME": "random_local_scaling", "LOCAL_SCALE_RANGE": [0.95, 1.05]},
+             {"NAME": "random_world_flip", "ALONG_AXIS_LIST": ["x"]},
+             {"NAME": "random_local_translation", "LOCAL_TRANSLATION_RANGE": [0.95, 1.05], "ALONG_AXIS_LIST": ["x", "y", "z"]},
+             {"NAME": "random_local_scaling", "LOCAL_SCALE_RANGE": [1.0, 1.0005]},
+             {"NAME": "random_local_rotation", "LOCAL_ROT_ANGLE": 0.1},
+             {"NAME": "random_local_frustum_dropout", "INTENSITY_RANGE": [0, 0.2], "DIRECTION": ["top", "left"]},
+             {"NAME": "random_world_frustum_dropout", "INTENSITY_RANGE": [0, 0.2], "DIRECTION": ["top", "bottom", "left", "right"]}]
+
+
+def _want(rs, n):
+    per_box = lambda lo, hi: np.array([rs.uniform(lo, hi) for _ in range(n)])
+    want = [("local_rotation", per_box(-0.15707963267, 0.15707963267)), ("local_scaling", per_box(0.95, 1.05)),
+            ("flip_x", rs.choice([False, True], replace=False, p=[0.5, 0.5]))]
+    want += [("local_translation_" + a, per_box(0.95, 1.05)) for a in "xyz"]
+    want += [("local_rotation", per_box(-0.1, 0.1))]
+    want += [("local_dropout_" + d, per_box(0, 0.2)) for d in ("top", "left")]
+    want += [("world_dropout_" + d, rs.uniform(0, 0.2)) for d in ("top", "bottom", "left", "right")]
+    return want
+
+
+def test_draw_params_replays_the_local_call_sequence():
+    """One stream, scene by scene: a world dropout at the end of the queue is followed by no per-box draw, so nothing is staged."""
+    from seevcn_amd.pcdet.datasets.augmentor import draw_params
+    rng = np.random.RandomState(17)
+    got = draw_params(rng, LOCAL_CFG, [3, 0, 5])
+    rs = np.random.RandomState(17)
+    for n, d in zip([3, 0, 5], got):
+        want = _want(rs, n)
+        assert [k for k, _ in d] == [k for k, _ in want]
+        assert all(np.array_equal(np.asarray(a), np.asarray(b)) for (_, a), (_, b) in zip(d, want))
+    assert rng.uniform() == rs.uniform()                         # the stream stands where the reference's calls leave it
+    assert got[1][0][1].shape == (0,)
+
+
+def test_staged_drawing_continues_every_scene_stream():
+    """pointpillar_newaugs with everything but gt_sampling enabled: the local dropout follows the world dropout, so the queue has two stages; each
+    scene's own stream, continued behind the boundary with the box count the device reports, is the reference's call sequence on that sample."""
+    from seevcn_amd.pcdet.datasets.augmentor import BatchDataAugmentor, data_augmentor as D, draw_params
+    from seevcn_amd.pcdet.model_cfgs import pointpillar_newaugs_augmentor_cfg
+    cfg = pointpillar_newaugs_augmentor_cfg()
+    assert cfg["DISABLE_AUG_LIST"] == ["random_world_frustum_dropout", "random_local_frustum_dropout", "random_local_translation"]
+    assert len(BatchDataAugmentor(None, dict(cfg, DISABLE_AUG_LIST=cfg["DISABLE_AUG_LIST"] + ["gt_sampling", "random_world_translation"]), ["Car"]).stages) == 1
+    cfg["DISABLE_AUG_LIST"] = ["gt_sampling"]
+    for entry in cfg["AUG_CONFIG_LIST"]:
+        if entry["NAME"] == "random_world_translation":
+            entry["NOISE_TRANSLATE_STD"] = 0.2                   # the YAML's WORLD_TRANSLATION_RANGE is not the key the code reads
+    aug = BatchDataAugmentor(None, cfg, ["Car", "Pedestrian", "Cyclist"])
+    assert [[D.cfg_get(c, "NAME") for c in st] for st in aug.stages] == [
+        ["random_local_rotation", "random_local_scaling", "random_world_flip", "random_world_rotation", "random_world_scaling",
+         "random_world_translation", "random_local_translation", "random_world_frustum_dropout"], ["random_local_frustum_dropout"]]
+    with pytest.raises(ValueError, match="one RandomState per scene"):
+        draw_params(np.random.RandomState(0), cfg, [2, 2])
+    for seed, (n0, n1) in enumerate([(5, 3), (4, 4), (2, 0)]):
+        rng = np.random.RandomState(seed)
+        first = D._draw_scene(rng, aug.stages[0], n0)
+        second = D._draw_scene(rng, aug.stages[1], n1)
+        rs = np.random.RandomState(seed)
+        per_box = lambda lo, hi, n: np.array([rs.uniform(lo, hi) for _ in range(n)])
+        want = [("local_rotation", per_box(-0.15707963267, 0.15707963267, n0)), ("local_scaling", per_box(0.95, 1.05, n0)),
+                ("flip_x", rs.choice([False, True], replace=False, p=[0.5, 0.5])), ("rotation", rs.uniform(-0.78539816, 0.78539816)),
+                ("scaling", rs.uniform(0.95, 1.05))] + [("translation_" + a, rs.normal(0, 0.2, 1)[0]) for a in "xyz"]
+        want += [("local_translation_" + a, per_box(0.95, 1.05, n0)) for a in "xyz"] + [("world_dropout_top", rs.uniform(0, 0.2))]
+        want += [("local_dropout_top", per_box(0, 0.2, n1))]
+        got = first + second
+        assert [k for k, _ in got] == [k for k, _ in want] == sum((D._entry_names(c) for st in aug.stages for c in st), [])
+        assert all(np.array_equal(np.asarray(a), np.asarray(b)) for (_, a), (_, b) in zip(got, want))
+        assert rng.uniform() == rs.uniform()
+
+
+def test_queue_refusals():
+    from seevcn_amd.pcdet.datasets.augmentor import BatchDataAugmentor, draw_params
+    with pytest.raises(NotImplementedError, match="random_local_pyramid_aug"):
+        BatchDataAugmentor(None, [{"NAME": "random_local_pyramid_aug", "DROP_PROB": 0.25}], ["car"])
+    with pytest.raises(NotImplementedError, match="random_local_scaling without LOCAL_SCALE_RANGE"):
+        draw_params(np.random.RandomState(0), [{"NAME": "random_local_scaling"}], [1])
+    drop = {"NAME": "random_world_frustum_dropout", "INTENSITY_RANGE": [0, 0.2], "DIRECTION": ["top"]}
+    with pytest.raises(NotImplementedError, match="random_object_scaling after random_world_frustum_dropout"):
+        BatchDataAugmentor(None, [drop, {"NAME": "random_object_scaling", "SCALE_UNIFORM_NOISE": [0.9, 1.1]}], ["car"])
+    # a narrow LOCAL_SCALE_RANGE draws nothing, so nothing behind the dropout is sized by the boxes: one stage, one shared stream
+    narrow = [drop, {"NAME": "random_local_scaling", "LOCAL_SCALE_RANGE": [1.0, 1.0005]}]
+    assert len(BatchDataAugmentor(None, narrow, ["car"]).stages) == 1
+    rs, replay = np.random.RandomState(5), np.random.RandomState(5)
+    got = draw_params(rs, narrow, [2, 3])
+    assert got == [[("world_dropout_top", replay.uniform(0, 0.2))], [("world_dropout_top", replay.uniform(0, 0.2))]] and rs.uniform() == replay.uniform()
