@@ -5,40 +5,30 @@
 // augmentor_utils.py:10-80 (scale_pre_object), :82-160 and :203-254 (world transforms), datasets/augmentor/data_augmentor.py:258-272,
 // datasets/processor/data_processor.py (mask_points_and_boxes_outside_range), utils/box_utils.py:28-53,93-109.
 //
-// Layout shared by every entry: the batch's points are rows of C floats in one buffer, scene b owns rows pt_start[b] .. pt_start[b] + pt_cnt[b];
-// its boxes are rows of W >= 7 floats [x, y, z, dx, dy, dz, heading, ...] at box_start[b] .. + box_cnt[b] (at most 256 per scene).  box_cls holds
-// one int32 per box row: >= 0 the index into class_names, -1 a box of another class (gt_boxes_mask == 0: never changed, still an obstacle),
-// -2 a box already filtered out (it does not exist for anyone).  keep holds one int32 per point row, 0 = dropped.  Starts and counts live on the
-// device; max_scene_points is a host upper bound of pt_cnt that only sizes the grid.  No float atomics anywhere: equal bits run to run.
+// The batch layout every entry shares is stated in augment.h.
 #include <math.h>
 
+#include "augment.h"
 #include "box_test.h"
 #include "common.h"
 #include "rbox.h"
 #include "wave.h"
 
-constexpr int AUG_MAX_BOXES = 256;
 constexpr int AUG_MAX_TRY = 64;
-constexpr int AUG_THREADS = 256;
 constexpr float AUG_MARGIN = 1e-2f;                            // the CPU matrix test's x/y margin (roiaware_pool3d.cpp:121-165)
-
-__device__ __forceinline__ int aug_box_count(const int32_t* __restrict__ box_cnt, int b) { return min(max(box_cnt[b], 0), AUG_MAX_BOXES); }
 
 // ------------------------------------------------------------------ points per box (dataset.py:131-133)
 __global__ __launch_bounds__(AUG_THREADS) void k_aug_count(const float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
                                                            const int32_t* __restrict__ pt_cnt, const int32_t* __restrict__ keep,
                                                            const float* __restrict__ boxes, int W, const int32_t* __restrict__ box_start,
                                                            const int32_t* __restrict__ box_cnt, int32_t* __restrict__ counts) {
-  __shared__ float sb[AUG_MAX_BOXES][8];                       // cx cy cz dx dy dz cos(-rz) sin(-rz)
+  __shared__ float sb[AUG_MAX_BOXES][8];                       // aug_box_row
   __shared__ int32_t sc[AUG_MAX_BOXES];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int b0 = box_start[b], nb = aug_box_count(box_cnt, b);
   if (nb == 0) return;
   for (int k = tid; k < nb; k += AUG_THREADS) {
-    const float* bx = boxes + (int64_t)(b0 + k) * W;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) sb[k][c] = bx[c];
-    sb[k][6] = cosf(-bx[6]), sb[k][7] = sinf(-bx[6]);
+    aug_box_row(sb[k], boxes + (int64_t)(b0 + k) * W);
     sc[k] = 0;
   }
   __syncthreads();
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_scale_points(float* __restr
                                                                   const float* __restrict__ boxes_before, int W,
                                                                   const int32_t* __restrict__ box_start, const int32_t* __restrict__ box_cnt,
                                                                   const int32_t* __restrict__ box_cls, const double* __restrict__ plan) {
-  __shared__ float sb[AUG_MAX_BOXES][12];                      // cx cy cz dx dy dz cos(-r) sin(-r) cos(r) sin(r) scale grows
+  __shared__ float sb[AUG_MAX_BOXES][12];                      // aug_box_row, then cos(r) sin(r) scale grows
   __shared__ int32_t wave_sums[AUG_THREADS / SV_WAVE];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int b0 = box_start[b], nb = aug_box_count(box_cnt, b);
@@ -176,9 +166,8 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_scale_points(float* __restr
   if (scaled) {                                                // the scaled boxes, in box order
     const float* bx = boxes_before + (int64_t)(b0 + tid) * W;
     float* s = sb[slot];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) s[c] = bx[c];
-    s[6] = cosf(-bx[6]), s[7] = sinf(-bx[6]), s[8] = cosf(bx[6]), s[9] = sinf(bx[6]);
+    aug_box_row(s, bx);
+    s[8] = cosf(bx[6]), s[9] = sinf(bx[6]);
     s[10] = (float)plan[b0 + tid], s[11] = plan[b0 + tid] > 1.0 ? 1.f : 0.f;
   }
   __syncthreads();
@@ -229,7 +218,6 @@ extern "C" int sv_object_scale_points(float* points, int C, const int32_t* pt_st
 //   1 flip along x (param != 0: y, heading, vy negated)      2 flip along y (x, vx negated, heading = -(heading + pi))
 //   3 rotation by param (fp32 cos / sin of the fp32 angle)    4 scaling by param (fp32 products)
 //   5 / 6 / 7 translation along x / y / z (the offset is a float64 array there: the sum is made in fp64 and rounded)
-__device__ __forceinline__ int aug_op(int64_t ops, int t) { return (int)((ops >> (4 * t)) & 15); }
 __device__ __forceinline__ void aug_rotate(float& x, float& y, float c, float s) {
   const float nx = x * c + y * (-s), ny = x * s + y * c;
   x = nx, y = ny;
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_world_points(float* __restr
   float x = q[0], y = q[1], z = q[2];
   for (int t = 0; t < num_ops; ++t) {
     const double v = params[(int64_t)b * num_ops + t];
-    switch (aug_op(ops, t)) {
+    switch (aug_code(ops, t)) {
       case 1: if (v != 0.0) y = -y; break;
       case 2: if (v != 0.0) x = -x; break;
       case 3: aug_rotate(x, y, cosf((float)v), sinf((float)v)); break;
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_world_boxes(float* __restri
   float vx = vel ? q[7] : 0.f, vy = W > 8 ? q[8] : 0.f;
   for (int t = 0; t < num_ops; ++t) {
     const double v = params[(int64_t)b * num_ops + t];
-    switch (aug_op(ops, t)) {
+    switch (aug_code(ops, t)) {
       case 1: if (v != 0.0) y = -y, h = -h, vy = -vy; break;
       case 2: if (v != 0.0) x = -x, h = -(h + (float)M_PI), vx = -vx; break;
       case 3: {
@@ -568,7 +556,7 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_gt_remove(const float* __re
                                                                int32_t* __restrict__ keep, const float* __restrict__ db_boxes, int W,
                                                                const int32_t* __restrict__ cand_idx, const int32_t* __restrict__ cand_start,
                                                                const int32_t* __restrict__ accept, float ex, float ey, float ez) {
-  __shared__ float sb[AUG_MAX_BOXES][8];
+  __shared__ float sb[AUG_MAX_BOXES][8];                       // aug_box_row of the enlarged box
   __shared__ int32_t wave_sums[AUG_THREADS / SV_WAVE];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int c0 = cand_start[b], nc = min(cand_start[b + 1] - c0, AUG_MAX_BOXES);
@@ -576,10 +564,7 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_gt_remove(const float* __re
   int32_t n;
   const int32_t slot = sv_block_excl_scan<AUG_THREADS>((int32_t)mine, &n, wave_sums);
   if (mine) {
-    const float* bx = db_boxes + (int64_t)cand_idx[c0 + tid] * W;
-    float* s = sb[slot];
-    s[0] = bx[0], s[1] = bx[1], s[2] = bx[2], s[3] = bx[3] + ex, s[4] = bx[4] + ey, s[5] = bx[5] + ez;
-    s[6] = cosf(-bx[6]), s[7] = sinf(-bx[6]);
+    aug_box_row<true>(sb[slot], db_boxes + (int64_t)cand_idx[c0 + tid] * W, ex, ey, ez);
   }
   __syncthreads();
   const int i = head_rows[b] + blockIdx.x * AUG_THREADS + tid;

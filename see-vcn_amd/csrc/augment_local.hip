@@ -4,8 +4,8 @@
 // detector3d/pcdet/datasets/augmentor/augmentor_utils.py:257-320 (random_local_translation_along_x / _y / _z), :323-388
 // (global_frustum_dropout_*), :391-422 (local_scaling), :425-470 (local_rotation), :473-550 (local_frustum_dropout_*), :553-570 (get_points_in_box).
 //
-// The batch layout is augment.hip's: stacked point rows of C floats with keep flags, stacked box rows of W >= 7 floats with box_cls (-2: the row
-// does not exist), starts and counts on the device, at most 256 boxes per scene.
+// The batch layout is the one augment.h states: stacked point rows of C floats with keep flags, stacked box rows of W >= 7 floats with box_cls
+// (-2: the row does not exist), starts and counts on the device, at most 256 boxes per scene.
 //
 // Why two kernels.  A box's own state never depends on the points (translation adds to one centre coordinate, scaling multiplies the sizes,
 // rotation adds to the heading), so one thread per box can walk all the steps and write down, per (step, box), the box as that step's test sees
@@ -18,12 +18,11 @@
 // thresholds), rounded to float32 where it meets a float32 array.  No float atomics: equal bits run to run.
 #include <math.h>
 
+#include "augment.h"
 #include "common.h"
 #include "wave.h"
 
 namespace {
-constexpr int AUGL_MAX_BOXES = 256;
-constexpr int AUGL_THREADS = 256;                              // AUG_THREADS of augment.hip
 constexpr int AUGL_ROW = 12;                                   // floats per plan row
 constexpr double AUGL_MARGIN = 1e-1;                           // get_points_in_box's MARGIN (:559): x / y only
 
@@ -31,16 +30,6 @@ constexpr double AUGL_MARGIN = 1e-1;                           // get_points_in_
 enum { L_TX = 1, L_TY = 2, L_TZ = 3, L_ROT = 4, L_SCALE = 5, L_DROP_TOP = 6, L_DROP_BOTTOM = 7, L_DROP_LEFT = 8, L_DROP_RIGHT = 9 };
 // directions of the world frustum dropout
 enum { D_TOP = 1, D_BOTTOM = 2, D_LEFT = 3, D_RIGHT = 4 };
-
-__device__ __forceinline__ int augl_code(int64_t codes, int t) { return (int)((codes >> (4 * t)) & 15); }
-__device__ __forceinline__ int augl_box_count(const int32_t* __restrict__ box_cnt, int b) { return min(max(box_cnt[b], 0), AUGL_MAX_BOXES); }
-
-// a float's bits as an unsigned integer that orders as the float does (negative values inverted, the others with the sign bit set)
-__device__ __forceinline__ uint32_t augl_ordered(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float augl_unordered(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
 }  // namespace
 
 // ------------------------------------------------------------------ the plan: one thread per box row
@@ -48,12 +37,12 @@ __device__ __forceinline__ float augl_unordered(uint32_t e) { return __uint_as_f
 //   0-2 centre   3 / 4 float32(dx / 2.0 + 0.1), float32(dy / 2.0 + 0.1)   5 dz / 2   6 / 7 float32(cos(-rz)), float32(sin(-rz)) of the float64 math.cos / sin
 //   8-10 the parameter: translation float32(offset); rotation cosf / sinf of float32(angle); scaling float32(scale); dropout float32(threshold)
 //   11 skip != 0 (box_cls == -2)
-__global__ __launch_bounds__(AUGL_THREADS) void k_augl_plan(float* __restrict__ boxes, int W, const int32_t* __restrict__ box_start,
-                                                            const int32_t* __restrict__ box_cnt, const int32_t* __restrict__ box_cls,
-                                                            int total_boxes, int64_t steps, int num_steps, const double* __restrict__ draws,
-                                                            float* __restrict__ plan) {
+__global__ __launch_bounds__(AUG_THREADS) void k_augl_plan(float* __restrict__ boxes, int W, const int32_t* __restrict__ box_start,
+                                                           const int32_t* __restrict__ box_cnt, const int32_t* __restrict__ box_cls,
+                                                           int total_boxes, int64_t steps, int num_steps, const double* __restrict__ draws,
+                                                           float* __restrict__ plan) {
   const int b = blockIdx.x, k = threadIdx.x;
-  if (k >= augl_box_count(box_cnt, b)) return;
+  if (k >= aug_box_count(box_cnt, b)) return;
   const int64_t row = (int64_t)box_start[b] + k;
   if (row >= total_boxes) return;
   const bool skip = box_cls[row] < -1;
@@ -72,7 +61,7 @@ __global__ __launch_bounds__(AUGL_THREADS) void k_augl_plan(float* __restrict__ 
     o[3] = (float)((double)d[0] / 2.0 + AUGL_MARGIN), o[4] = (float)((double)d[1] / 2.0 + AUGL_MARGIN), o[5] = d[2] / 2.f;
     o[6] = (float)cos(-(double)h), o[7] = (float)sin(-(double)h);
     float p0 = 0.f, p1 = 0.f;
-    switch (augl_code(steps, t)) {
+    switch (aug_code(steps, t)) {
       case L_TX: p0 = (float)v, c[0] = (float)((double)c[0] + v); break;                        // :270-272
       case L_TY: p0 = (float)v, c[1] = (float)((double)c[1] + v); break;
       case L_TZ: p0 = (float)v, c[2] = (float)((double)c[2] + v); break;
@@ -97,13 +86,13 @@ extern "C" int sv_local_transform_plan(float* boxes, int W, const int32_t* box_s
                                        int total_boxes, int64_t steps, int num_steps, const double* draws, float* plan, void* stream) {
   SV_CHECK_ARG(batch >= 0 && total_boxes >= 0 && W >= 7 && num_steps >= 0 && num_steps <= 16, "local_transform_plan: bad arguments (at most 16 steps)");
   for (int t = 0; t < num_steps; ++t) {
-    const int code = (int)((steps >> (4 * t)) & 15);
+    const int code = aug_code(steps, t);
     SV_CHECK_ARG(code >= L_TX && code <= L_DROP_RIGHT, "local_transform_plan: unknown step code %d", code);
     SV_CHECK_ARG(!(code == L_ROT && W > 8), "local_transform_plan: local rotation of boxes wider than 8 columns");
   }
   if (batch == 0 || total_boxes == 0 || num_steps == 0) return SV_OK;
   SV_CHECK_ARG(boxes && box_start && box_cnt && box_cls && draws && plan, "local_transform_plan: null pointer");
-  hipLaunchKernelGGL(k_augl_plan, dim3(batch), dim3(AUGL_THREADS), 0, sv_stream(stream), boxes, W, box_start, box_cnt, box_cls, total_boxes, steps,
+  hipLaunchKernelGGL(k_augl_plan, dim3(batch), dim3(AUG_THREADS), 0, sv_stream(stream), boxes, W, box_start, box_cnt, box_cls, total_boxes, steps,
                      num_steps, draws, plan);
   SV_LAUNCH_CHECK();
   return SV_OK;
@@ -113,16 +102,16 @@ extern "C" int sv_local_transform_plan(float* boxes, int W, const int32_t* box_s
 // Per step the scene's plan rows (at most 256 x 12 floats = 12 KB) are staged through LDS; the whole plan of 16 steps would not fit and need not.
 // A dead point (keep == 0) is skipped, which equals the reference's removal: nothing a dead point does reaches a live one.  No coarse reject in
 // front of the test: the z comparison already comes first and is one subtraction.
-__global__ __launch_bounds__(AUGL_THREADS) void k_augl_points(float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
-                                                              const int32_t* __restrict__ pt_cnt, int32_t* __restrict__ keep,
-                                                              const int32_t* __restrict__ box_start, const int32_t* __restrict__ box_cnt,
-                                                              int total_boxes, int64_t steps, int num_steps, const float* __restrict__ plan) {
-  __shared__ float sb[AUGL_MAX_BOXES * AUGL_ROW];
+__global__ __launch_bounds__(AUG_THREADS) void k_augl_points(float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
+                                                             const int32_t* __restrict__ pt_cnt, int32_t* __restrict__ keep,
+                                                             const int32_t* __restrict__ box_start, const int32_t* __restrict__ box_cnt,
+                                                             int total_boxes, int64_t steps, int num_steps, const float* __restrict__ plan) {
+  __shared__ float sb[AUG_MAX_BOXES * AUGL_ROW];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int b0 = box_start[b];
-  const int nb = min(augl_box_count(box_cnt, b), max(total_boxes - b0, 0));
+  const int nb = min(aug_box_count(box_cnt, b), max(total_boxes - b0, 0));
   if (nb == 0) return;                                         // (uniform over the workgroup)
-  const int i = blockIdx.x * AUGL_THREADS + tid;
+  const int i = blockIdx.x * AUG_THREADS + tid;
   const int64_t p = (int64_t)pt_start[b] + i;
   bool alive = i < pt_cnt[b];
   if (alive) alive = keep[p] != 0;
@@ -133,9 +122,9 @@ __global__ __launch_bounds__(AUGL_THREADS) void k_augl_points(float* __restrict_
   for (int t = 0; t < num_steps; ++t) {
     const float* src = plan + ((int64_t)t * total_boxes + b0) * AUGL_ROW;
     __syncthreads();                                           // the last step's readers are done
-    for (int j = tid; j < nb * AUGL_ROW; j += AUGL_THREADS) sb[j] = src[j];
+    for (int j = tid; j < nb * AUGL_ROW; j += AUG_THREADS) sb[j] = src[j];
     __syncthreads();
-    const int op = augl_code(steps, t);
+    const int op = aug_code(steps, t);
     for (int k = 0; k < nb && alive; ++k) {
       const float* s = sb + k * AUGL_ROW;
       if (s[11] != 0.f) continue;
@@ -174,7 +163,7 @@ extern "C" int sv_local_transform_points(float* points, int C, const int32_t* pt
   if (batch == 0 || max_scene_points == 0 || total_boxes == 0 || num_steps == 0) return SV_OK;
   SV_CHECK_ARG(points && pt_start && pt_cnt && keep && box_start && box_cnt && plan && batch <= 65535,
                "local_transform_points: null pointer or batch > 65535");
-  hipLaunchKernelGGL(k_augl_points, dim3(sv_div_up(max_scene_points, AUGL_THREADS), batch), dim3(AUGL_THREADS), 0, sv_stream(stream), points, C,
+  hipLaunchKernelGGL(k_augl_points, dim3(sv_div_up(max_scene_points, AUG_THREADS), batch), dim3(AUG_THREADS), 0, sv_stream(stream), points, C,
                      pt_start, pt_cnt, keep, box_start, box_cnt, total_boxes, steps, num_steps, plan);
   SV_LAUNCH_CHECK();
   return SV_OK;
@@ -186,15 +175,15 @@ extern "C" int sv_local_transform_points(float* points, int C, const int32_t* pt
 // on the order.  The second forms the threshold as the reference does -- the float32 range times the Python float, in float64, rounded where it
 // meets the float32 columns -- and clears keep for the points and sets box_cls = -2 for the boxes whose coordinate fails the strict comparison.
 // A scene without live points keeps both words at 0xffffffff and passes through (np.max of an empty array raises in the reference).
-__global__ __launch_bounds__(AUGL_THREADS) void k_augl_minmax(const float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
-                                                              const int32_t* __restrict__ pt_cnt, const int32_t* __restrict__ keep, int col,
-                                                              uint32_t* __restrict__ minmax) {
-  const int b = blockIdx.y, i = blockIdx.x * AUGL_THREADS + threadIdx.x;
+__global__ __launch_bounds__(AUG_THREADS) void k_augl_minmax(const float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
+                                                             const int32_t* __restrict__ pt_cnt, const int32_t* __restrict__ keep, int col,
+                                                             uint32_t* __restrict__ minmax) {
+  const int b = blockIdx.y, i = blockIdx.x * AUG_THREADS + threadIdx.x;
   uint32_t lo = 0xffffffffu, hi = 0xffffffffu;
   if (i < pt_cnt[b]) {
     const int64_t p = (int64_t)pt_start[b] + i;
     if (keep[p]) {
-      const uint32_t e = augl_ordered(points[p * C + col]);
+      const uint32_t e = sv_ordered_f32(points[p * C + col]);
       lo = e, hi = ~e;
     }
   }
@@ -205,28 +194,28 @@ __global__ __launch_bounds__(AUGL_THREADS) void k_augl_minmax(const float* __res
   }
 }
 
-__global__ __launch_bounds__(AUGL_THREADS) void k_augl_world_drop(const float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
-                                                                  const int32_t* __restrict__ pt_cnt, int32_t* __restrict__ keep,
-                                                                  const float* __restrict__ boxes, int W, const int32_t* __restrict__ box_start,
-                                                                  const int32_t* __restrict__ box_cnt, int32_t* __restrict__ box_cls,
-                                                                  int total_boxes, int dir, const double* __restrict__ intensity, int num_dirs,
-                                                                  int which, const uint32_t* __restrict__ minmax) {
+__global__ __launch_bounds__(AUG_THREADS) void k_augl_world_drop(const float* __restrict__ points, int C, const int32_t* __restrict__ pt_start,
+                                                                 const int32_t* __restrict__ pt_cnt, int32_t* __restrict__ keep,
+                                                                 const float* __restrict__ boxes, int W, const int32_t* __restrict__ box_start,
+                                                                 const int32_t* __restrict__ box_cnt, int32_t* __restrict__ box_cls,
+                                                                 int total_boxes, int dir, const double* __restrict__ intensity, int num_dirs,
+                                                                 int which, const uint32_t* __restrict__ minmax) {
   const int b = blockIdx.y, tid = threadIdx.x;
   const uint32_t elo = minmax[2 * b], ehi = minmax[2 * b + 1];
   if (elo == 0xffffffffu && ehi == 0xffffffffu) return;        // no live point
-  const float mn = augl_unordered(elo), mx = augl_unordered(~ehi);
+  const float mn = sv_unordered_f32(elo), mx = sv_unordered_f32(~ehi);
   const double v = intensity[(int64_t)b * num_dirs + which];
   const double span = (double)(mx - mn);                       // float32 scalar - float32 scalar
   const bool upper = dir == D_TOP || dir == D_LEFT;
   const float thr = (float)(upper ? (double)mx - v * span : (double)mn + v * span);
   const int col = (dir == D_TOP || dir == D_BOTTOM) ? 2 : 1;
-  const int i = blockIdx.x * AUGL_THREADS + tid;
+  const int i = blockIdx.x * AUG_THREADS + tid;
   if (i < pt_cnt[b]) {
     const int64_t p = (int64_t)pt_start[b] + i;
     const float c = points[p * C + col];
     if (keep[p] && !(upper ? c < thr : c > thr)) keep[p] = 0;
   }
-  if (blockIdx.x == 0 && tid < augl_box_count(box_cnt, b)) {   // the scene's boxes: at most one workgroup's worth
+  if (blockIdx.x == 0 && tid < aug_box_count(box_cnt, b)) {   // the scene's boxes: at most one workgroup's worth
     const int64_t row = (int64_t)box_start[b] + tid;
     if (row < total_boxes && box_cls[row] >= -1) {
       const float c = boxes[row * W + col];
@@ -247,7 +236,7 @@ extern "C" int sv_world_frustum_dropout(const float* points, int C, const int32_
   SV_CHECK_ARG(batch >= 0 && max_scene_points >= 0 && total_boxes >= 0 && C >= 3 && W >= 7 && num_dirs >= 0 && num_dirs <= 16,
                "world_frustum_dropout: bad arguments (at most 16 directions)");
   for (int t = 0; t < num_dirs; ++t) {
-    const int dir = (int)((dirs >> (4 * t)) & 15);
+    const int dir = aug_code(dirs, t);
     SV_CHECK_ARG(dir >= D_TOP && dir <= D_RIGHT, "world_frustum_dropout: unknown direction code %d", dir);
   }
   if (batch == 0 || max_scene_points == 0 || num_dirs == 0) return SV_OK;
@@ -256,12 +245,12 @@ extern "C" int sv_world_frustum_dropout(const float* points, int C, const int32_
   hipStream_t st = sv_stream(stream);
   uint32_t* minmax = reinterpret_cast<uint32_t*>(scratch);
   SV_HIP(hipMemsetAsync(minmax, 0xff, sv_world_frustum_dropout_scratch_bytes(batch, num_dirs), st));
-  const dim3 grid(sv_div_up(max_scene_points, AUGL_THREADS), batch);
+  const dim3 grid(sv_div_up(max_scene_points, AUG_THREADS), batch);
   for (int t = 0; t < num_dirs; ++t) {
-    const int dir = (int)((dirs >> (4 * t)) & 15);
+    const int dir = aug_code(dirs, t);
     uint32_t* mm = minmax + (size_t)t * batch * 2;
-    hipLaunchKernelGGL(k_augl_minmax, grid, dim3(AUGL_THREADS), 0, st, points, C, pt_start, pt_cnt, keep, (dir == D_TOP || dir == D_BOTTOM) ? 2 : 1, mm);
-    hipLaunchKernelGGL(k_augl_world_drop, grid, dim3(AUGL_THREADS), 0, st, points, C, pt_start, pt_cnt, keep, boxes, W, box_start, box_cnt, box_cls,
+    hipLaunchKernelGGL(k_augl_minmax, grid, dim3(AUG_THREADS), 0, st, points, C, pt_start, pt_cnt, keep, (dir == D_TOP || dir == D_BOTTOM) ? 2 : 1, mm);
+    hipLaunchKernelGGL(k_augl_world_drop, grid, dim3(AUG_THREADS), 0, st, points, C, pt_start, pt_cnt, keep, boxes, W, box_start, box_cnt, box_cls,
                        total_boxes, dir, intensity, num_dirs, t, mm);
   }
   SV_LAUNCH_CHECK();

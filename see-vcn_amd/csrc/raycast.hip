@@ -35,11 +35,6 @@ __device__ __forceinline__ RcV3 rc_cross(RcV3 a, RcV3 b) { return {a.y * b.z - a
 __device__ __forceinline__ float rc_dot(RcV3 a, RcV3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // ------------------------------------------------------------------ build, part 1: bounds of the centroids and the sort keys
-__device__ __forceinline__ unsigned rc_ordered(float f) {      // monotone float -> unsigned
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rc_unordered(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 __device__ __forceinline__ RcV3 rc_centroid(const float* __restrict__ t) {
   return {((t[0] + t[3]) + t[6]) / 3.f, ((t[1] + t[4]) + t[7]) / 3.f, ((t[2] + t[5]) + t[8]) / 3.f};
 }
@@ -56,7 +51,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_bounds(const float* __restric
     for (int k = 0; k < 9; ++k) bad |= !isfinite(t[k]);
     if (!bad) {
       const RcV3 c = rc_centroid(t);
-      lo[0] = hi[0] = rc_ordered(c.x), lo[1] = hi[1] = rc_ordered(c.y), lo[2] = hi[2] = rc_ordered(c.z);
+      lo[0] = hi[0] = sv_ordered_f32(c.x), lo[1] = hi[1] = sv_ordered_f32(c.y), lo[2] = hi[2] = sv_ordered_f32(c.z);
     }
   }
 #pragma unroll
@@ -92,9 +87,9 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_keys(const float* __restrict_
   const int64_t i = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x;
   if (i >= T) return;
   const RcV3 c = rc_centroid(tris + i * 9);
-  const unsigned m = (rc_spread10(rc_cell(c.x, rc_unordered(bounds[0]), rc_unordered(bounds[3]))) << 2) |
-                     (rc_spread10(rc_cell(c.y, rc_unordered(bounds[1]), rc_unordered(bounds[4]))) << 1) |
-                     rc_spread10(rc_cell(c.z, rc_unordered(bounds[2]), rc_unordered(bounds[5])));
+  const unsigned m = (rc_spread10(rc_cell(c.x, sv_unordered_f32(bounds[0]), sv_unordered_f32(bounds[3]))) << 2) |
+                     (rc_spread10(rc_cell(c.y, sv_unordered_f32(bounds[1]), sv_unordered_f32(bounds[4]))) << 1) |
+                     rc_spread10(rc_cell(c.z, sv_unordered_f32(bounds[2]), sv_unordered_f32(bounds[5])));
   keys[i] = ((int64_t)m << 32) | i;
 }
 
@@ -452,17 +447,8 @@ __global__ __launch_bounds__(1024) void k_rc_scan_chunks(const int32_t* __restri
   __shared__ int32_t wave_sums[1024 / SV_WAVE];
   __shared__ int32_t totals[2];
   for (int which = 0; which < 2; ++which) {
-    int32_t carry = 0;
-    for (int64_t base = 0; base < n; base += 1024) {           // every thread of the workgroup takes every round
-      const int64_t k = base + threadIdx.x;
-      const int32_t v = k < n ? chunk_cnt[which * n + k] : 0;
-      int32_t total;
-      const int32_t ex = sv_block_excl_scan<1024>(v, &total, wave_sums);
-      if (k < n) chunk_off[which * n + k] = carry + ex;
-      carry += total;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[which] = carry;
+    const int32_t total = sv_block_excl_scan_array<1024>(chunk_cnt + which * n, chunk_off + which * n, n, wave_sums);
+    if (threadIdx.x == 0) totals[which] = total;
   }
   __syncthreads();
   for (int k = threadIdx.x; k < 2 * C; k += 1024) {

@@ -329,29 +329,11 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_count(HardVoxArgs a) {
 
 // one workgroup per scene: exclusive scan of the block counts in place, number of open voxels
 __global__ __launch_bounds__(1024) void k_hv_offsets(HardVoxArgs a) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ int32_t wsum[1024 / SV_WAVE];
+  const int b = blockIdx.x;
   int32_t* off = a.block_off + (int64_t)b * a.blocks_per_scene;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < a.blocks_per_scene; base += 1024) {
-    const int j = base + tid;
-    const int v = j < a.blocks_per_scene ? off[j] : 0;
-    const int incl = sv_wave_incl_scan(v);
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    int pre = carry, tot = 0;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wid) pre += wsum[w];
-      tot += wsum[w];
-    }
-    if (j < a.blocks_per_scene) off[j] = pre + incl - v;
-    __syncthreads();
-    if (tid == 0) carry += tot;
-    __syncthreads();
-  }
-  if (tid == 0) a.num_voxels[b] = min(carry, a.max_voxels);
+  const int32_t total = sv_block_excl_scan_array<1024>(off, off, a.blocks_per_scene, wsum);
+  if (threadIdx.x == 0) a.num_voxels[b] = min(total, a.max_voxels);
 }
 
 __global__ __launch_bounds__(HV_THREADS) void k_hv_fill(HardVoxArgs a) {

@@ -11,32 +11,15 @@ import numpy as np
 import torch
 
 from .... import _lib as L
+from .... import data_pipeline as P
 
 # library calls and blocking device -> host reads since the last reset_counters(); neither depends on the batch size or the number of boxes
-COUNTERS = {"library_calls": 0, "host_reads": 0}
+_counted = P.Counted()
+COUNTERS, reset_counters, call, read = _counted.counters, _counted.reset, _counted.call, _counted.read
 
 MAX_BOXES_PER_SCENE = 256
 MAX_NUM_TRY = 64
-OPS = {"flip_x": 1, "flip_y": 2, "rotation": 3, "scaling": 4, "translation_x": 5, "translation_y": 6, "translation_z": 7}
-
-_ws = L.Workspace()
-
-
-def reset_counters():
-    COUNTERS["library_calls"] = 0
-    COUNTERS["host_reads"] = 0
-
-
-def call(name, *args):
-    """One call into the library through the binding layer, counted."""
-    COUNTERS["library_calls"] += 1
-    L.check(getattr(L.load(), name)(*args), name)
-
-
-def read(t):
-    """One blocking device -> host read, counted."""
-    COUNTERS["host_reads"] += 1
-    return t.cpu().numpy()
+OPS, LOCAL_STEPS, WORLD_DROPOUT = P.codes_of("world"), P.codes_of("local"), P.codes_of("drop")   # views of data_pipeline.OP_CODES
 
 
 class DeviceBatch:
@@ -147,9 +130,7 @@ def world_transform(batch, ops, params, limit_heading=False):
     the boxes, whatever the number of ops; limit_heading adds limit_period(heading, 0.5, 2 pi) (data_augmentor.py:258-260)."""
     if len(ops) > 16:
         raise ValueError("at most 16 world transforms in one call")
-    code = 0
-    for i, name in enumerate(ops):
-        code |= OPS[name] << (4 * i)
+    code = P.pack_codes(ops, "world")
     dev = batch.points.device
     p = _device_f64(np.zeros((batch.batch_size, 1)) if len(ops) == 0 else params, dev)
     assert len(ops) == 0 or tuple(p.shape) == (batch.batch_size, len(ops))
@@ -200,9 +181,6 @@ def random_translation_along_z(batch, offset):
 
 
 # ------------------------------------------------------------------ local and frustum augmentors (csrc/augment_local.hip)
-LOCAL_STEPS = {"local_translation_x": 1, "local_translation_y": 2, "local_translation_z": 3, "local_rotation": 4, "local_scaling": 5,
-               "local_dropout_top": 6, "local_dropout_bottom": 7, "local_dropout_left": 8, "local_dropout_right": 9}
-WORLD_DROPOUT = {"world_dropout_top": 1, "world_dropout_bottom": 2, "world_dropout_left": 3, "world_dropout_right": 4}
 PLAN_ROW = 12
 
 
@@ -220,9 +198,7 @@ def local_transform(batch, steps, params):
     assert tuple(p.shape) == (N, len(steps))
     for first in range(0, len(steps), 16):
         run = steps[first:first + 16]
-        code = 0
-        for i, name in enumerate(run):
-            code |= LOCAL_STEPS[name] << (4 * i)
+        code = P.pack_codes(run, "local")
         draws = p if len(run) == len(steps) else p[:, first:first + 16].contiguous()
         plan = torch.empty(len(run) * N * PLAN_ROW, dtype=torch.float32, device=dev)
         call("sv_local_transform_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, N, code, len(run), L.ptr(draws), L.ptr(plan),
@@ -288,13 +264,11 @@ def world_frustum_dropout(batch, directions, intensity):
         raise ValueError("at most 16 directions in one call")
     if len(directions) == 0:
         return
-    code = 0
-    for i, name in enumerate(directions):
-        code |= WORLD_DROPOUT[name] << (4 * i)
+    code = P.pack_codes(directions, "drop")
     dev, B = batch.points.device, batch.batch_size
     v = _device_f64(intensity, dev)
     assert tuple(v.shape) == (B, len(directions))
-    scratch = _ws.scratch("world_frustum_dropout", max(int(L.load().sv_world_frustum_dropout_scratch_bytes(B, len(directions))), 4), dev)
+    scratch = L.workspace.scratch("world_frustum_dropout", max(int(L.load().sv_world_frustum_dropout_scratch_bytes(B, len(directions))), 4), dev)
     call("sv_world_frustum_dropout", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
          batch.total_boxes, code, len(directions), L.ptr(v), L.ptr(scratch), L.stream())
 
@@ -327,7 +301,7 @@ def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
     gt_stride = batch.max_scene_boxes
     gt = torch.empty(B, max(gt_stride, 1), W + 1, dtype=torch.float32, device=dev)
     box_keep = torch.zeros(max(batch.total_boxes, 1), dtype=torch.int32, device=dev)
-    scratch = _ws.scratch("augment_compact", max(int(L.load().sv_augment_compact_scratch_bytes(B, batch.max_scene_points)), 4), dev)
+    scratch = L.workspace.scratch("augment_compact", max(int(L.load().sv_augment_compact_scratch_bytes(B, batch.max_scene_points)), 4), dev)
     pr = None if point_range is None else L.host_array(ctypes.c_double, [float(point_range[i]) for i in (0, 1, 3, 4)])
     br = None if not min_num_corners else L.host_array(ctypes.c_double, [float(v) for v in list(box_range)[:6]])
     call("sv_augment_compact", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, pr, *batch._box_args(), L.ptr(batch.box_cls), br,

@@ -13,21 +13,132 @@ boundary, runs the device work, reads the class codes back (one host read per bo
 import numpy as np
 import torch
 
+from .... import data_pipeline as P
 from ...utils.common_utils import cfg_get
 from . import augmentor_utils as A
 from . import database_sampler
 
 NUM_TRY = 50                                                     # scale_pre_object's default (augmentor_utils.py:10)
-
-BUILT = ("gt_sampling", "random_object_scaling", "random_world_flip", "random_world_rotation", "random_world_scaling", "random_world_translation",
-         "random_local_rotation", "random_local_scaling", "random_local_translation", "random_world_frustum_dropout",
-         "random_local_frustum_dropout")
-BOUNDARY = ("gt_sampling", "random_world_frustum_dropout")       # they change the number of boxes on the device
 DIRECTIONS = ("top", "bottom", "left", "right")
-# the keys the local / frustum entries are read by (data_augmentor.py:134-219); the reference has no default for any of them
-REQUIRED = {"random_local_rotation": ("LOCAL_ROT_ANGLE",), "random_local_scaling": ("LOCAL_SCALE_RANGE",),
-            "random_local_translation": ("LOCAL_TRANSLATION_RANGE", "ALONG_AXIS_LIST"),
-            "random_world_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION"), "random_local_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION")}
+
+
+# ---------------------------------------------------------------------------------------------------------- the augmentor table
+# One generator per config NAME: given the entry it yields the entry's draws in order as (draw name, per box, draw(rng, n, sampler, gt_names)), n
+# being the boxes the scene holds at that point (only gt_sampling looks at the sampler and the names).  The config is read once, when the
+# generator runs; the draw functions are then called scene after scene.  The calls are the reference's, per scene in queue order:
+#   gt_sampling               permutation(len(db_infos[class])) whenever a group's pointer has wrapped    database_sampler.py:132-134
+#   random_object_scaling     uniform(lo, hi, size=[N, 50])                                    augmentor_utils.py:26
+#   random_world_flip         choice([False, True], replace=False, p=[.5, .5]) per axis         :89, :109
+#   random_world_rotation     uniform(lo, hi)                                                   :130
+#   random_world_scaling      uniform(lo, hi), nothing when hi - lo < 1e-3                      :153-155
+#   random_world_translation  normal(0, std, 1) per axis, nothing at all when std == 0          data_augmentor.py:120-122, :211
+#   random_local_translation  uniform(lo, hi) per axis, per box                                 augmentor_utils.py:267, :290, :313
+#   random_local_rotation     uniform(lo, hi) per box                                           :435
+#   random_local_scaling      uniform(lo, hi) per box, nothing at all when hi - lo < 1e-3       :399-404
+#   random_world_frustum_dropout   uniform(lo, hi) per direction                                :331, :348, :365, :382
+#   random_local_frustum_dropout   uniform(lo, hi) per direction, per box                       :484, :504, :524, :544
+def _per_box(lo, hi):
+    """One Python-float draw per box, as the reference's loop over the boxes makes them."""
+    return lambda rng, n, *scene: np.array([rng.uniform(lo, hi) for _ in range(int(n))], np.float64)
+
+
+def _symmetric(r):
+    return list(r) if isinstance(r, (list, tuple)) else [-r, r]
+
+
+def _gt_sampling(cur):
+    yield "gt_sampling", False, lambda rng, n, sampler, gt_names: sampler.draw(gt_names, rng)
+
+
+def _object_scaling(cur):
+    s = cfg_get(cur, "SCALE_UNIFORM_NOISE")
+    s = list(s) if isinstance(s, (list, tuple, np.ndarray)) else [-s, s]
+    yield "object_scaling", True, lambda rng, n, *scene: rng.uniform(s[0], s[1], size=[int(n), NUM_TRY])
+
+
+def _world_flip(cur):
+    for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
+        assert axis in ("x", "y")
+        yield "flip_" + axis, False, lambda rng, n, *scene: bool(rng.choice([False, True], replace=False, p=[0.5, 0.5]))
+
+
+def _world_rotation(cur):
+    r = _symmetric(cfg_get(cur, "WORLD_ROT_ANGLE"))
+    yield "rotation", False, lambda rng, n, *scene: rng.uniform(r[0], r[1])
+
+
+def _world_scaling(cur):
+    r = cfg_get(cur, "WORLD_SCALE_RANGE")
+    if not r[1] - r[0] < 1e-3:
+        yield "scaling", False, lambda rng, n, *scene: rng.uniform(r[0], r[1])
+
+
+def _world_translation(cur):
+    std = cfg_get(cur, "NOISE_TRANSLATE_STD")
+    if std == 0:
+        return
+    for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
+        assert axis in ("x", "y", "z")
+        yield "translation_" + axis, False, lambda rng, n, *scene: float(rng.normal(0, std, 1)[0])
+
+
+def _local_translation(cur):
+    r = cfg_get(cur, "LOCAL_TRANSLATION_RANGE")
+    for axis in cfg_get(cur, "ALONG_AXIS_LIST"):                 # every axis is a whole pass over the boxes
+        assert axis in ("x", "y", "z")
+        yield "local_translation_" + axis, True, _per_box(r[0], r[1])
+
+
+def _local_rotation(cur):
+    r = _symmetric(cfg_get(cur, "LOCAL_ROT_ANGLE"))
+    yield "local_rotation", True, _per_box(r[0], r[1])
+
+
+def _local_scaling(cur):
+    r = cfg_get(cur, "LOCAL_SCALE_RANGE")
+    if not r[1] - r[0] < 1e-3:
+        yield "local_scaling", True, _per_box(r[0], r[1])
+
+
+def _frustum_dropout(prefix, per_box):
+    def draws(cur):
+        r = cfg_get(cur, "INTENSITY_RANGE")
+        for d in cfg_get(cur, "DIRECTION"):
+            assert d in DIRECTIONS
+            yield prefix + d, per_box, _per_box(r[0], r[1]) if per_box else (lambda rng, n, *scene: rng.uniform(r[0], r[1]))
+    return draws
+
+
+# NAME -> (the keys the entry is read by and the reference has no default for (data_augmentor.py:134-219), whether it changes the number of boxes
+# on the device, its draws)
+AUGMENTORS = {
+    "gt_sampling": ((), True, _gt_sampling),
+    "random_object_scaling": ((), False, _object_scaling),
+    "random_world_flip": ((), False, _world_flip),
+    "random_world_rotation": ((), False, _world_rotation),
+    "random_world_scaling": ((), False, _world_scaling),
+    "random_world_translation": ((), False, _world_translation),
+    "random_local_rotation": (("LOCAL_ROT_ANGLE",), False, _local_rotation),
+    "random_local_scaling": (("LOCAL_SCALE_RANGE",), False, _local_scaling),
+    "random_local_translation": (("LOCAL_TRANSLATION_RANGE", "ALONG_AXIS_LIST"), False, _local_translation),
+    "random_world_frustum_dropout": (("INTENSITY_RANGE", "DIRECTION"), True, _frustum_dropout("world_dropout_", False)),
+    "random_local_frustum_dropout": (("INTENSITY_RANGE", "DIRECTION"), False, _frustum_dropout("local_dropout_", True)),
+}
+
+
+def _draws(cur):
+    """The draws of one queue entry: (draw name, per box, draw) in order."""
+    return AUGMENTORS[cfg_get(cur, "NAME")][2](cur)
+
+
+def _plan(entries):
+    """The draws of a run of queue entries, read from the config once for all scenes: [(draw name, draw), ...] in order."""
+    return [(name, draw) for cur in entries for name, _, draw in _draws(cur)]
+
+
+def _draw(plan, rng, n, sampler=None, gt_names=None):
+    """One scene's draws: [(name, value), ...] in draw order; n: the boxes the scene holds at that point."""
+    return [(name, draw(rng, n, sampler, gt_names)) for name, draw in plan]
 
 
 def _queue(augmentor_configs):
@@ -40,9 +151,9 @@ def _queue(augmentor_configs):
         name = cfg_get(cur, "NAME")
         if name in disabled:
             continue
-        if name not in BUILT:
+        if name not in AUGMENTORS:
             raise NotImplementedError(name)
-        for key in REQUIRED.get(name, ()):
+        for key in AUGMENTORS[name][0]:
             if cfg_get(cur, key) is None:                        # refused when the queue is built, not at the first draw
                 raise NotImplementedError(f"{name} without {key}")
         if name == "random_object_scaling" and any(cfg_get(q, "NAME") == "gt_sampling" for q in queue):
@@ -57,11 +168,7 @@ def _queue(augmentor_configs):
 
 def _draws_per_box(cur):
     """Whether the entry makes a draw per box of the scene."""
-    name = cfg_get(cur, "NAME")
-    if name == "random_local_scaling":
-        r = cfg_get(cur, "LOCAL_SCALE_RANGE")
-        return not r[1] - r[0] < 1e-3
-    return name in ("random_object_scaling", "random_local_rotation", "random_local_translation", "random_local_frustum_dropout")
+    return any(per_box for _, per_box, _ in _draws(cur))
 
 
 def _stages(queue):
@@ -72,7 +179,7 @@ def _stages(queue):
             # its draw needs the names of the boxes that are left, which only the device knows by then
             raise NotImplementedError("gt_sampling behind a per-box draw that follows random_world_frustum_dropout")
         cur.append(q)
-        if cfg_get(q, "NAME") in BOUNDARY and any(_draws_per_box(r) for r in queue[i + 1:]):
+        if AUGMENTORS[cfg_get(q, "NAME")][1] and any(_draws_per_box(r) for r in queue[i + 1:]):
             stages.append(cur)
             cur = []
     return stages + [cur]
@@ -80,119 +187,26 @@ def _stages(queue):
 
 def _entry_names(cur):
     """The names of the draws one queue entry makes, in order (fixed by the config)."""
-    name = cfg_get(cur, "NAME")
-    if name == "gt_sampling":
-        return ["gt_sampling"]
-    if name == "random_object_scaling":
-        return ["object_scaling"]
-    if name == "random_world_flip":
-        return ["flip_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
-    if name == "random_world_rotation":
-        return ["rotation"]
-    if name == "random_world_scaling":
-        r = cfg_get(cur, "WORLD_SCALE_RANGE")
-        return [] if r[1] - r[0] < 1e-3 else ["scaling"]
-    if name == "random_world_translation":
-        return [] if cfg_get(cur, "NOISE_TRANSLATE_STD") == 0 else ["translation_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
-    if name == "random_local_translation":
-        return ["local_translation_" + a for a in cfg_get(cur, "ALONG_AXIS_LIST")]
-    if name == "random_local_rotation":
-        return ["local_rotation"]
-    if name == "random_local_scaling":
-        return ["local_scaling"] if _draws_per_box(cur) else []
-    if name == "random_world_frustum_dropout":
-        return ["world_dropout_" + d for d in cfg_get(cur, "DIRECTION")]
-    if name == "random_local_frustum_dropout":
-        return ["local_dropout_" + d for d in cfg_get(cur, "DIRECTION")]
-    raise NotImplementedError(name)
+    return [name for name, _, _ in _draws(cur)]
 
 
 def _draw_scene(rng, entries, n, sampler=None, gt_names=None):
     """One scene's draws for a run of queue entries: [(name, value), ...] in draw order; n: the boxes the scene holds at that point."""
-    draws = []
-
-    def per_box(lo, hi):
-        return np.array([rng.uniform(lo, hi) for _ in range(int(n))], np.float64)   # one Python-float draw per box, as the reference's loop makes them
-
-    for cur in entries:
-        name = cfg_get(cur, "NAME")
-        if name == "gt_sampling":
-            draws.append(("gt_sampling", sampler.draw(gt_names, rng)))
-        elif name == "random_object_scaling":
-            s = cfg_get(cur, "SCALE_UNIFORM_NOISE")
-            s = list(s) if isinstance(s, (list, tuple, np.ndarray)) else [-s, s]
-            draws.append(("object_scaling", rng.uniform(s[0], s[1], size=[int(n), NUM_TRY])))
-        elif name == "random_world_flip":
-            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
-                assert axis in ("x", "y")
-                draws.append(("flip_" + axis, bool(rng.choice([False, True], replace=False, p=[0.5, 0.5]))))
-        elif name == "random_world_rotation":
-            r = cfg_get(cur, "WORLD_ROT_ANGLE")
-            r = list(r) if isinstance(r, (list, tuple)) else [-r, r]
-            draws.append(("rotation", rng.uniform(r[0], r[1])))
-        elif name == "random_world_scaling":
-            r = cfg_get(cur, "WORLD_SCALE_RANGE")
-            if not r[1] - r[0] < 1e-3:
-                draws.append(("scaling", rng.uniform(r[0], r[1])))
-        elif name == "random_world_translation":
-            std = cfg_get(cur, "NOISE_TRANSLATE_STD")
-            if std == 0:
-                continue
-            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):
-                assert axis in ("x", "y", "z")
-                draws.append(("translation_" + axis, float(rng.normal(0, std, 1)[0])))
-        elif name == "random_local_translation":
-            r = cfg_get(cur, "LOCAL_TRANSLATION_RANGE")
-            for axis in cfg_get(cur, "ALONG_AXIS_LIST"):           # every axis is a whole pass over the boxes
-                assert axis in ("x", "y", "z")
-                draws.append(("local_translation_" + axis, per_box(r[0], r[1])))
-        elif name == "random_local_rotation":
-            r = cfg_get(cur, "LOCAL_ROT_ANGLE")
-            r = list(r) if isinstance(r, (list, tuple)) else [-r, r]
-            draws.append(("local_rotation", per_box(r[0], r[1])))
-        elif name == "random_local_scaling":
-            r = cfg_get(cur, "LOCAL_SCALE_RANGE")
-            if not r[1] - r[0] < 1e-3:
-                draws.append(("local_scaling", per_box(r[0], r[1])))
-        elif name == "random_world_frustum_dropout":
-            r = cfg_get(cur, "INTENSITY_RANGE")
-            for d in cfg_get(cur, "DIRECTION"):
-                assert d in DIRECTIONS
-                draws.append(("world_dropout_" + d, rng.uniform(r[0], r[1])))
-        elif name == "random_local_frustum_dropout":
-            r = cfg_get(cur, "INTENSITY_RANGE")
-            for d in cfg_get(cur, "DIRECTION"):
-                assert d in DIRECTIONS
-                draws.append(("local_dropout_" + d, per_box(r[0], r[1])))
-    return draws
+    return _draw(_plan(entries), rng, n, sampler, gt_names)
 
 
 def draw_params(rng, augmentor_configs, num_boxes, sampler=None, gt_names=None):
     """Every draw of one batch: rng is a numpy.random.RandomState, num_boxes[b] the boxes that enter scene b's augmentation (after
     MIN_POINTS_OF_GT) and, for gt_sampling, gt_names[b] their names and sampler the DataBaseSampler.  Scene by scene, per scene in queue order, with
-    the reference's calls:
-      gt_sampling               permutation(len(db_infos[class])) whenever a group's pointer has wrapped    database_sampler.py:132-134
-      random_object_scaling     uniform(lo, hi, size=[N, 50])                                    augmentor_utils.py:26
-      random_world_flip         choice([False, True], replace=False, p=[.5, .5]) per axis         :89, :109
-      random_world_rotation     uniform(lo, hi)                                                   :130
-      random_world_scaling      uniform(lo, hi), nothing when hi - lo < 1e-3                      :153-155
-      random_world_translation  normal(0, std, 1) per axis, nothing at all when std == 0          data_augmentor.py:120-122, :211
-      random_local_translation  uniform(lo, hi) per axis, per box                                 augmentor_utils.py:267, :290, :313
-      random_local_rotation     uniform(lo, hi) per box                                           :435
-      random_local_scaling      uniform(lo, hi) per box, nothing at all when hi - lo < 1e-3       :399-404
-      random_world_frustum_dropout   uniform(lo, hi) per direction                                :331, :348, :365, :382
-      random_local_frustum_dropout   uniform(lo, hi) per direction, per box                       :484, :504, :524, :544
+    the reference's calls (the table above AUGMENTORS lists them with their lines).
     Returns one list per scene of (name, value) in draw order; ops without a draw are left out; a per-box draw is an (n,) float64 array.
     A queue in which a per-box draw follows gt_sampling or random_world_frustum_dropout cannot be drawn ahead: ValueError (see forward)."""
     queue = _queue(augmentor_configs)
     if len(_stages(queue)) > 1:
         raise ValueError("a per-box draw follows gt_sampling or random_world_frustum_dropout: the number of boxes it is sized by is decided on the "
                          "device, so one shared stream cannot be replayed; give forward() one RandomState per scene")
-    return [_draw_scene(rng, queue, n, sampler, None if gt_names is None else gt_names[b]) for b, n in enumerate(num_boxes)]
-
-
-def _kind(name):
-    return "world" if name in A.OPS else "local" if name in A.LOCAL_STEPS else "drop" if name in A.WORLD_DROPOUT else name
+    plan = _plan(queue)
+    return [_draw(plan, rng, n, sampler, None if gt_names is None else gt_names[b]) for b, n in enumerate(num_boxes)]
 
 
 class BatchDataAugmentor:
@@ -230,13 +244,13 @@ class BatchDataAugmentor:
         B, N, dev = batch.batch_size, batch.total_boxes, batch.points.device
         names = [name for name, _ in draws[0]]
         assert all([name for name, _ in d] == names for d in draws), "every scene makes the same draws"
-        count = {k: sum(_kind(n) == k for n in names) for k in ("world", "local", "drop")}
+        count = {k: sum(P.op_kind(n) == k for n in names) for k in ("world", "local", "drop")}
         noises = np.zeros((max(N, 1) if "object_scaling" in names else 0, NUM_TRY))
         world, local, drop = np.zeros((B, count["world"])), np.zeros((N, count["local"])), np.zeros((B, count["drop"]))
         for b, d in enumerate(draws):
             col = {"world": 0, "local": 0, "drop": 0}
             for name, value in d:
-                k = _kind(name)
+                k = P.op_kind(name)
                 if name == "object_scaling":
                     assert np.shape(value) == (len(rows[b]), NUM_TRY)
                     noises[rows[b]] = value                      # row i of the draw belongs to the i-th box that exists
@@ -264,7 +278,7 @@ class BatchDataAugmentor:
         done = {"world": 0, "local": 0, "drop": 0}
         pending, kind = [], None
         for name in names + [None]:
-            k = None if name is None else _kind(name)
+            k = None if name is None else P.op_kind(name)
             if k in done and (k == kind or not pending):
                 pending.append(name)
                 kind = k
@@ -329,7 +343,8 @@ class BatchDataAugmentor:
                     taken[b] += n
                 return out
             if per_scene:
-                return [_draw_scene(rng[b], entries, num_boxes[b], self.db_sampler, names[b]) for b in range(B)]
+                plan = _plan(entries)
+                return [_draw(plan, rng[b], num_boxes[b], self.db_sampler, names[b]) for b in range(B)]
             return draw_params(rng if rng is not None else np.random, self.augmentor_configs, num_boxes, self.db_sampler, names)
 
         first = stage_draws(stages[0]) if len(stages) > 1 or given is None else [list(d) for d in given]

@@ -8,26 +8,11 @@ import numpy as np
 import torch
 
 from ..... import _lib as L
+from ..... import data_pipeline as P
 
 # library calls and blocking device -> host reads made by this package since the last reset_counters(); neither depends on the number of frames
-COUNTERS = {"library_calls": 0, "host_reads": 0}
-
-
-def reset_counters():
-    COUNTERS["library_calls"] = 0
-    COUNTERS["host_reads"] = 0
-
-
-def call(name, *args):
-    """One call into the library through the binding layer, counted."""
-    COUNTERS["library_calls"] += 1
-    L.check(getattr(L.load(), name)(*args), name)
-
-
-def read(t):
-    """One blocking device -> host read, counted."""
-    COUNTERS["host_reads"] += 1
-    return t.cpu().numpy()
+_counted = P.Counted()
+COUNTERS, reset_counters, call, read = _counted.counters, _counted.reset, _counted.call, _counted.read
 
 
 def device(device_id=0):

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ... import data_pipeline as P
 from ..utils.transform import rotate_points_along_z
 
 
@@ -27,28 +28,12 @@ class ResamplePoints(object):
 
 
 # library calls and blocking device -> host reads since the last reset_counters(); neither depends on the batch size
-COUNTERS = {"library_calls": 0, "host_reads": 0}
+_counted = P.Counted()
+COUNTERS, reset_counters, call, read = _counted.counters, _counted.reset, _counted.call, _counted.read
 
 MAX_RINGS = 1024                      # SV_VC_MAX_RINGS
 MAX_OBJECT_POINTS = 1 << 20           # bins = 'sqrt' gives at most MAX_RINGS bins up to here
 PLAN_WORDS = 40                       # SV_VC_PLAN_WORDS
-
-
-def reset_counters():
-    COUNTERS["library_calls"] = 0
-    COUNTERS["host_reads"] = 0
-
-
-def call(name, *args):
-    """One call into the library through the binding layer, counted."""
-    COUNTERS["library_calls"] += 1
-    L.check(getattr(L.load(), name)(*args), name)
-
-
-def read(t):
-    """One blocking device -> host read, counted."""
-    COUNTERS["host_reads"] += 1
-    return t.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------- planners
@@ -264,7 +249,7 @@ def vc_pointwise(clouds, noise, mode):
 
 def vc_world_transform(clouds, op, params):
     """One op of sv_world_transform_points (flip_x, flip_y, rotation, scaling) with one float64 parameter per object, in place."""
-    code = {"flip_x": 1, "flip_y": 2, "rotation": 3, "scaling": 4}[op]
+    code = P.pack_codes([op], "world")
     p = torch.from_numpy(np.ascontiguousarray(params, np.float64).reshape(clouds.batch_size, 1)).to(clouds.points.device)
     call("sv_world_transform_points", L.ptr(clouds.points), 3, L.ptr(clouds.start), L.ptr(clouds.cnt), clouds.batch_size, int(clouds.counts.max()),
          code, 1, L.ptr(p), L.stream())

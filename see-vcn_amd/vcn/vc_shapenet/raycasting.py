@@ -6,29 +6,12 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ... import data_pipeline as P
 
 # library calls and blocking device -> host reads since the last reset_counters(); neither depends on the number of triangles, cameras or cars
-COUNTERS = {"library_calls": 0, "host_reads": 0}
+_counted = P.Counted()
+COUNTERS, reset_counters, call, host_ints = _counted.counters, _counted.reset, _counted.call, _counted.host_ints
 MAX_TRIANGLES = 1 << 24                                         # the sort key holds 24 index bits (csrc/raycast.hip RC_KEY_INDEX_BITS)
-
-_ws = L.Workspace()
-
-
-def reset_counters():
-    COUNTERS["library_calls"] = 0
-    COUNTERS["host_reads"] = 0
-
-
-def call(name, *args):
-    """One call into the library through the binding layer, counted."""
-    COUNTERS["library_calls"] += 1
-    L.check(getattr(L.load(), name)(*args), name)
-
-
-def host_ints(tensors):
-    """One blocking device -> host read, counted (checks parked on the stream ride on it)."""
-    COUNTERS["host_reads"] += 1
-    return L.host_ints(tensors)
 
 
 def pinhole_camera(fov_deg, center, eye, up, width_px, height_px):
@@ -77,7 +60,7 @@ def hit_points(t_hit, segments, width_px, height_px, rays=None, cams=None, boxes
     nbytes = int(L.load().sv_ray_hit_points_scratch_bytes(segments, int(width_px), int(height_px)))
     if nbytes == 0:
         raise L.SeevcnHipError(f"hit_points: {segments} segments of {width_px} x {height_px} rays exceed the index width (2^31 rays, 65535 segments)")
-    scratch = _ws.scratch("ray_hit_points", nbytes, dev)
+    scratch = L.workspace.scratch("ray_hit_points", nbytes, dev)
     call("sv_ray_hit_points", L.ptr(rays), L.ptr(cams), segments, int(width_px), int(height_px), L.ptr(t_hit), L.ptr(boxes), L.ptr(scratch),
          L.ptr(points), L.ptr(flags), L.ptr(obj_points), L.ptr(counts), L.stream())
     return points, flags, obj_points, counts
@@ -131,7 +114,7 @@ class RaycastingScene:
                                              output_size=T)
             prim = torch.arange(T, dtype=torch.int32, device=dev) - starts
             keys = torch.empty(T, dtype=torch.int64, device=dev)
-            scratch = _ws.scratch("bvh", int(L.load().sv_bvh_scratch_bytes(T)), dev)
+            scratch = L.workspace.scratch("bvh", int(L.load().sv_bvh_scratch_bytes(T)), dev)
             call("sv_bvh_keys", L.ptr(tris), T, L.ptr(keys), L.ptr(status), L.ptr(scratch), L.stream())
             keys = torch.sort(keys).values
             call("sv_bvh_build", L.ptr(tris), L.ptr(geom), L.ptr(prim), T, L.ptr(keys), L.ptr(nodes), L.ptr(leaves), L.ptr(scratch), L.stream())

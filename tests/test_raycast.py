@@ -1,5 +1,6 @@
 """csrc/raycast.hip and seevcn_amd.vcn.vc_shapenet against the float32 brute-force restatement (tests/raycast_reference.py): bit for bit, no
-exemption.  Images are at most 64 x 32, scenes at most 1 360 triangles."""
+exemption.  Images are at most 64 x 32, scenes at most 1 360 triangles; the hit-point compaction is also held at the tile edge of its chunk
+scan, on images of 256 x 1023 .. 2049 rays of a two-triangle mesh."""
 import numpy as np
 import pytest
 
@@ -245,6 +246,61 @@ def test_hit_points_order_flags_and_counts(cuda):
     p2, f2, _, c2 = rc.hit_points(t0, 1, W * H, 1, rays=torch.from_numpy(rays0).to(cuda))
     n0 = int(counts[0, 0])
     assert c2.cpu().tolist() == [[n0], [0]] and np.array_equal(bits(p2.cpu().numpy()[:n0]), bits(pts[:n0])) and not f2.cpu().numpy()[:n0].any()
+
+
+# One workgroup scans the chunk counts (a chunk: 256 rays) in tiles of 1024 with a carry: images of 256 x H rays make H chunks a camera.  The
+# trapezoid fills part of every image row, the last one included, and narrows from row to row: every chunk counts and the counts differ.
+TILE_QUAD = np.array([[[5, -1.7, -15], [5, 1.7, -15], [5, 0.2, 15]], [[5, -1.7, -15], [5, 0.2, 15], [5, -0.2, 15]]], np.float32)
+TILE_BOX = np.array([5, 0.26, 0, 1, 0.6, 40, 0.3], np.float32)    # of every row's hits some are inside and some outside
+
+
+def _assert_hit_points_equal_the_restatement(cuda, cams, boxes, W, H, last_tile_from):
+    """Counts, order and flags of sv_ray_hit_points for TILE_QUAD against the restatement; the integer work (counts, ranks) exactly."""
+    import torch
+    from seevcn_amd.vcn.vc_shapenet import raycasting as rc
+    tris, gid, pid = R.scene_arrays([TILE_QUAD])
+    scene = device_scene([TILE_QUAD], cuda)
+    camt = cams_tensor(cams, cuda)
+    ans = scene.cast_pinhole(camt, W, H)
+    pts, flags, obj, counts = rc.hit_points(ans["t_hit"], len(cams), W, H, cams=camt, boxes=torch.from_numpy(boxes).to(cuda))
+    t_hit, counts = ans["t_hit"].cpu().numpy(), counts.cpu().numpy()
+    pts, flags, obj = pts.cpu().numpy(), flags.cpu().numpy(), obj.cpu().numpy()
+    at = at_in = chunk = 0
+    for c, cam in enumerate(cams):
+        rays = R.create_rays_pinhole(*cam)
+        want = R.brute_force(rays, tris, gid, pid, np.float32, chunk=1 << 16)
+        assert np.array_equal(bits(t_hit[c * W * H:(c + 1) * W * H]), bits(want["t_hit"]))
+        per_chunk = np.add.reduceat(np.isfinite(want["t_hit"]), np.arange(0, W * H, 256))
+        assert per_chunk.min() > 0 and len(set(per_chunk)) > 8, c     # no empty chunk: each one moves the offsets behind it
+        chunk += len(per_chunk)
+        wp = R.hit_points(rays, want["t_hit"])
+        n = len(wp)
+        assert counts[0, c] == n, (c, counts, n)
+        assert np.array_equal(bits(pts[at:at + n]), bits(wp))       # bit for bit, in ray order
+        inside, face = R.in_box(wp, boxes[c])
+        sure = face > FACE_BAND
+        f = flags[at:at + n]
+        assert np.array_equal(f[sure] != 0, inside[sure]) and set(np.unique(f)) == {0, 1}
+        assert counts[1, c] == f.sum()
+        assert np.array_equal(bits(obj[at_in:at_in + f.sum()]), bits(wp[f != 0]))
+        if c == len(cams) - 1 and last_tile_from is not None:       # hits and in-box hits behind the first 1024 chunks of the launch
+            tail = f[np.isfinite(want["t_hit"])[:last_tile_from * 256].sum():]
+            assert chunk > 1024 and 0 < tail.sum() < len(tail)
+        at, at_in = at + n, at_in + int(f.sum())
+
+
+@pytest.mark.parametrize("H", [1023, 1024, 1025, 2049])
+def test_hit_points_chunk_scan_at_its_tile_edge(cuda, H):
+    """One camera of 256 x H rays: 1023, 1024, 1025 and 2049 chunks -- below, at and one past the tile of the scan, and into its third tile."""
+    cams = [(40, (5, 0, 0), (0, 0, 0), (0, 0, 1), 256, H)]
+    _assert_hit_points_equal_the_restatement(cuda, cams, TILE_BOX[None], 256, H, 1024 if H > 1024 else None)
+
+
+def test_hit_points_chunk_scan_carries_across_cameras(cuda):
+    """Five cameras of 205 chunks each: 1025 in all, so the last camera's last chunk lies behind the scan's first tile."""
+    cams = [(40 + 3 * c, (5, 0, 0), (0, 0.1 * c, 0), (0, 0, 1), 256, 205) for c in range(5)]
+    boxes = np.stack([TILE_BOX + np.float32([0, 0.05 * c, 0, 0, 0, 0, 0]) for c in range(5)])
+    _assert_hit_points_equal_the_restatement(cuda, cams, boxes, 256, 205, 204)
 
 
 # ------------------------------------------------------------------ RaycastingScene

@@ -2,8 +2,9 @@
 sequential oracles (oracle/voxelize.py, oracle/hard_voxelize.py) and float64 references written from the definitions
 (tests/voxel_edge_reference.py).  CPU: every generated case is shown to hit the edge it is named after.  GPU: points on cell faces and one
 ulp either side, feature / stride shapes, the 2^16-point and 2^15-magnitude limits of the fixed-point sums, capacity < V, the 1024-block
-seam of the hard voxeliser's scan, a voxel cap inside a block, dense cells up to max_points = 64, non-finite coordinates, and MeanVFE and
-the pillar decoration at a tolerance derived per element from fp32 arithmetic."""
+seam of the hard voxeliser's scan (and a scene that ends one block past it, beside a one-block scene), a voxel cap inside a block, dense
+cells up to max_points = 64, non-finite coordinates, and MeanVFE and the pillar decoration at a tolerance derived per element from fp32
+arithmetic."""
 import numpy as np
 import pytest
 
@@ -28,6 +29,13 @@ def _seam():
         with np.errstate(invalid="ignore"):
             return pts, geom, ohv.points_to_voxel(pts, geom["vs"], geom["pc_range"], 3, 40000)
     return _cached("seam", make)
+
+
+def _tile_edge():
+    def make():
+        big, small, geom = ve.tile_edge_scenes(13)
+        return big, small, geom, _hard_oracle(big, geom, 3, 4096), _hard_oracle(small, geom, 3, 4096)
+    return _cached("tile_edge", make)
 
 
 def _hard_oracle(points, geom, max_points, max_voxels):
@@ -84,6 +92,17 @@ def test_seam_scene_has_first_points_on_both_sides_of_the_seam():
     cell = ve.cells_fp32(pts[:, :3], geom["lo"], geom["vs"])
     in_range = ((cell >= 0) & (cell < np.asarray(geom["grid"], F))).all(1).mean()
     assert 0.05 < in_range < 0.15                                          # about nine points in ten are out of range
+
+
+def test_tile_edge_scene_ends_one_block_past_the_scan_tile():
+    big, small, geom, (vox, crd, nump), (_, scrd, _) = _tile_edge()
+    assert len(big) == 1024 * 256 + 1 and len(small) == 255
+    first, coords = ve.first_appearance(big[:, :3], geom)
+    assert np.array_equal(coords, crd) and np.array_equal(vox[:, 0], big[first])
+    assert first[-1] == 1024 * 256                                         # the one point of block 1024 opens the last voxel
+    block = first // ve.HV_BLOCK
+    assert len(np.unique(block)) > 500 and (block == 1023).any() and np.bincount(block).max() > 4
+    assert (nump == 3).sum() > 1000 and (nump < 3).any() and 100 < len(scrd) < 255
 
 
 def test_cap_cut_scene_cuts_inside_a_block():
@@ -330,6 +349,19 @@ def test_hip_hard_seam_scene_between_an_empty_and_an_all_out_scene(cuda, hip_lib
     _assert_hard_scene(got, 0, empty, "empty scene")
     _assert_hard_scene(got, 1, want, "seam in the middle")
     _assert_hard_scene(got, 2, empty, "all points out of range")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("big_first", [True, False])
+def test_hip_hard_scan_tile_edge_beside_a_small_scene(cuda, hip_lib, big_first):
+    """1025 point blocks beside a scene of one block: the scan of the block counts takes a second tile for its last element in one scene and
+    scans 1024 empty blocks in the other.  Integer work: order, coordinates, counts and num_voxels are the oracle's exactly."""
+    big, small, geom, want_big, want_small = _tile_edge()
+    scenes = [(big, want_big), (small, want_small)][::1 if big_first else -1]
+    got = _hard(np.concatenate([p for p, _ in scenes]), 0, 4, [len(p) for p, _ in scenes], geom, 3, 4096, cuda)
+    assert got[3].tolist() == [len(w[1]) for _, w in scenes]
+    for b, (_, want) in enumerate(scenes):
+        _assert_hard_scene(got, b, want, f"scene {b}")
 
 
 @pytest.mark.gpu

@@ -112,6 +112,28 @@ def seam_scene(seed):
     return np.ascontiguousarray(pts), SEAM_GEOM
 
 
+TILE_GEOM = dict(lo=[0.0, 0.0, 0.0], vs=[1.0, 1.0, 1.0], grid=[32, 32, 2], pc_range=[0, 0, 0, 32, 32, 2])
+
+
+def tile_edge_scenes(seed):
+    """(big, small, geom): a scene of 1024*256 + 1 points [x, y, z, f] -- 1025 point blocks, one past the tile of the scan of the block counts,
+    the last block holding one point -- and a scene of 255 points, over the coarse TILE_GEOM (2048 cells).  In the big scene the cells open
+    gradually (point i falls among the first 1 + i * 2046 // n cells of a shuffled list), so first points lie in blocks all along the scene,
+    and the very last point opens the one cell kept back for it: its voxel number is the sum of all 1024 block counts before it."""
+    rng = np.random.default_rng(seed)
+    g = np.asarray(TILE_GEOM["grid"])
+    order = rng.permutation(int(g.prod()))
+    n = 1024 * HV_BLOCK + 1
+    pick = (rng.random(n) * (1 + np.arange(n) * (len(order) - 2) // n)).astype(np.int64)
+    pick[-1] = len(order) - 1
+    scenes = []
+    for cell in (order[pick], order[rng.integers(0, len(order), HV_BLOCK - 1)]):
+        ijk = np.stack([cell % g[0], cell // g[0] % g[1], cell // (g[0] * g[1])], axis=1)
+        xyz = ijk + rng.uniform(0.05, 0.95, ijk.shape)
+        scenes.append(np.ascontiguousarray(np.concatenate([xyz, rng.normal(size=(len(xyz), 1))], axis=1).astype(F)))
+    return scenes[0], scenes[1], TILE_GEOM
+
+
 CAP_GEOM = dict(lo=[0.0, 0.0, 0.0], vs=[1.0, 1.0, 1.0], grid=[40, 40, 4], pc_range=[0, 0, 0, 40, 40, 4])
 CAP_BLOCK = 4                        # the 256-point block the cap falls into
 
