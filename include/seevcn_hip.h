@@ -1323,6 +1323,42 @@ int sv_world_frustum_dropout(const float* points, int C, const int32_t* pt_start
                              int max_scene_points, const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, int32_t* box_cls,
                              int total_boxes, int64_t dirs, int num_dirs, const double* intensity, void* scratch, void* stream);
 
+/* The pyramid augmentor, random_local_pyramid_aug (csrc/augment_pyramid.hip; data_augmentor.py:221-242) on the same layout.  A box row has six
+ * pyramids, the centre as apex over one face's corners, faces in pyramid_orders' order (augmentor_utils.py:574-581).  One membership test serves
+ * every entry: float32 corners as boxes_to_corners_3d makes them (box_utils.py:28-53; cos / sin are the float64 functions rounded once), the five
+ * face planes in float64, closed -- what in_hull's Delaunay.find_simplex(p) >= 0 decides (box_utils.py:12-25, augmentor_utils.py:606-611).
+ * sv_get_pyramids (augmentor_utils.py:573-595): out (total_boxes, 6, 15) fp32, apex then the four base corners. */
+int sv_get_pyramids(const float* boxes, int W, int total_boxes, float* out, void* stream);
+/* local_pyramid_dropout's point half (augmentor_utils.py:620-624): face holds one int32 per box row, 0..5 or anything else for none; every live
+ * point inside a marked pyramid of a box of its scene (box_cls != -2) gets keep = 0.  One thread per point, the scene's marked boxes through LDS. */
+int sv_pyramid_dropout(const float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, int32_t* keep, int batch, int max_scene_points,
+                       const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls, const int32_t* face,
+                       void* stream);
+/* points_in_pyramids_mask(...).sum(0) (augmentor_utils.py:643-644, :690-691): mask holds 6 bits per box row, the faces asked for; counts
+ * (total_boxes, 6) int32 receives the live member points per pyramid (integer atomics, in LDS first; cleared here).  member (may be NULL; zeroed by
+ * the caller): one byte per (point row, box of its scene) at member[row * member_stride + box], the faces among those asked for that hold the point. */
+int sv_pyramid_count(const float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, const int32_t* keep, int batch, int max_scene_points,
+                     const float* boxes, int W, const int32_t* box_start, const int32_t* box_cnt, const int32_t* box_cls, int total_boxes,
+                     const int32_t* mask, int32_t* counts, uint8_t* member, int member_stride, void* stream);
+/* local_pyramid_sparsify's point half (augmentor_utils.py:647-659), one workgroup per pyramid that holds more than SPARSIFY_MAX_NUM points.  pyr
+ * (num_pyramids, 5) int32: scene, box row, face, the member count the host read, the first output row (a row of the scene with keep == 0); ranks
+ * (num_pyramids, K) int32: np.random.choice(count, K, replace=False), a member's rank being the number of live members before it in row order.
+ * Liveness is read from keep_in, a copy of keep made before the call, so that pyramids which share a point each see it; every member's keep is
+ * cleared, and the member of rank ranks[j][q] is copied, bits untouched, to row out + q with keep = 1.  flag (one int32, kept by the caller):
+ * |= 1 when a pyramid holds another number of members than the host planned with, |= 2 / 4 for output rows outside the scene / a plan row that
+ * names nothing; the caller reads it with its next host read and raises.  K <= 1024. */
+int sv_pyramid_sparsify(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, const int32_t* keep_in, int32_t* keep, int batch,
+                        const float* boxes, int W, int total_boxes, const int32_t* pyr, int num_pyramids, const int32_t* ranks, int K, int32_t* flag,
+                        void* stream);
+/* local_pyramid_swap's point half (augmentor_utils.py:664-682, :716-758), one workgroup per pair.  pairs (num_pairs, 8) int32: scene; box row, face
+ * and member count of the to-swap pyramid; the same three of its partner; the first output row.  On the entry flags keep_in: the members of both
+ * pyramids in row order, the minimum and maximum of the last column of each (integer atomics on an order-preserving code); rows out .. receive the
+ * partner's points mapped into the to-swap pyramid, then rows out + |partner| .. the to-swap pyramid's points mapped into the partner, keep = 1; the
+ * members' keep is cleared.  get_points_ratio / recover_points_by_ratio and the last column's rescaling by np.clip(max - min, 1e-6, 1) are float32
+ * with one rounding per operation.  C must be 4 (the reference raises otherwise); flag as above, and nothing is written on a count mismatch. */
+int sv_pyramid_swap(float* points, int C, const int32_t* pt_start, const int32_t* pt_cnt, const int32_t* keep_in, int32_t* keep, int batch,
+                    const float* boxes, int W, int total_boxes, const int32_t* pairs, int num_pairs, int32_t* flag, void* stream);
+
 /* Mesh ray casting for the VCN's "VC" training data (csrc/raycast.hip); replaces open3d.t.geometry.RaycastingScene (Embree, CPU) in
  * see/surface_completion/models/vcn/vc_shapenet/dataset_functions.py:265-342 and raycast_surface_from_meshes.py:16-52.  The arithmetic is stated in
  * tests/raycast_reference.py: Moeller-Trumbore without culling in fp32, one rounding per operation; a triangle is hit when det != 0 && u >= 0 &&

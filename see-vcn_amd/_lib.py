@@ -268,6 +268,11 @@ SIGNATURES = {
     "sv_local_transform_points": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i64, c_i, c_p, c_p]),
     "sv_world_frustum_dropout_scratch_bytes": (c_sz, [c_i, c_i]),
     "sv_world_frustum_dropout": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_p, c_p]),
+    "sv_get_pyramids": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "sv_pyramid_dropout": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "sv_pyramid_count": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
+    "sv_pyramid_sparsify": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "sv_pyramid_swap": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_p, c_p]),
     "sv_bvh_scratch_bytes": (c_sz, [c_i64]),
     "sv_bvh_keys": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p]),
     "sv_bvh_build": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),

@@ -1,4 +1,5 @@
-"""Training augmentation on the device (reference: datasets/augmentor/augmentor_utils.py, numpy on dataloader workers) on csrc/augment.hip.
+"""Training augmentation on the device (reference: datasets/augmentor/augmentor_utils.py, numpy on dataloader workers) on csrc/augment.hip,
+csrc/augment_local.hip and csrc/augment_pyramid.hip.
 
 The functions keep the reference's names and take a `DeviceBatch` -- every scene of the batch in one stacked point buffer and one stacked box
 buffer -- plus the random draws, which the caller makes on the host in the reference's order (data_augmentor.draw_params).  Points are never
@@ -26,7 +27,9 @@ class DeviceBatch:
     """The scenes of one batch, stacked.  points (P, C) fp32 and keep (P,) int32; boxes (N, W) fp32 and box_cls (N,) int32 (>= 0 index into
     class_names, -1 another class, -2 filtered out); pt_start / pt_cnt / box_start / box_cnt (B,) int32 on the device.  max_scene_points and
     max_scene_boxes are host upper bounds.  With point_slots / box_slots (GT sampling) scene b's point rows begin with point_slots[b] spare rows
-    (keep = 0 until an object is pasted there) and its box rows end with box_slots[b] spare rows (box_cls = -2, beyond box_cnt)."""
+    (keep = 0 until an object is pasted there) and its box rows end with box_slots[b] spare rows (box_cls = -2, beyond box_cnt).  add_room
+    re-stacks the points with spare rows behind each scene's (the pyramid augmentor's appended rows).  check: None, or one int32 on the device
+    that kernels raise on a broken plan; it is read with the next host read (compact's at the latest) and a non-zero value is an error."""
 
     def __init__(self, points, boxes, box_cls, pt_sizes, box_sizes, box_slots=None, point_slots=None):
         L.require_cuda(points, boxes)
@@ -50,6 +53,7 @@ class DeviceBatch:
         self.boxes = boxes.contiguous() if self.total_boxes else torch.zeros(1, boxes.shape[1], device=dev)
         self.keep = torch.ones(max(self.total_points, 1), dtype=torch.int32, device=dev)
         self.pt_offsets, self.box_offsets = np.cumsum(pt_sizes) - pt_sizes, np.cumsum(box_rows) - box_rows
+        self.pt_sizes, self.check = pt_sizes, None
         self.box_sizes = box_rows - box_slots                     # the boxes that exist on entry
         host = np.concatenate([self.pt_offsets, pt_sizes, self.box_offsets, self.box_sizes, box_rows, box_cls, [-2]]).astype(np.int32)
         meta = torch.from_numpy(host).to(dev)                   # one upload for the whole layout
@@ -75,6 +79,27 @@ class DeviceBatch:
         flags[0] = 0
         inst.keep = torch.cat([t for b in range(B) for t in (flags[0, :point_slots[b]], flags[1, :len(pts[b])])] + [flags[1, :1]])
         return inst
+
+    def add_room(self, extra):
+        """Re-stack the points with extra[b] spare rows (zeros, keep = 0) behind scene b's rows; pt_cnt then includes them and max_scene_points
+        follows.  The spare rows in front (point_slots) stay where they are.  Returns the first spare row of every scene (host, global rows)."""
+        extra = np.asarray(extra, np.int64).reshape(-1)
+        assert len(extra) == self.batch_size and (extra >= 0).all()
+        if extra.sum() == 0:
+            return self.pt_offsets + self.pt_sizes
+        dev, B = self.points.device, self.batch_size
+        spare_p = torch.zeros(int(extra.max()), self.num_point_features, device=dev)
+        spare_k = torch.zeros(int(extra.max()), dtype=torch.int32, device=dev)
+        ends = self.pt_offsets + self.pt_sizes
+        self.points = torch.cat([t for b in range(B) for t in (self.points[self.pt_offsets[b]:ends[b]], spare_p[:extra[b]])])
+        self.keep = torch.cat([t for b in range(B) for t in (self.keep[self.pt_offsets[b]:ends[b]], spare_k[:extra[b]])])
+        first = np.cumsum(self.pt_sizes + extra) - extra
+        self.pt_sizes = self.pt_sizes + extra
+        self.pt_offsets = np.cumsum(self.pt_sizes) - self.pt_sizes
+        self.max_scene_points, self.total_points = int(self.pt_sizes.max()), int(self.pt_sizes.sum())
+        meta = torch.from_numpy(np.concatenate([self.pt_offsets, self.pt_sizes]).astype(np.int32)).to(dev)
+        self.pt_start, self.pt_cnt = meta[:B], meta[B:]
+        return first
 
     def _pt_args(self):
         return L.ptr(self.points), self.num_point_features, L.ptr(self.pt_start), L.ptr(self.pt_cnt)
@@ -293,6 +318,194 @@ def global_frustum_dropout_right(batch, intensity):
     world_frustum_dropout(batch, ["world_dropout_right"], _per_scene(batch, intensity))
 
 
+# ------------------------------------------------------------------ the pyramid augmentor (csrc/augment_pyramid.hip)
+# The draws of one scene, in the reference's stream order (augmentor_utils.py:617-619, :635-637, :656, :687, :699, :708); out["draws"] carries them
+# under these names.  *_face / *_u hold one value per box the step looks at, sparsify_choice one index array per sparsified pyramid, swap_face and
+# swap_partner one value per swapped pair (the partner as an index into the boxes the swap looks at).
+PYRAMID_DRAWS = ("pyramid_drop_face", "pyramid_drop_u", "pyramid_sparsify_face", "pyramid_sparsify_u", "pyramid_sparsify_choice", "pyramid_swap_u",
+                 "pyramid_swap_face", "pyramid_swap_partner")
+MAX_SPARSIFY_NUM = 1024
+_CHECK_BITS = ((1, "a pyramid holds another number of points than the count its draws and rows were planned with"),
+               (2, "appended rows outside the scene's rows"), (4, "a plan row that names no scene, box or face"))
+
+
+def _check_tensor(batch):
+    if batch.check is None:
+        batch.check = torch.zeros(1, dtype=torch.int32, device=batch.points.device)
+    return batch.check
+
+
+def read_checked(batch, t):
+    """One counted host read of the int32 tensor t; the batch's check flag rides on it and a raised flag is an error."""
+    if batch.check is None:
+        return read(t)
+    values = read(torch.cat([t.reshape(-1), batch.check]))
+    if values[-1] != 0:
+        raise L.SeevcnHipError("pyramid augmentor: " + "; ".join(text for bit, text in _CHECK_BITS if int(values[-1]) & bit))
+    return values[:-1].reshape(t.shape)
+
+
+def get_pyramids(boxes):
+    """augmentor_utils.py:573-595: boxes (N, W >= 7) fp32 on the device -> (N, 6, 15) fp32, per face the apex (the centre) and the four base corners,
+    as boxes_to_corners_3d makes them in float32 (cos / sin: the float64 function rounded once)."""
+    L.require_cuda(boxes)
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] >= 7
+    boxes = boxes.contiguous()
+    out = torch.empty(boxes.shape[0], 6, 15, dtype=torch.float32, device=boxes.device)
+    call("sv_get_pyramids", L.ptr(boxes), int(boxes.shape[1]), int(boxes.shape[0]), L.ptr(out), L.stream())
+    return out
+
+
+def _box_ints(batch, values):
+    """One int32 per box row on the device (and one more, so that an empty batch hands no null pointer)."""
+    host = np.zeros(batch.total_boxes + 1, np.int32)
+    host[:batch.total_boxes] = np.asarray(values, np.int64).reshape(-1)
+    return torch.from_numpy(host).to(batch.points.device)
+
+
+def points_in_pyramids_mask(batch, face_mask=None, member=False):
+    """augmentor_utils.py:606-611 for the whole batch: face_mask (N,) holds 6 bits per box row, the faces asked for (default: all six of every row;
+    rows with box_cls == -2 never take part).  Returns counts (N, 6) int32 on the device, the live points per pyramid, and with member=True also
+    (total_points, max_scene_boxes) uint8: per point row and box of its scene the faces whose pyramid holds the point.  One library call."""
+    dev, N = batch.points.device, batch.total_boxes
+    mask = _box_ints(batch, np.full(N, 63) if face_mask is None else face_mask)
+    counts = torch.zeros(max(N, 1), 6, dtype=torch.int32, device=dev)
+    stride = batch.max_scene_boxes if member else 0
+    flags = torch.zeros(max(batch.total_points, 1), max(stride, 1), dtype=torch.uint8, device=dev) if member else None
+    call("sv_pyramid_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
+         N, L.ptr(mask), L.ptr(counts), L.ptr(flags), stride, L.stream())
+    return (counts[:N], flags[:batch.total_points]) if member else counts[:N]
+
+
+def local_pyramid_dropout(batch, faces, u, dropout_prob):
+    """augmentor_utils.py:614-627: faces / u (N,) are the draws randint(0, 6) and uniform(0, 1) per box row (rows that do not take part are not
+    read: NaN is fine there); box row i loses the live points of face faces[i] when u[i] <= dropout_prob.  Returns the (N,) bool host mask of the
+    boxes that dropped a face: they leave the pyramid list.  One library call."""
+    u, faces = np.asarray(u, np.float64).reshape(-1), np.asarray(faces, np.float64).reshape(-1)
+    assert len(u) == len(faces) == batch.total_boxes
+    drop = np.zeros(len(u), bool)
+    np.less_equal(u, float(dropout_prob), out=drop, where=~np.isnan(u))
+    if drop.any():
+        code = _box_ints(batch, np.where(drop, np.nan_to_num(faces), -1))
+        call("sv_pyramid_dropout", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(),
+             L.ptr(batch.box_cls), L.ptr(code), L.stream())
+    return drop
+
+
+def plan_pyramid_sparsify(counts, selected, max_num, rngs=None, choices=None):
+    """The count-dependent half of local_pyramid_sparsify (augmentor_utils.py:645-657) on the host.  counts (N, 6): the live points per pyramid as read
+    from the device; selected[b] = (box rows, faces) of scene b's selected boxes in box order.  Per selected pyramid with more than max_num points,
+    in order, choice(count, size=max_num, replace=False) from rngs[b] (or choices[b], the replay).  Returns the plan local_pyramid_sparsify runs:
+    pyr rows (scene, box row, face, count, first output row relative to the scene's appended rows), ranks, the draws per scene and the rows to
+    append per scene."""
+    K = int(max_num)
+    if not 0 <= K <= MAX_SPARSIFY_NUM:
+        raise ValueError(f"SPARSIFY_MAX_NUM must be in 0..{MAX_SPARSIFY_NUM}, got {K}")
+    pyr, ranks, drawn, room = [], [], [], []
+    for b, (rows, faces) in enumerate(selected):
+        mine = []
+        for row, face in zip(rows, faces):
+            c = int(counts[int(row), int(face)])
+            if c <= K:
+                continue
+            if choices is None:
+                idx = np.asarray(rngs[b].choice(c, size=K, replace=False), np.int64).reshape(-1)
+            else:
+                if len(mine) >= len(choices[b]):
+                    raise ValueError(f"scene {b}: pyramid_sparsify_choice holds {len(choices[b])} draws, more pyramids than that hold over {K} points")
+                idx = np.asarray(choices[b][len(mine)], np.int64).reshape(-1)
+                if len(idx) != K or len(set(idx.tolist())) != K or (K and (idx.min() < 0 or idx.max() >= c)):
+                    raise ValueError(f"scene {b}: a replayed choice is not {K} distinct indices below the pyramid's {c} points")
+            pyr.append((b, int(row), int(face), c, len(mine) * K))
+            ranks.append(idx)
+            mine.append(idx)
+        if choices is not None and len(mine) != len(choices[b]):
+            raise ValueError(f"scene {b}: pyramid_sparsify_choice holds {len(choices[b])} draws for {len(mine)} pyramids over {K} points")
+        drawn.append(mine)
+        room.append(len(mine) * K)
+    return {"pyr": np.array(pyr, np.int64).reshape(-1, 5), "ranks": np.array(ranks, np.int64).reshape(len(pyr), K), "K": K, "choices": drawn,
+            "room": np.array(room, np.int64)}
+
+
+def _plan_rows(batch, plan, key, column):
+    """Make room behind the scenes for the plan's rows and turn its relative output rows into global ones; the table on the device."""
+    first = batch.add_room(plan["room"])
+    table = plan[key].copy()
+    table[:, column] += first[table[:, 0]]
+    return table
+
+
+def local_pyramid_sparsify(batch, plan):
+    """augmentor_utils.py:647-659 with a plan from plan_pyramid_sparsify: every member of a planned pyramid gets keep = 0 and the chosen ones are
+    copied behind the scene's rows in choice order, pyramid after pyramid.  One library call (none for an empty plan), no host read; a count that
+    differs from the plan's raises the batch's check flag."""
+    if len(plan["pyr"]) == 0:
+        return
+    table = _plan_rows(batch, plan, "pyr", 4)
+    up = torch.from_numpy(np.concatenate([table.reshape(-1), plan["ranks"].reshape(-1), [0]]).astype(np.int32)).to(batch.points.device)
+    keep_in = batch.keep.clone()
+    call("sv_pyramid_sparsify", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width,
+         batch.total_boxes, L.ptr(up[:table.size]), len(table), L.ptr(up[table.size:]), plan["K"], L.ptr(_check_tensor(batch)), L.stream())
+
+
+def plan_pyramid_swap(counts, left, selected, max_num, rngs=None, faces=None, partners=None):
+    """The count-dependent half of local_pyramid_swap (augmentor_utils.py:689-713) on the host.  counts (N, 6) as read from the device; left[b]: the
+    box rows the swap looks at, in order; selected[b]: (k,) bool, the boxes whose uniform fell under SWAP_PROB.  Per selected box with a face of more
+    than max_num points choice(its valid faces); the chosen pairs leave the valid table; per pair choice(boxes whose face is still valid), or the
+    box itself without a draw.  faces / partners: the replay.  Returns the plan local_pyramid_swap runs: pairs (scene, box row, face, count,
+    partner row, face, count, first output row relative to the scene's appended rows), the draws and the rows to append per scene."""
+    pairs, f_out, p_out, room = [], [], [], []
+    for b, rows in enumerate(left):
+        rows, sel = np.asarray(rows, np.int64), np.asarray(selected[b], bool)
+        nums = np.asarray(counts)[rows].reshape(len(rows), 6)
+        valid = nums > int(max_num)
+        chosen = valid & sel[:, None]
+        ci = [i for i in range(len(rows)) if chosen[i].any()]
+        if faces is None:
+            cj = [int(rngs[b].choice(np.nonzero(chosen[i])[0])) for i in ci]
+        else:
+            cj = [int(v) for v in np.asarray(faces[b]).reshape(-1)]
+            if len(cj) != len(ci) or not all(0 <= j < 6 and chosen[i, j] for i, j in zip(ci, cj)):
+                raise ValueError(f"scene {b}: the replayed pyramid_swap_face does not name one valid face per selected box")
+        valid[np.array(ci, np.int64), np.array(cj, np.int64)] = False
+        part = []
+        for t, (i, j) in enumerate(zip(ci, cj)):
+            cand = np.nonzero(valid[:, j])[0]
+            if partners is None:
+                part.append(int(rngs[b].choice(cand)) if len(cand) else i)
+            else:
+                q = int(np.asarray(partners[b]).reshape(-1)[t]) if t < len(np.asarray(partners[b]).reshape(-1)) else -1
+                if not (q in cand.tolist() if len(cand) else q == i):
+                    raise ValueError(f"scene {b}: the replayed pyramid_swap_partner names no box whose face is still valid")
+                part.append(q)
+        if partners is not None and len(np.asarray(partners[b]).reshape(-1)) != len(ci):
+            raise ValueError(f"scene {b}: pyramid_swap_partner holds another number of draws than there are pairs")
+        at = 0
+        for i, j, q in zip(ci, cj, part):
+            pairs.append((b, rows[i], j, nums[i, j], rows[q], j, nums[q, j], at))
+            at += int(nums[i, j] + nums[q, j])
+        f_out.append(np.array(cj, np.int64))
+        p_out.append(np.array(part, np.int64))
+        room.append(at)
+    return {"pairs": np.array(pairs, np.int64).reshape(-1, 8), "faces": f_out, "partners": p_out, "room": np.array(room, np.int64)}
+
+
+def local_pyramid_swap(batch, plan):
+    """augmentor_utils.py:716-761 with a plan from plan_pyramid_swap: the points of every involved pyramid get keep = 0; per pair the partner's points
+    mapped into the to-swap pyramid and then the to-swap pyramid's points mapped into the partner are written behind the scene's rows (a self-swap
+    and a partner shared by two pairs come out once per pair, as they do there).  One library call (none for an empty plan), no host read."""
+    if len(plan["pairs"]) == 0:
+        return
+    if batch.num_point_features != 4:
+        raise ValueError(f"local_pyramid_swap re-assembles x y z and the last column: points with {batch.num_point_features} columns cannot be "
+                         "swapped (np.concatenate raises in the reference)")
+    table = _plan_rows(batch, plan, "pairs", 7)
+    up = torch.from_numpy(table.reshape(-1).astype(np.int32)).to(batch.points.device)
+    keep_in = batch.keep.clone()
+    call("sv_pyramid_swap", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width,
+         batch.total_boxes, L.ptr(up), len(table), L.ptr(_check_tensor(batch)), L.stream())
+
+
 def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
     """sv_augment_compact without the host read: (out_points, out_meta, gt, box_keep).  batch.keep holds the points' final flags afterwards."""
     dev, B, C, W = batch.points.device, batch.batch_size, batch.num_point_features, batch.box_width
@@ -320,7 +533,7 @@ def compact(batch, point_range=None, box_range=None, min_num_corners=0, shuffle=
     points_per_scene / boxes_per_scene (host) and empty_scenes (scenes that ended with no box)."""
     B = batch.batch_size
     out_points, out_meta, gt, _ = launch_compact(batch, point_range, box_range, min_num_corners)
-    counts = read(out_meta[B + 1:])
+    counts = read_checked(batch, out_meta[B + 1:])
     points_per_scene, boxes_per_scene = counts[:B].astype(np.int64), counts[B:].astype(np.int64)
     points = out_points[:int(points_per_scene.sum())]
     if shuffle is not None and shuffle is not False:

@@ -9,6 +9,10 @@ Staged draws.  The local augmentors draw once per box, counted by the boxes that
 on the device: gt_sampling (by its acceptances) and random_world_frustum_dropout (by the boxes it drops).  A queue in which a per-box draw
 follows one of the two is cut behind it into stages: `forward` then takes one RandomState per scene, draws every scene's stream up to the
 boundary, runs the device work, reads the class codes back (one host read per boundary, a number fixed by the queue) and continues every stream.
+
+random_local_pyramid_aug sizes draws by point counts that only the device knows, so a queue that holds it is always staged, and the entry cuts
+itself twice: dropout and sparsify box draws -> device -> read of the selected pyramids' counts; choice draws and swap box draws -> device ->
+read of the swap's counts; the swap's choices and the rest of the queue.  A read is skipped when no scene selected a box for that step.
 """
 import numpy as np
 import torch
@@ -37,6 +41,9 @@ DIRECTIONS = ("top", "bottom", "left", "right")
 #   random_local_scaling      uniform(lo, hi) per box, nothing at all when hi - lo < 1e-3       :399-404
 #   random_world_frustum_dropout   uniform(lo, hi) per direction                                :331, :348, :365, :382
 #   random_local_frustum_dropout   uniform(lo, hi) per direction, per box                       :484, :504, :524, :544
+#   random_local_pyramid_aug  randint(0, 6, n), uniform(0, 1, n); randint(0, 6, m), uniform(0, 1, m), choice(count, MAX, replace=False) per
+#                             sparsified pyramid; uniform(0, 1, k), choice(valid faces) per selected box, choice(valid boxes) per pair
+#                             (made by BatchDataAugmentor._run_pyramid between its device steps)                  :617-619, :635-656, :687-710
 def _per_box(lo, hi):
     """One Python-float draw per box, as the reference's loop over the boxes makes them."""
     return lambda rng, n, *scene: np.array([rng.uniform(lo, hi) for _ in range(int(n))], np.float64)
@@ -109,6 +116,15 @@ def _frustum_dropout(prefix, per_box):
     return draws
 
 
+PYRAMID = "random_local_pyramid_aug"
+PYRAMID_KEYS = ("DROP_PROB", "SPARSIFY_PROB", "SPARSIFY_MAX_NUM", "SWAP_PROB", "SWAP_MAX_NUM")
+
+
+def _pyramid(cur):
+    for name in A.PYRAMID_DRAWS:                                 # sized by what the device decides: no draw function, the entry is a stage of its own
+        yield name, True, None
+
+
 # NAME -> (the keys the entry is read by and the reference has no default for (data_augmentor.py:134-219), whether it changes the number of boxes
 # on the device, its draws)
 AUGMENTORS = {
@@ -124,11 +140,18 @@ AUGMENTORS = {
     "random_world_frustum_dropout": (("INTENSITY_RANGE", "DIRECTION"), True, _frustum_dropout("world_dropout_", False)),
     "random_local_frustum_dropout": (("INTENSITY_RANGE", "DIRECTION"), False, _frustum_dropout("local_dropout_", True)),
 }
+# the same three per NAME for the entries whose draws are sized by numbers the device decides: a stage of their own, never drawn ahead
+DEVICE_SIZED = {PYRAMID: (PYRAMID_KEYS, False, _pyramid)}
+
+
+def _entry(name):
+    """The table row of a config NAME, None for a name that is not built."""
+    return AUGMENTORS.get(name) or DEVICE_SIZED.get(name)
 
 
 def _draws(cur):
     """The draws of one queue entry: (draw name, per box, draw) in order."""
-    return AUGMENTORS[cfg_get(cur, "NAME")][2](cur)
+    return _entry(cfg_get(cur, "NAME"))[2](cur)
 
 
 def _plan(entries):
@@ -151,9 +174,9 @@ def _queue(augmentor_configs):
         name = cfg_get(cur, "NAME")
         if name in disabled:
             continue
-        if name not in AUGMENTORS:
+        if _entry(name) is None:
             raise NotImplementedError(name)
-        for key in AUGMENTORS[name][0]:
+        for key in _entry(name)[0]:
             if cfg_get(cur, key) is None:                        # refused when the queue is built, not at the first draw
                 raise NotImplementedError(f"{name} without {key}")
         if name == "random_object_scaling" and any(cfg_get(q, "NAME") == "gt_sampling" for q in queue):
@@ -171,15 +194,26 @@ def _draws_per_box(cur):
     return any(per_box for _, per_box, _ in _draws(cur))
 
 
+def _is_pyramid(stage):
+    return len(stage) == 1 and cfg_get(stage[0], "NAME") == PYRAMID
+
+
 def _stages(queue):
-    """The queue cut behind every gt_sampling / random_world_frustum_dropout that a per-box draw follows; one stage for every queue without."""
+    """The queue cut behind every gt_sampling / random_world_frustum_dropout that a per-box draw follows; one stage for every queue without.  A
+    random_local_pyramid_aug is a stage of its own (it cuts itself further: _run_pyramid), between stages of the other entries; the first and the
+    last stage are always of the other kind (empty where the queue begins or ends with the pyramid entry): they carry the class codes' upload and the
+    heading's limit_period."""
     stages, cur = [], []
     for i, q in enumerate(queue):
         if cfg_get(q, "NAME") == "gt_sampling" and stages:
             # its draw needs the names of the boxes that are left, which only the device knows by then
             raise NotImplementedError("gt_sampling behind a per-box draw that follows random_world_frustum_dropout")
+        if cfg_get(q, "NAME") == PYRAMID:
+            stages += ([cur] if cur or not stages else []) + [[q]]
+            cur = []
+            continue
         cur.append(q)
-        if AUGMENTORS[cfg_get(q, "NAME")][1] and any(_draws_per_box(r) for r in queue[i + 1:]):
+        if _entry(cfg_get(q, "NAME"))[1] and any(_draws_per_box(r) for r in queue[i + 1:]):
             stages.append(cur)
             cur = []
     return stages + [cur]
@@ -203,8 +237,9 @@ def draw_params(rng, augmentor_configs, num_boxes, sampler=None, gt_names=None):
     A queue in which a per-box draw follows gt_sampling or random_world_frustum_dropout cannot be drawn ahead: ValueError (see forward)."""
     queue = _queue(augmentor_configs)
     if len(_stages(queue)) > 1:
-        raise ValueError("a per-box draw follows gt_sampling or random_world_frustum_dropout: the number of boxes it is sized by is decided on the "
-                         "device, so one shared stream cannot be replayed; give forward() one RandomState per scene")
+        raise ValueError("a per-box draw follows gt_sampling or random_world_frustum_dropout, or the queue holds random_local_pyramid_aug: the "
+                         "number of boxes or points it is sized by is decided on the device, so one shared stream cannot be replayed; give "
+                         "forward() one RandomState per scene")
     plan = _plan(queue)
     return [_draw(plan, rng, n, sampler, None if gt_names is None else gt_names[b]) for b, n in enumerate(num_boxes)]
 
@@ -220,7 +255,13 @@ class BatchDataAugmentor:
     then equals the reference run on that sample alone from that state.  A staged queue (module docstring) needs the list, and costs one more
     host read per boundary.  The local augmentors move every box that exists (box_cls != -2), those of other classes too, as the reference's
     loops over gt_boxes do; behind a gt_sampling that accepted something, the scene's boxes of other classes are gone, as they are there
-    (database_sampler.py: gt_boxes[gt_boxes_mask]).  random_local_pyramid_aug is not built and raises."""
+    (database_sampler.py: gt_boxes[gt_boxes_mask]).
+
+    random_local_pyramid_aug (SE-SSD's face dropout, sparsify and swap; csrc/augment_pyramid.hip) is always staged: it needs the list of random
+    states and adds at most two host reads, whatever the batch.  Every box row that exists takes part, other classes included.  Its rows come out
+    in the reference's order: the scene's remaining points, then each sparsified pyramid's chosen points, then per swapped pair the two mapped
+    blocks (a self-swap and a shared partner repeat points, as they do there).  SWAP_PROB > 0 needs points of exactly 4 columns and raises
+    otherwise when the batch is formed (the reference raises at the first swap); dropout and sparsify work for any C >= 3."""
 
     def __init__(self, root_path, augmentor_configs, class_names, logger=None, min_points_of_gt=1, data_processor=None, db_infos=None,
                  database=None):
@@ -309,9 +350,71 @@ class BatchDataAugmentor:
                     cls = batch.box_cls[:N]
                     cls.copy_(torch.where((cls == -1) & (batch.box_cnt > before)[scene], torch.full_like(cls, -2), cls))
 
+    def _run_pyramid(self, batch, cur, rows, rng, given):
+        """random_local_pyramid_aug on the device (data_augmentor.py:221-242).  rows[b]: the box rows of scene b that exist; rng: one RandomState
+        per scene, or given[b]: the scene's eight replayed draws.  A fixed number of library calls and at most two host reads; returns the draws."""
+        B, N = batch.batch_size, batch.total_boxes
+        drop_p, sp_p, sp_max, sw_p, sw_max = (cfg_get(cur, k) for k in PYRAMID_KEYS)
+        replay = None if given is None else [dict(d) for d in given]
+        if replay is not None and any(tuple(n for n, _ in d) != A.PYRAMID_DRAWS for d in given):
+            raise ValueError(f"random_local_pyramid_aug replays the draws {A.PYRAMID_DRAWS} in that order")
+
+        def draw(b, name, n, make):
+            if replay is None:
+                return make(rng[b])
+            value = np.asarray(replay[b][name]).reshape(-1)
+            if len(value) != n:
+                raise ValueError(f"scene {b}: {name} holds {len(value)} draws, the scene has {n} boxes at that point")
+            return value
+
+        out = [{} for _ in range(B)]
+        # dropout's and sparsify's box draws; the device drops the faces and counts the selected pyramids
+        faces, u = np.full(N, np.nan), np.full(N, np.nan)
+        for b in range(B):
+            n = len(rows[b])
+            out[b]["pyramid_drop_face"] = faces[rows[b]] = draw(b, "pyramid_drop_face", n, lambda r: r.randint(0, 6, n))
+            out[b]["pyramid_drop_u"] = u[rows[b]] = draw(b, "pyramid_drop_u", n, lambda r: r.uniform(0, 1, n))
+        dropped = A.local_pyramid_dropout(batch, faces, u, drop_p)
+        selected, left = [], []
+        mask = np.zeros(N, np.int64)
+        for b in range(B):
+            mine = rows[b][~dropped[rows[b]]]
+            m = len(mine)
+            f = out[b]["pyramid_sparsify_face"] = draw(b, "pyramid_sparsify_face", m, lambda r: r.randint(0, 6, m))
+            v = out[b]["pyramid_sparsify_u"] = draw(b, "pyramid_sparsify_u", m, lambda r: r.uniform(0, 1, m))
+            sel = v <= sp_p
+            selected.append((mine[sel], np.asarray(f)[sel].astype(np.int64)))
+            left.append(mine[~sel])
+            mask[selected[b][0]] = 1 << selected[b][1]
+        counts = A.read_checked(batch, A.points_in_pyramids_mask(batch, mask)) if mask.any() else np.zeros((N, 6), np.int32)
+        # the choices the counts size; sparsify; the swap's box draws; the device counts the pyramids of the boxes that are left
+        plan = A.plan_pyramid_sparsify(counts, selected, sp_max, rng, None if replay is None else [d["pyramid_sparsify_choice"] for d in replay])
+        A.local_pyramid_sparsify(batch, plan)
+        chosen = []
+        mask = np.zeros(N, np.int64)
+        for b in range(B):
+            out[b]["pyramid_sparsify_choice"] = plan["choices"][b]
+            k = len(left[b])
+            v = out[b]["pyramid_swap_u"] = draw(b, "pyramid_swap_u", k, lambda r: r.uniform(0, 1, k))
+            chosen.append(v <= sw_p)
+            if chosen[b].any():
+                mask[left[b]] = 63
+        counts = A.read_checked(batch, A.points_in_pyramids_mask(batch, mask)) if mask.any() else np.zeros((N, 6), np.int32)
+        # the swap's choices; the swap
+        plan = A.plan_pyramid_swap(counts, left, chosen, sw_max, rng, None if replay is None else [d["pyramid_swap_face"] for d in replay],
+                                   None if replay is None else [d["pyramid_swap_partner"] for d in replay])
+        A.local_pyramid_swap(batch, plan)
+        for b in range(B):
+            out[b]["pyramid_swap_face"], out[b]["pyramid_swap_partner"] = plan["faces"][b], plan["partners"][b]
+        return [[(name, d[name]) for name in A.PYRAMID_DRAWS] for d in out]
+
     def forward(self, scenes, rng=None, draws=None):
         cls = [self._class_index(s["gt_names"]) for s in scenes]
         pts, boxes = [s["points"] for s in scenes], [s["gt_boxes"] for s in scenes]
+        for cur in self.data_augmentor_queue:
+            if cfg_get(cur, "NAME") == PYRAMID and cfg_get(cur, "SWAP_PROB") > 0 and any(p.shape[1] != 4 for p in pts):
+                raise ValueError("random_local_pyramid_aug with SWAP_PROB > 0 needs points of exactly 4 columns: the swap re-assembles x y z and "
+                                 f"the last column (the reference raises at the first swap); got {sorted({int(p.shape[1]) for p in pts})}")
         batch = None
         # MIN_POINTS_OF_GT before anything else (dataset.py:129-137)
         if all(s.get("num_points_in_gt") is not None for s in scenes):
@@ -329,7 +432,8 @@ class BatchDataAugmentor:
             raise ValueError(f"{len(rng)} random states for {B} scenes")
         if draws is None and len(stages) > 1 and not per_scene:
             raise ValueError("this queue makes a per-box draw behind gt_sampling or random_world_frustum_dropout, whose number of boxes is decided "
-                             "on the device: scene 1's draws would have to come before it is known how many scene 0 makes, so one shared "
+                             "on the device (or holds random_local_pyramid_aug, whose draws are sized by point counts decided there): scene 1's "
+                             "draws would have to come before it is known how many scene 0 makes, so one shared "
                              "stream cannot follow the reference; pass rng as a list of one numpy RandomState per scene")
         given, taken = draws, [0] * B
         names = [np.asarray(s["gt_names"])[p] for s, p in zip(scenes, present)]
@@ -365,14 +469,27 @@ class BatchDataAugmentor:
         all_draws = [list(d) for d in first]
         self._run_stage(batch, first, rows, codes, candidates, len(stages) == 1)
         bounds = np.append(batch.box_offsets, N)
+        changes_boxes = lambda entries: any(_entry(cfg_get(q, "NAME"))[1] for q in entries)
+        stale = changes_boxes(stages[0])                         # whether the device has changed which box rows exist since the host last knew
         for s in range(1, len(stages)):
-            now = A.read(batch.box_cls[:N])                      # the boundary: which box rows exist now
-            rows = [bounds[b] + np.nonzero(now[bounds[b]:bounds[b + 1]] != -2)[0] for b in range(B)]
-            num_boxes = [len(r) for r in rows]
-            cur = stage_draws(stages[s])
+            if stale:
+                now = A.read_checked(batch, batch.box_cls[:N])   # the boundary: which box rows exist now
+                rows = [bounds[b] + np.nonzero(now[bounds[b]:bounds[b + 1]] != -2)[0] for b in range(B)]
+                num_boxes = [len(r) for r in rows]
+                stale = False
+            if _is_pyramid(stages[s]):
+                mine = None
+                if given is not None:
+                    mine = [list(given[b][taken[b]:taken[b] + len(A.PYRAMID_DRAWS)]) for b in range(B)]
+                    for b in range(B):
+                        taken[b] += len(A.PYRAMID_DRAWS)
+                cur = self._run_pyramid(batch, stages[s][0], rows, rng, mine)
+            else:
+                cur = stage_draws(stages[s])
+                self._run_stage(batch, cur, rows, None, candidates, s == len(stages) - 1)
+                stale = changes_boxes(stages[s])
             for b in range(B):
                 all_draws[b] += cur[b]
-            self._run_stage(batch, cur, rows, None, candidates, s == len(stages) - 1)
         dp = self.data_processor
         out = A.compact(batch, **(dp.tail_args() if dp is not None else {}))
         out["draws"] = all_draws

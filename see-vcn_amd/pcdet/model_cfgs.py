@@ -440,3 +440,20 @@ def pointpillar_newaugs_augmentor_cfg():
             dict(NAME='random_local_translation', LOCAL_TRANSLATION_RANGE=[0.95, 1.05], ALONG_AXIS_LIST=['x', 'y', 'z']),
             dict(NAME='random_world_frustum_dropout', INTENSITY_RANGE=[0, 0.2], DIRECTION=['top']),
             dict(NAME='random_local_frustum_dropout', INTENSITY_RANGE=[0, 0.2], DIRECTION=['top'])])
+
+
+def pointpillar_pyramid_aug_augmentor_cfg():
+    """DATA_CONFIG.DATA_AUGMENTOR of detector3d/tools/cfgs/kitti_models/pointpillar_pyramid_aug.yaml:23-57, values copied as data, with
+    USE_ROAD_PLANE=False: road planes are not built (the YAML says True).  The pyramid entry follows gt_sampling, so BatchDataAugmentor runs this
+    queue staged: forward() takes one RandomState per scene."""
+    return dict(
+        DISABLE_AUG_LIST=['placeholder'],
+        AUG_CONFIG_LIST=[
+            dict(NAME='gt_sampling', USE_ROAD_PLANE=False, DB_INFO_PATH=['kitti_dbinfos_train.pkl'],
+                 PREPARE=dict(filter_by_min_points=['Car:5', 'Pedestrian:5', 'Cyclist:5'], filter_by_difficulty=[-1]),
+                 SAMPLE_GROUPS=['Car:15', 'Pedestrian:15', 'Cyclist:15'], NUM_POINT_FEATURES=4, DATABASE_WITH_FAKELIDAR=False,
+                 REMOVE_EXTRA_WIDTH=[0.0, 0.0, 0.0], LIMIT_WHOLE_SCENE=False),
+            dict(NAME='random_world_flip', ALONG_AXIS_LIST=['x']),
+            dict(NAME='random_world_rotation', WORLD_ROT_ANGLE=[-0.78539816, 0.78539816]),
+            dict(NAME='random_world_scaling', WORLD_SCALE_RANGE=[0.95, 1.05]),
+            dict(NAME='random_local_pyramid_aug', DROP_PROB=0.25, SPARSIFY_PROB=0.05, SPARSIFY_MAX_NUM=50, SWAP_PROB=0.1, SWAP_MAX_NUM=50)])
