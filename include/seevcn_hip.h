@@ -1426,6 +1426,36 @@ int sv_vc_pointwise(float* points, int64_t total, const double* noise, int mode,
  * fp32 rotation of utils/transform.py:33-58), float64 product with the scale, fp32 rotation back, float64 sum with the centre.  In place. */
 int sv_vc_object_scale(float* points, const int32_t* start, const int32_t* cnt, int batch, int max_points, const double* params, void* stream);
 
+/* ---- VCN validation metrics (csrc/vc_metrics.hip): see/surface_completion/models/vcn/utils/metrics.py (Metrics.get, the six enabled items over the
+ * whole batch and the four num_pts levels), utils/losses.py:90-103 (get_oob_error), utils/bbox_utils.py:29-78, utils/transform.py:163-187.  The
+ * arithmetic is stated in tests/vc_metrics_reference.py.
+ * sv_vc_metrics_objects: coarse (B,n,3), complete (B,m,3), gt_boxes (B,7), reg_rot (B,3,3) or null, reg_centre (B,3) or null -> table
+ * (B, SV_VCM_COLS) of 4-byte words, fp32 unless said otherwise, one row an object:
+ *    0 .. 3   sum d1, sum sqrt d1 (coarse -> complete), sum d2, sum sqrt d2 (complete -> coarse); d = the minimum over the other cloud of the fp32
+ *             (dx*dx + dy*dy) + dz*dz
+ *    4 .. 7   the same four over the rows with (x + y) + z != 0 in fp32, the minimum over such rows of the other cloud (0 when it has none)
+ *    8, 9     int32: rows of coarse, of complete with (x + y) + z != 0
+ *   10 .. 15  get_bbox_from_keypoints: centre of the bounds, extents in the ground-truth heading frame (the heading is gt_boxes[:, 6])
+ *   16        3-D IoU of that box with the ground-truth box (sv_boxes_iou3d_batch's arithmetic, this pair only)
+ *   17, 18    int32: distinct rows of coarse outside the ground-truth cuboid (float64 test, faces inclusive); distinct scalars among its 3 n coordinates
+ *   19        fp32(17) / fp32(18)
+ *   20        |atan2f(r01 / |r0|, r00 / |r0|) - heading|, r0 = row 0 of reg_rot; -1 when reg_rot is null
+ *   21        ((|dx| + |dy|) + |dz|) / 3 of reg_centre - centre; -1 when reg_centre is null
+ *   22, 23    int32: n, m
+ * One workgroup of 1024 an object; the summation order is stated in the source's header.  1 <= n <= 4096 (the cloud and its sort live in LDS), m >= 1;
+ * complete == null with m == 0 skips the Chamfer columns (they are written as 0): get_oob_error's call.
+ * sv_vc_metrics_levels: table, num_pts (B) int32 -> out (30) fp32 in Metrics.names() order: CDL1, CDL2, OUT_OF_BOX, IOU_3D, Rotation_Error,
+ * Translation_Error, each for the whole batch, then L1 (num_pts 201 .. 1000000), L2 (81 .. 200), L3 (31 .. 80), L4 (5 .. 30); sums over the objects in
+ * ascending index.  An empty group gives -1; the Chamfer values of a one-object group come from columns 4 .. 9 (-1 when a count is 0) and are -1 when
+ * m == 1; Rotation_Error is the lower median; columns 20 / 21 at -1 give -1.  1 <= B <= 4096.
+ * sv_vc_metrics_columns() == SV_VCM_COLS; sv_vc_metrics_tile(): rows of the complete cloud staged in LDS at a time. */
+#define SV_VCM_COLS 24
+int sv_vc_metrics_columns(void);
+int sv_vc_metrics_tile(void);
+int sv_vc_metrics_objects(const float* coarse, const float* complete, const float* gt_boxes, const float* reg_rot, const float* reg_centre,
+                          int batch, int n, int m, float* table, void* stream);
+int sv_vc_metrics_levels(const float* table, const int32_t* num_pts, int batch, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

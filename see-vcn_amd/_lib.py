@@ -286,6 +286,10 @@ SIGNATURES = {
     "sv_vc_resample": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
     "sv_vc_pointwise": (c_i, [c_p, c_i64, c_p, c_i, c_p]),
     "sv_vc_object_scale": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "sv_vc_metrics_columns": (c_i, []),
+    "sv_vc_metrics_tile": (c_i, []),
+    "sv_vc_metrics_objects": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    "sv_vc_metrics_levels": (c_i, [c_p, c_p, c_i, c_p, c_p]),
 }
 
 _lib = None

@@ -62,7 +62,8 @@ __device__ __forceinline__ bool seg_x(P2 p1, P2 p0, P2 q1, P2 q0, P2& ans) {
   return true;
 }
 
-__device__ inline float overlap_area(const RBox& a, const RBox& b) {
+// pts, ang: room for 24 polygon points and their angles, the caller's (private arrays, or LDS where a kernel must stay without scratch)
+__device__ inline float overlap_area_in(const RBox& a, const RBox& b, P2* pts, float* ang) {
   // pairs whose bounding circles (+ the 1e-2 corner margin, + slack) are apart have no crossing and no corner inside:
   // the construction below would return exactly 0
   {
@@ -73,8 +74,6 @@ __device__ inline float overlap_area(const RBox& a, const RBox& b) {
   P2 A[5], B[5];
   corners(a, A);
   corners(b, B);
-  P2 pts[24];
-  float ang[24];
   int cnt = 0;
   float sx = 0.f, sy = 0.f;
   for (int i = 0; i < 4; ++i)
@@ -99,6 +98,12 @@ __device__ inline float overlap_area(const RBox& a, const RBox& b) {
   for (int k = 0; k < cnt - 1; ++k)
     area += (pts[k].x - pts[0].x) * (pts[k + 1].y - pts[0].y) - (pts[k].y - pts[0].y) * (pts[k + 1].x - pts[0].x);
   return fabsf(area) / 2.0f;
+}
+
+__device__ inline float overlap_area(const RBox& a, const RBox& b) {
+  P2 pts[24];
+  float ang[24];
+  return overlap_area_in(a, b, pts, ang);
 }
 
 __device__ __forceinline__ float iou_bev(const RBox& a, const RBox& b) {

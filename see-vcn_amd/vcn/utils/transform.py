@@ -41,3 +41,12 @@ def restore_scale(points, gt_label):
     """multiply by the box length (transform.py:153-165)."""
     assert gt_label.shape[1] == 7 and points.shape[2] == 3
     return points * gt_label[:, 3].view(-1, 1, 1)
+
+
+def rotm_to_heading(R):
+    """(B,3,3) -> (B) heading in [-pi, pi] (transform.py:163-187).  The reference rotates (1, 0, 0) by R and takes atan2 of the z component of
+    its cross product with (1, 0, 0) and of its dot product, both over the norms: that is atan2 of row 0's normalised y and x."""
+    assert len(R.shape) == 3, f'Shape (B,3,3) expected. Instead received {R.shape}.'
+    v = R[:, 0, :]
+    norm = torch.linalg.norm(v, dim=1)
+    return torch.atan2(v[:, 1] / norm, v[:, 0] / norm)
