@@ -41,7 +41,7 @@ struct WideCode {
 // ------------------------------------------------------------------------------------------------ decode
 template <class Code>
 __global__ __launch_bounds__(256) void k_anchor_decode(int64_t total, int64_t A, const float* __restrict__ anchors, const float* __restrict__ enc,
-                                                       const float* __restrict__ dir_logits, int num_bins, float dir_offset,
+                                                       const float* __restrict__ dir_logits, int num_bins, float period, float dir_offset,
                                                        float dir_limit_offset, float* __restrict__ out, Code code) {
   const int bw = 7 + code.E, cw = 7 + code.sincos + code.E;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -63,7 +63,6 @@ __global__ __launch_bounds__(256) void k_anchor_decode(int64_t total, int64_t A,
       float best = d[0];
       for (int k = 1; k < num_bins; ++k)
         if (d[k] > best) { best = d[k]; lab = k; }               // first maximum, like torch.max(dim=-1)[1] on ties
-      const float period = 2.0f * PI_F / (float)num_bins;
       const float val = rg - dir_offset;
       const float rot = val - floorf(val / period + dir_limit_offset) * period;   // limit_period
       rg = rot + dir_offset + period * (float)lab;
@@ -80,8 +79,11 @@ static int anchor_decode(const char* who, Code code, const float* anchors, int64
   const int64_t total = num_anchors * batch;
   if (total == 0) return SV_OK;
   SV_CHECK_ARG(anchors && box_encodings && out && (!dir_cls_preds || num_dir_bins >= 1), "%s: null pointer", who);
+  // the reference's period is the double 2 pi / num_bins rounded to fp32 (anchor_head_template.py:262-266); 2.0f * PI_F / num_bins in fp32 is one
+  // ulp off it for 9 and 11 bins, which moves the floor of limit_period for headings on a bin boundary
+  const float period = dir_cls_preds ? (float)(2.0 * 3.14159265358979323846 / (double)num_dir_bins) : 0.f;
   hipLaunchKernelGGL(k_anchor_decode<Code>, dim3(sv_grid_1d(total, 256)), dim3(256), 0, sv_stream(stream), total, num_anchors, anchors, box_encodings,
-                     dir_cls_preds, num_dir_bins, dir_offset, dir_limit_offset, out, code);
+                     dir_cls_preds, num_dir_bins, period, dir_offset, dir_limit_offset, out, code);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -739,6 +741,8 @@ __global__ __launch_bounds__(256) void k_weighted_smooth_l1(int64_t total, int C
   }
 }
 
+// beta < 1e-5f selects |diff| (WeightedL1Loss).  The reference decides `beta < 1e-5` on a Python double; a double just below 1e-5 rounds onto 1e-5f,
+// so a caller that holds beta as a double decides the L1 case itself and passes 0 (as loss_utils.WeightedSmoothL1Loss does).
 extern "C" int sv_weighted_smooth_l1_loss(const float* input, const float* target, const float* code_weights, const float* weights, int64_t n_rows,
                                           int num_codes, float beta, const float* grad_out, float* out, void* stream) {
   SV_CHECK_ARG(n_rows >= 0 && num_codes > 0, "weighted_smooth_l1_loss: bad sizes");

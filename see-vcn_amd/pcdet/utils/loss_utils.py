@@ -114,7 +114,9 @@ class WeightedSmoothL1Loss(nn.Module):
                 and (self.code_weights is None or self.code_weights.numel() == input.shape[-1])):
             if self.code_weights is not None and self.code_weights.device != input.device:
                 self.code_weights = self.code_weights.to(input.device)
-            return _SmoothL1Function.apply(input, target, self.code_weights, weights, self.beta)
+            # `beta < 1e-5` is decided here, on the Python double as in smooth_l1_loss below: the kernel compares the fp32 beta with 1e-5f, and a
+            # beta just below 1e-5 (float32(1e-5) given as a double, say) rounds onto it.  0 selects |diff| in the kernel
+            return _SmoothL1Function.apply(input, target, self.code_weights, weights, 0.0 if self.beta < 1e-5 else self.beta)
         target = torch.where(torch.isnan(target), input, target)  # ignore nan targets
         diff = input - target
         if self.code_weights is not None:
