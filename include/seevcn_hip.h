@@ -1157,6 +1157,47 @@ int sv_focal_backward(const float* g, const float* f, const float* s, const int3
                       const int32_t* row_of_in, const float* w, const int32_t* cnt, int64_t n, int channels, int mask_multi, int skip_mask_kernel,
                       double threshold, float* dots, float* grad_f, float* grad_s, void* stream);
 
+/* ---- Focal sparse convolution, image branch: FocalSparseConv.construct_multimodal_features (focal_sparse_conv.py:50-113), which the reference runs
+ * per scene with the projection on the host (`.cpu().numpy()` at :92, Calibration.lidar_to_img, detector3d/pcdet/utils/calibration_kitti.py:65-93) and
+ * a (B, C, H, W) map from F.interpolate (:69-70).  coords (n, 4) int32 [b, z, y, x], 16-byte aligned; rows of a scene need not be contiguous.
+ *
+ * Pixels -- :62-64, :82-96: pix (n) int32 = v * W + u of the voxel's projection into its scene's (H, W) image, -1 when it falls outside (or b is
+ * not in [0, batch)).  voxel_size_host / origin_host: the layer's z-first voxel_size and point_cloud_range[:3], 3 floats each on the host.
+ * calib (batch, 24) fp32 on the device: M = np.dot(V2C.T, R0.T) (4 x 3, row-major; formed on the host in float32 as lidar_to_rect forms it), then P2
+ * (3 x 4, row-major).  aug (batch, 4) fp32 on the device: noise_scale, noise_rot, flip_x, flip_y (non-zero = flipped); 1, 0, 0, 0 stand in for keys
+ * the batch does not carry.  Per row in fp32, statement for statement:
+ *     (z, y, x) = (idx * voxel_stride) * voxel_size + origin            the integer product first
+ *     (x, y, z) /= noise_scale                                           :84
+ *     (x, y, z) = [x y z] @ [[c s 0] [-s c 0] [0 0 1]], c = cosf(-noise_rot), s = sinf(-noise_rot)      :86, rotate_points_along_z
+ *     y = -y under flip_x, x = -x under flip_y                           :88, :90 (the reference's z-first columns 1 and 2)
+ *     rect = [x y z 1] @ M;  p = [rect 1] @ P2^T;  u = p0 / rect_z,  v = p1 / rect_z      the divisor is the rect depth, as rect_to_img's
+ *     u, v truncated toward zero (.long()); kept iff 0 <= u < W and 0 <= v < H            :94-96
+ * Every sum runs in ascending term order with one fp32 rounding per operation and no FMA contraction (numpy's BLAS and torch's matmul leave their
+ * order open).  As in the reference there is no depth test: a voxel behind the camera that projects into the image keeps its pixel, and u in (-1, 0)
+ * truncates to 0 and counts as inside.  A non-finite u or v gives -1 (the reference leaves that cast undefined). */
+int sv_focal_image_pixels(const int32_t* coords, int64_t n, int batch, int voxel_stride, const float* voxel_size_host, const float* origin_host,
+                          const float* calib, const float* aug, int H, int W, int32_t* pix, void* stream);
+/* Fused rows -- :69-70, :102-108.  features (batch, h, w, C): the storage of a channels_last (batch, C, h, w) tensor; f (n, Cv) the voxel features.
+ * mode 0 (concat): out (n, C + Cv) = [img | f]; mode 1 (sum): out (n, Cv) = f + img, C == Cv.  img of row i: zero when pix[i] < 0 (or is not a
+ * pixel of the image); features[b, v, u, :] when (h, w) == (H, W); otherwise what F.interpolate(features, (H, W), mode='bilinear',
+ * align_corners=False) holds at (v, u), read through its four taps.  Per axis src = max(in / out * (dst + 0.5) - 0.5, 0) is the rational
+ * (in * (2 dst + 1) - out) / (2 out): i0 its integer part, i1 = i0 + (i0 < in - 1), l1 the remainder over 2 out rounded to fp32 once, l0 = 1 - l1.
+ * Taps t = 0..3 = (y0,x0), (y0,x1), (y1,x0), (y1,x1), w_t = ly * lx, img = ((f_0 w_0 + f_1 w_1) + f_2 w_2) + f_3 w_3 in fp32.  Nothing of size
+ * batch * C * H * W is allocated.  16-byte accesses along C when C % 4 == 0, Cv % 4 == 0 and features, f and out are 16-byte aligned, else one
+ * float a lane.  Needs H * W < 2^31 and batch * h * w < 2^31. */
+int sv_focal_image_sample(const float* features, int batch, int h, int w, int C, int H, int W, const float* f, int Cv, const int32_t* coords,
+                          const int32_t* pix, int64_t n, int mode, float* out, void* stream);
+/* Its gradient with respect to features (the one with respect to f is a slice or the identity and stays with the caller): no float atomics, a
+ * fixed order, every element of grad_features (batch, h, w, C) written exactly once and the map never cleared beforehand.  grad_out (n, ldg): its
+ * first C columns are the gradient of img (ldg = C + Cv after a concat, C after a sum).  Key 4 * i + t names the low-resolution pixel of tap t of
+ * row i; with (h, w) == (H, W) key i names row i's pixel; rows without a pixel have no keys.  One wave per pixel walks its keys in ascending order
+ * (sv_inv_lists_build): grad_features[pixel, c] = +0.0f + sum of grad_out[i, c] * w_t, every product and every sum rounded to fp32.  n == 0
+ * writes the zero map.  scratch: sv_focal_image_sample_grad_scratch_bytes bytes, uninitialised (0: the sizes exceed the guards).  Needs
+ * batch * h * w < 2^31, H * W < 2^31 and 4 * n < 2^31. */
+size_t sv_focal_image_sample_grad_scratch_bytes(int64_t n, int batch, int h, int w, int H, int W);
+int sv_focal_image_sample_grad(const float* grad_out, int ldg, const int32_t* coords, const int32_t* pix, int64_t n, int batch, int h, int w, int C,
+                               int H, int W, void* scratch, float* grad_features, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (detector3d/pcdet/datasets/kitti/kitti_object_eval_python/eval.py, rotate_iou.py).  All arrays are device memory.  Frame f
  * owns detections [dt_off[f], dt_off[f+1]) and ground truths [gt_off[f], gt_off[f+1]); its (n_dt_f, n_gt_f) overlap block starts at

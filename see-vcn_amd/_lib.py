@@ -245,6 +245,10 @@ SIGNATURES = {
     "sv_focal_expand": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_d, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "sv_focal_place": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_d, c_i64, c_p, c_p, c_p, c_p]),
     "sv_focal_backward": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p]),
+    "sv_focal_image_pixels": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "sv_focal_image_sample": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
+    "sv_focal_image_sample_grad_scratch_bytes": (c_sz, [c_i64, c_i, c_i, c_i, c_i, c_i]),
+    "sv_focal_image_sample_grad": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "sv_kitti_eval_max_detections": (c_i, []),
     "sv_kitti_overlaps": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_p, c_p]),
     "sv_kitti_match_scores": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_p]),

@@ -494,3 +494,15 @@ class BatchDataAugmentor:
         out = A.compact(batch, **(dp.tail_args() if dp is not None else {}))
         out["draws"] = all_draws
         return out
+
+
+def world_draws_to_batch(draws, device=None):
+    """The per-scene tensors the focal image branch reads from batch_dict to take the world transforms back (reference data_augmentor.py sets
+    'flip_x' / 'flip_y', 'noise_rot', 'noise_scale' beside the points): {'noise_scale', 'noise_rot' (B,) fp32, 'flip_x', 'flip_y' (B,) bool} from
+    out["draws"] of BatchDataAugmentor.forward.  A draw the queue does not make is the identity (1, 0, False); one upload per tensor, no read."""
+    def column(name, identity):
+        return [next((value for key, value in scene if key == name), identity) for scene in draws]
+    return {"noise_scale": torch.tensor(column("scaling", 1.0), dtype=torch.float32, device=device),
+            "noise_rot": torch.tensor(column("rotation", 0.0), dtype=torch.float32, device=device),
+            "flip_x": torch.tensor(column("flip_x", False), dtype=torch.bool, device=device),
+            "flip_y": torch.tensor(column("flip_y", False), dtype=torch.bool, device=device)}

@@ -155,12 +155,14 @@ def voxelrcnn_model_cfg(dynamic_vfe=False, **kw):
                 ROI_HEAD=voxelrcnn_cfg(**kw), POST_PROCESSING=pp)
 
 
-def voxelrcnn_focal_model_cfg(dynamic_vfe=False, backbone=None, **kw):
-    """MODEL section of kitti_models/voxel_rcnn_car_focal_multimodal.yaml (:37-187): voxel_rcnn_car.yaml with BACKBONE_3D VoxelBackBone8xFocal, restated with
-    USE_IMG: False (the image branch is not built; the yaml's IMG_PRETRAIN belongs to it).  backbone: further BACKBONE_3D keys (TOPK, THRESHOLD,
-    MASK_MULTI, SKIP_MASK_KERNEL, ENLARGE_VOXEL_CHANNELS, last_pad); the yaml leaves them at the class defaults."""
+def voxelrcnn_focal_model_cfg(dynamic_vfe=False, backbone=None, use_img=False, img_pretrain="../checkpoints/deeplabv3_resnet50_coco-cd0a2569.pth", **kw):
+    """MODEL section of kitti_models/voxel_rcnn_car_focal_multimodal.yaml (:37-187): voxel_rcnn_car.yaml with BACKBONE_3D VoxelBackBone8xFocal.  The yaml
+    sets USE_IMG: True with IMG_PRETRAIN at the checkpoint the reference downloads; use_img=True restates that (img_pretrain: a local file, or None
+    for a randomly initialised image network), the default leaves the image branch out.  backbone: further BACKBONE_3D keys (TOPK, THRESHOLD,
+    MASK_MULTI, SKIP_MASK_KERNEL, SKIP_MASK_KERNEL_IMG, ENLARGE_VOXEL_CHANNELS, last_pad); the yaml leaves them at the class defaults."""
     cfg = voxelrcnn_model_cfg(dynamic_vfe=dynamic_vfe, **kw)
-    cfg['BACKBONE_3D'] = dict(NAME='VoxelBackBone8xFocal', USE_IMG=False, **(backbone or {}))
+    image = dict(USE_IMG=True, IMG_PRETRAIN=img_pretrain) if use_img else dict(USE_IMG=False)
+    cfg['BACKBONE_3D'] = dict(NAME='VoxelBackBone8xFocal', **image, **(backbone or {}))
     return cfg
 
 

@@ -1,6 +1,7 @@
 """Focal sparse convolution's expansion of the active set (csrc/focal_conv.hip): host wrappers over the sv_focal_* entries and the autograd
 Function the FocalSparseConv module calls.  Replaces split_voxels / check_repeat / combine_out of the reference
-(detector3d/pcdet/models/backbones_3d/focal_sparse_conv/focal_sparse_utils.py:39-147, focal_sparse_conv.py:171-197)."""
+(detector3d/pcdet/models/backbones_3d/focal_sparse_conv/focal_sparse_utils.py:39-147, focal_sparse_conv.py:171-197).  Below them the image branch
+(csrc/focal_image.hip): the pixels of the projected voxels and the fused [image | voxel] rows of construct_multimodal_features (focal_sparse_conv.py:50-113)."""
 import ctypes
 
 import torch
@@ -119,3 +120,82 @@ def focal_expand(x, s, nbr, topk=False, threshold=0.5, mask_multi=False, skip_ma
     out, out_indices, fore, row_of_in = FocalExpandFunction.apply(x.features, s, x.indices, nbr, x.batch_size, x.spatial_shape, topk, threshold,
                                                                   mask_multi, skip_mask_kernel, capacity)
     return SparseConvTensor(out, out_indices, x.spatial_shape, x.batch_size, x.grid, x.indice_dict), fore, row_of_in
+
+
+# ---- the image branch (csrc/focal_image.hip): FocalSparseConv.construct_multimodal_features, focal_sparse_conv.py:50-113 ----
+def image_aug_table(batch_dict, batch_size, device):
+    """(B, 4) fp32 [noise_scale, noise_rot, flip_x, flip_y] from the keys the batch carries (focal_sparse_conv.py:83-90); identity values stand in
+    for absent keys.  Device tensors stay on the device: no read."""
+    identity = (1.0, 0.0, 0.0, 0.0)
+    cols = []
+    for key, fill in zip(('noise_scale', 'noise_rot', 'flip_x', 'flip_y'), identity):
+        if key in batch_dict:
+            cols.append(torch.as_tensor(batch_dict[key]).to(device=device, dtype=torch.float32).reshape(batch_size))
+        else:
+            cols.append(torch.full((batch_size,), fill, dtype=torch.float32, device=device))
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def focal_image_pixels(indices, batch_size, voxel_stride, voxel_size, origin, calib_table, aug_table, image_hw):
+    """pix (n) int32 = v * W + u of every row's projection into its scene's image, -1 outside (sv_focal_image_pixels).  voxel_size / origin: the
+    layer's z-first host values; calib_table (B, 24), aug_table (B, 4) fp32 on the device.  No host read."""
+    lib = _lib.load()
+    _lib.require_cuda(indices, calib_table, aug_table)
+    assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4, "indices: (n, 4) int32 [b, z, y, x]"
+    assert calib_table.dtype == torch.float32 and calib_table.shape == (batch_size, 24), "calib_table: (B, 24) fp32 = [V2C^T R0^T (4 x 3) | P2 (3 x 4)]"
+    assert aug_table.dtype == torch.float32 and aug_table.shape == (batch_size, 4), "aug_table: (B, 4) fp32"
+    indices = indices.contiguous()
+    n = indices.shape[0]
+    pix = torch.empty((n,), dtype=torch.int32, device=indices.device)
+    vs = _lib.host_array(ctypes.c_float, [float(v) for v in voxel_size])
+    org = _lib.host_array(ctypes.c_float, [float(v) for v in origin])
+    _lib.check(lib.sv_focal_image_pixels(_lib.ptr(indices), n, int(batch_size), int(voxel_stride), vs, org, _lib.ptr(calib_table.contiguous()),
+                                         _lib.ptr(aug_table.contiguous()), int(image_hw[0]), int(image_hw[1]), _lib.ptr(pix), _lib.stream()),
+               "sv_focal_image_pixels")
+    return pix
+
+
+class FocalImageSampleFunction(torch.autograd.Function):
+    """(f (n, Cv), image features (B, h, w, C) channel-last) -> [img | f] (n, C + Cv), or f + img (n, Cv) under fuse_sum, where img is the row of
+    the features bilinearly up-sampled to image_hw at the row's pixel (sv_focal_image_sample).  indices and pix are constant.  The gradient into
+    the features is sv_focal_image_sample_grad: per-pixel lists in ascending key order, no float atomics, equal bits run to run."""
+
+    @staticmethod
+    def forward(ctx, f, features, indices, pix, image_hw, fuse_sum):
+        lib = _lib.load()
+        _lib.require_cuda(f, features, indices, pix)
+        f, features, indices, pix = f.contiguous().float(), features.contiguous().float(), indices.contiguous(), pix.contiguous()
+        (n, Cv), (B, h, w, C) = f.shape, features.shape
+        assert indices.dtype == torch.int32 and indices.shape == (n, 4) and pix.dtype == torch.int32 and pix.shape == (n,)
+        mode = int(bool(fuse_sum))
+        H, W = int(image_hw[0]), int(image_hw[1])
+        out = torch.empty((n, Cv if mode else C + Cv), dtype=torch.float32, device=f.device)
+        _lib.check(lib.sv_focal_image_sample(_lib.ptr(features), B, h, w, C, H, W, _lib.ptr(f), Cv, _lib.ptr(indices), _lib.ptr(pix), n, mode,
+                                             _lib.ptr(out), _lib.stream()), "sv_focal_image_sample")
+        ctx.save_for_backward(indices, pix)
+        ctx.geom = (B, h, w, C, H, W, Cv, mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        indices, pix = ctx.saved_tensors
+        B, h, w, C, H, W, Cv, mode = ctx.geom
+        n = indices.shape[0]
+        g = grad_out.contiguous().float()
+        grad_f = (g if mode else g[:, C:]) if ctx.needs_input_grad[0] else None
+        grad_features = None
+        if ctx.needs_input_grad[1]:
+            nbytes = lib.sv_focal_image_sample_grad_scratch_bytes(n, B, h, w, H, W)
+            if nbytes == 0:
+                raise _lib.SeevcnHipError("sv_focal_image_sample_grad: pixel index or tap key exceeds int32")
+            scratch = _lib.workspace.scratch("focal_image_grad", nbytes, g.device)
+            grad_features = torch.empty((B, h, w, C), dtype=torch.float32, device=g.device)
+            _lib.check(lib.sv_focal_image_sample_grad(_lib.ptr(g), g.shape[1], _lib.ptr(indices), _lib.ptr(pix), n, B, h, w, C, H, W, _lib.ptr(scratch),
+                                                      _lib.ptr(grad_features), _lib.stream()), "sv_focal_image_sample_grad")
+        return grad_f, grad_features, None, None, None, None
+
+
+def focal_image_fuse(f, features_nhwc, indices, pix, image_hw, fuse_sum=False):
+    """The fused rows of construct_multimodal_features for rows `indices` whose pixels are `pix` (focal_image_pixels)."""
+    return FocalImageSampleFunction.apply(f, features_nhwc, indices, pix, image_hw, fuse_sum)
