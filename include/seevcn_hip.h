@@ -1497,6 +1497,49 @@ int sv_vc_metrics_objects(const float* coarse, const float* complete, const floa
                           int batch, int n, int m, float* table, void* stream);
 int sv_vc_metrics_levels(const float* table, const int32_t* num_pts, int batch, float* out, void* stream);
 
+/* ---- optimizer step (csrc/optim.hip): the parameter update of every detector config and of the VCN.  Replaces, per train step,
+ * detector3d/tools/train_utils/train_utils.py:53-54 (clip_grad_norm_, optimizer.step()), the per-parameter p.data.mul_(1 - wd*lr) loops of
+ * detector3d/tools/train_utils/optimization/fastai_optim.py:135-152 and torch.optim.Adam / AdamW as built by
+ * detector3d/tools/train_utils/optimization/__init__.py:11-36 and see/surface_completion/models/vcn/tools/builder.py:49-58.
+ * The kernels run over a chunk table on the device: `chunks` is nchunks records of sv_optim_chunk_bytes() == 48 bytes,
+ *    { float* p, g, m, v;  int32 n, tensor, group, pad }
+ * one per slice of at most sv_optim_chunk_elems() == SV_OPTIM_CHUNK consecutive elements of one fp32 tensor that has a gradient (parameter,
+ * gradient, exp_avg, exp_avg_sq at the slice, its element count, the tensor's index into t / tensor_scal, its parameter group).  A tensor
+ * without a gradient has no record and is not touched: no decay, no state change, no advance of t (torch skips .grad is None).
+ * sv_optim_grad_sqnorm (clip_grad_norm_'s norms): partials[c] = sum of g*g over chunk c in float64, one workgroup of 256 a chunk, no atomics.
+ * Thread t adds the exact float64 squares of elements 4i .. 4i+3, i = t, t + 256, ..., ascending, to one accumulator (the n % 4 last elements
+ * go to the thread whose group they would complete); xor butterfly over the wave (32 .. 1); the four wave totals in ascending order.  The
+ * order does not depend on the gradient's alignment.
+ * sv_optim_adam_step: two launches.  (1) one workgroup: the partials in ascending chunk order in float64, in 256 blocks (thread j adds partials
+ * [j B, (j + 1) B), B = ceil(nchunks / 256), ascending; thread 0 adds the 256 block sums, ascending) give total,
+ * total_norm = fp32(sqrt(total)), clip = min(1, max_norm / (total_norm + 1e-6f)) in fp32 (a NaN stays NaN, as torch.clamp keeps it);
+ * partials == null or max_norm <= 0: no clipping, total_norm = 0, clip = 1.  For each of the npresent (tensor, group) int32 pairs of `present`:
+ * t[tensor] += 1, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in float64 with the group's CURRENT betas (torch's semantics under a schedule that
+ * moves beta1), tensor_scal[2 tensor] = {step = fp32(lr / bc1), rbc2 = fp32(sqrt(bc2))}.  (2) one workgroup a chunk, per element in fp32,
+ * every operation rounded once:
+ *      g = grad * clip
+ *      g = g + wd * p                        mode SV_OPTIM_L2 (OPTIMIZER: adam)
+ *      p = p * decay                         mode SV_OPTIM_DECOUPLED (true_wd / AdamW), decay = fp32(1 - lr * wd) from float64
+ *      m = b1 * m + omb1 * g                 b1 = fp32(beta1), omb1 = fp32(1 - beta1), likewise b2, omb2
+ *      v = b2 * v + (omb2 * g) * g
+ *      p = p - (step * m) / (sqrt(v) / rbc2 + eps)
+ * consume != 0 stores zeros over the gradient it has read.  dwordx4 loads and stores where all four pointers of a chunk are 16-byte aligned
+ * (then only a tensor's last chunk has a scalar tail of n % 4); a chunk with any pointer off a 16-byte boundary takes coalesced dwords
+ * throughout.  Nothing outside [0, n) of a slice is read or written.
+ * groups: ngroups x 6 float64 ON THE HOST, {lr, beta1, beta2, eps, wd, mode}, passed on to the kernels by value; 1 <= ngroups <=
+ * SV_OPTIM_MAX_GROUPS.  norm_out (2) fp32 on the device: total_norm, clip.  t (tensors) int32, tensor_scal (2 x tensors) fp32.  No host read. */
+#define SV_OPTIM_CHUNK 4096
+#define SV_OPTIM_MAX_GROUPS 16
+#define SV_OPTIM_NO_DECAY 0
+#define SV_OPTIM_L2 1
+#define SV_OPTIM_DECOUPLED 2
+int sv_optim_chunk_elems(void);
+int sv_optim_chunk_bytes(void);
+int sv_optim_max_groups(void);
+int sv_optim_grad_sqnorm(const void* chunks, int nchunks, double* partials, void* stream);
+int sv_optim_adam_step(const void* chunks, int nchunks, const int32_t* present, int npresent, const double* groups, int ngroups,
+                       const double* partials, float max_norm, int consume, int32_t* t, float* tensor_scal, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -294,6 +294,11 @@ SIGNATURES = {
     "sv_vc_metrics_tile": (c_i, []),
     "sv_vc_metrics_objects": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "sv_vc_metrics_levels": (c_i, [c_p, c_p, c_i, c_p, c_p]),
+    "sv_optim_chunk_elems": (c_i, []),
+    "sv_optim_chunk_bytes": (c_i, []),
+    "sv_optim_max_groups": (c_i, []),
+    "sv_optim_grad_sqnorm": (c_i, [c_p, c_i, c_p, c_p]),
+    "sv_optim_adam_step": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_f, c_i, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None
