@@ -31,19 +31,19 @@ def _gemm_nt(a, w, bias, act, slope, group_bias=None, rows_per_group=1):
     if M == 0:
         return out
     if K == 3 and group_bias is None and N % 4 == 0:
-        _lib.check(lib.sv_pointwise_conv3(_lib.ptr(a), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), M, N, int(act), float(slope), _lib.stream()), "sv_pointwise_conv3")
+        _lib.launch("sv_pointwise_conv3", _lib.ptr(a), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), M, N, int(act), float(slope))
         return out
     if K % 32 == 0 and lib.sv_gemm_splitk_splits(M, N, K) > 1:             # few output tiles, long K (the 27 648 -> 256 layer of PV-RCNN's RoI head)
         sc = _scratch("dense_splitk", lib.sv_gemm_splitk_scratch_bytes(M, N, K), a.device)
-        _lib.check(lib.sv_gemm_bias_act_splitk(_lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group), _lib.ptr(out), N, M, N, K,
-                                               int(act), float(slope), _lib.ptr(sc), _lib.stream()), "sv_gemm_bias_act_splitk")
+        _lib.launch("sv_gemm_bias_act_splitk", _lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group), _lib.ptr(out), N, M,
+                    N, K, int(act), float(slope), _lib.ptr(sc))
         return out
     if K % 32 == 0:
-        _lib.check(lib.sv_gemm_bias_act(_lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group), _lib.ptr(out), N, None, M, N, K,
-                                        int(act), float(slope), _lib.stream()), "sv_gemm_bias_act")
+        _lib.launch("sv_gemm_bias_act", _lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group), _lib.ptr(out), N, None, M, N,
+                    K, int(act), float(slope))
         return out
     sc = _scratch("dense_sg", lib.sv_gemm_strided_scratch_bytes(M, N, K), a.device)
-    _lib.check(lib.sv_gemm_strided(_lib.ptr(a), K, 1, _lib.ptr(w), 1, K, _lib.ptr(out), N, M, N, K, _lib.ptr(sc), _lib.stream()), "sv_gemm_strided")
+    _lib.launch("sv_gemm_strided", _lib.ptr(a), K, 1, _lib.ptr(w), 1, K, _lib.ptr(out), N, M, N, K, _lib.ptr(sc))
     if bias is not None:
         out += bias
     if group_bias is not None:
@@ -77,7 +77,7 @@ class _Linear(torch.autograd.Function):
         dz = dy.contiguous().float()
         if ctx.act != ACT_NONE:
             out = torch.empty_like(dz)
-            _lib.check(lib.sv_act_backward(_lib.ptr(dz), _lib.ptr(y), dz.numel(), ctx.act, ctx.slope, _lib.ptr(out), _lib.stream()), "sv_act_backward")
+            _lib.launch("sv_act_backward", _lib.ptr(dz), _lib.ptr(y), dz.numel(), ctx.act, ctx.slope, _lib.ptr(out))
             dz = out
         dx = dw = db = dgb = None
         if ctx.needs_input_grad[0]:
@@ -87,19 +87,19 @@ class _Linear(torch.autograd.Function):
             else:
                 dx = torch.empty((M, K), dtype=torch.float32, device=dev)
                 sc = _scratch("dense_sg", lib.sv_gemm_strided_scratch_bytes(M, K, N), dev)
-                _lib.check(lib.sv_gemm_strided(_lib.ptr(dz), N, 1, _lib.ptr(w), K, 1, _lib.ptr(dx), K, M, K, N, _lib.ptr(sc), _lib.stream()), "sv_gemm_strided")
+                _lib.launch("sv_gemm_strided", _lib.ptr(dz), N, 1, _lib.ptr(w), K, 1, _lib.ptr(dx), K, M, K, N, _lib.ptr(sc))
         if ctx.needs_input_grad[1]:
             dw = torch.empty((N, K), dtype=torch.float32, device=dev)
             sc = _scratch("dense_tn", lib.sv_gemm_tn_scratch_bytes(M, N, K), dev)
-            _lib.check(lib.sv_gemm_tn(_lib.ptr(dz), N, _lib.ptr(x), K, _lib.ptr(dw), K, M, N, K, _lib.ptr(sc), _lib.stream()), "sv_gemm_tn")
+            _lib.launch("sv_gemm_tn", _lib.ptr(dz), N, _lib.ptr(x), K, _lib.ptr(dw), K, M, N, K, _lib.ptr(sc))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty((N,), dtype=torch.float32, device=dev)
             sc = _scratch("dense_cs", lib.sv_column_sums_scratch_bytes(M, N), dev)
-            _lib.check(lib.sv_column_sums(_lib.ptr(dz), N, M, N, _lib.ptr(db), _lib.ptr(sc), _lib.stream()), "sv_column_sums")
+            _lib.launch("sv_column_sums", _lib.ptr(dz), N, M, N, _lib.ptr(db), _lib.ptr(sc))
         if ctx.has_gb and ctx.needs_input_grad[5]:
             groups = M // ctx.rows_per_group
             dgb = torch.empty((groups, N), dtype=torch.float32, device=dev)
-            _lib.check(lib.sv_segment_sum(_lib.ptr(dz), N, groups, ctx.rows_per_group, N, _lib.ptr(dgb), _lib.stream()), "sv_segment_sum")
+            _lib.launch("sv_segment_sum", _lib.ptr(dz), N, groups, ctx.rows_per_group, N, _lib.ptr(dgb))
         return dx, dw, db, None, None, dgb, None
 
 
@@ -114,14 +114,12 @@ def linear(x, weight, bias=None, act=ACT_NONE, slope=0.01, group_bias=None, rows
 class _SegmentMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rows_per_group):
-        lib = _lib.load()
-        _lib.require_cuda(x)
         x = x.contiguous().float()
         M, C = x.shape
         groups = M // rows_per_group
         out = torch.empty((groups, C), dtype=torch.float32, device=x.device)
         arg = torch.empty((groups, C), dtype=torch.int32, device=x.device)
-        _lib.check(lib.sv_segment_max(_lib.ptr(x), C, groups, int(rows_per_group), C, _lib.ptr(out), _lib.ptr(arg), _lib.stream()), "sv_segment_max")
+        _lib.launch("sv_segment_max", _lib.ptr(x), C, groups, int(rows_per_group), C, _lib.ptr(out), _lib.ptr(arg))
         ctx.rows_per_group, ctx.shape = int(rows_per_group), (M, C)
         ctx.save_for_backward(arg)
         ctx.mark_non_differentiable()
@@ -129,12 +127,11 @@ class _SegmentMax(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         (arg,) = ctx.saved_tensors
         M, C = ctx.shape
         dx = torch.empty((M, C), dtype=torch.float32, device=dout.device)
-        _lib.check(lib.sv_segment_max_backward(_lib.ptr(dout.contiguous().float()), _lib.ptr(arg), M // ctx.rows_per_group, ctx.rows_per_group, C, _lib.ptr(dx), C,
-                                               _lib.stream()), "sv_segment_max_backward")
+        _lib.launch("sv_segment_max_backward", _lib.ptr(dout.contiguous().float()), _lib.ptr(arg), M // ctx.rows_per_group, ctx.rows_per_group, C, _lib.ptr(dx),
+                    C)
         return dx, None
 
 

@@ -185,15 +185,13 @@ class FusedAdam(torch.optim.Optimizer):
         if key != self._key:
             self._rebuild(key)
         groups = self._group_scalars(decay_override)
-        lib, st = self._lib, _lib.stream()
         max_norm = self.max_grad_norm
         clipped = max_norm is not None and max_norm > 0 and self._nchunks > 0
         if clipped:
-            _lib.check(lib.sv_optim_grad_sqnorm(self._table, self._nchunks, self._partials.data_ptr(), st), "sv_optim_grad_sqnorm")
-        _lib.check(lib.sv_optim_adam_step(self._table, self._nchunks, self._present, self._npresent, groups, len(self.param_groups),
-                                          self._partials.data_ptr() if clipped else None, float(max_norm) if clipped else 0.0,
-                                          int(self.consume_grads), self._t.data_ptr(), self._tensor_scal.data_ptr(), self._norm_out.data_ptr(), st),
-                   "sv_optim_adam_step")
+            _lib.launch("sv_optim_grad_sqnorm", self._table, self._nchunks, self._partials.data_ptr())
+        _lib.launch("sv_optim_adam_step", self._table, self._nchunks, self._present, self._npresent, groups, len(self.param_groups),
+                    self._partials.data_ptr() if clipped else None, float(max_norm) if clipped else 0.0,
+                    int(self.consume_grads), self._t.data_ptr(), self._tensor_scal.data_ptr(), self._norm_out.data_ptr())
         self.last_total_norm = self._norm_out[0] if clipped else None
         self._consumed = self.consume_grads
         return loss

@@ -118,8 +118,8 @@ def _device_f64(values, device):
 def points_in_boxes_count(batch):
     """(N,) int32: the points of its scene inside each box by the CPU matrix test, margin 1e-2 in x / y and none in z (dataset.py:131-133)."""
     counts = torch.empty(max(batch.total_boxes, 1), dtype=torch.int32, device=batch.points.device)
-    call("sv_points_in_boxes_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(),
-         batch.total_boxes, L.ptr(counts), L.stream())
+    call("sv_points_in_boxes_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(), batch.total_boxes,
+         L.ptr(counts))
     return counts[:batch.total_boxes]
 
 
@@ -144,9 +144,9 @@ def scale_pre_object(batch, scale_noises):
         raise ValueError(f"num_try must be in 1..{MAX_NUM_TRY}, got {num_try}")
     before = batch.boxes.clone()
     plan = torch.empty(batch.total_boxes, dtype=torch.float64, device=dev)
-    call("sv_object_scale_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, L.ptr(noises), num_try, L.ptr(plan), L.stream())
+    call("sv_object_scale_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, L.ptr(noises), num_try, L.ptr(plan))
     call("sv_object_scale_points", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, L.ptr(before), batch.box_width,
-         L.ptr(batch.box_start), L.ptr(batch.box_cnt), L.ptr(batch.box_cls), L.ptr(plan), L.stream())
+         L.ptr(batch.box_start), L.ptr(batch.box_cnt), L.ptr(batch.box_cls), L.ptr(plan))
     return plan
 
 
@@ -160,10 +160,9 @@ def world_transform(batch, ops, params, limit_heading=False):
     p = _device_f64(np.zeros((batch.batch_size, 1)) if len(ops) == 0 else params, dev)
     assert len(ops) == 0 or tuple(p.shape) == (batch.batch_size, len(ops))
     if len(ops):
-        call("sv_world_transform_points", *batch._pt_args(), batch.batch_size, batch.max_scene_points, code, len(ops), L.ptr(p), L.stream())
+        call("sv_world_transform_points", *batch._pt_args(), batch.batch_size, batch.max_scene_points, code, len(ops), L.ptr(p))
     if len(ops) or limit_heading:
-        call("sv_world_transform_boxes", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, code, len(ops), L.ptr(p), int(limit_heading),
-             L.stream())
+        call("sv_world_transform_boxes", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, code, len(ops), L.ptr(p), int(limit_heading))
 
 
 def _per_scene(batch, values):
@@ -226,10 +225,9 @@ def local_transform(batch, steps, params):
         code = P.pack_codes(run, "local")
         draws = p if len(run) == len(steps) else p[:, first:first + 16].contiguous()
         plan = torch.empty(len(run) * N * PLAN_ROW, dtype=torch.float32, device=dev)
-        call("sv_local_transform_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, N, code, len(run), L.ptr(draws), L.ptr(plan),
-             L.stream())
+        call("sv_local_transform_plan", *batch._box_args(), L.ptr(batch.box_cls), batch.batch_size, N, code, len(run), L.ptr(draws), L.ptr(plan))
         call("sv_local_transform_points", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, L.ptr(batch.box_start),
-             L.ptr(batch.box_cnt), N, code, len(run), L.ptr(plan), L.stream())
+             L.ptr(batch.box_cnt), N, code, len(run), L.ptr(plan))
 
 
 def _per_box(batch, values):
@@ -295,7 +293,7 @@ def world_frustum_dropout(batch, directions, intensity):
     assert tuple(v.shape) == (B, len(directions))
     scratch = L.workspace.scratch("world_frustum_dropout", max(int(L.load().sv_world_frustum_dropout_scratch_bytes(B, len(directions))), 4), dev)
     call("sv_world_frustum_dropout", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
-         batch.total_boxes, code, len(directions), L.ptr(v), L.ptr(scratch), L.stream())
+         batch.total_boxes, code, len(directions), L.ptr(v), L.ptr(scratch))
 
 
 def global_frustum_dropout_top(batch, intensity):
@@ -348,11 +346,10 @@ def read_checked(batch, t):
 def get_pyramids(boxes):
     """augmentor_utils.py:573-595: boxes (N, W >= 7) fp32 on the device -> (N, 6, 15) fp32, per face the apex (the centre) and the four base corners,
     as boxes_to_corners_3d makes them in float32 (cos / sin: the float64 function rounded once)."""
-    L.require_cuda(boxes)
     assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] >= 7
     boxes = boxes.contiguous()
     out = torch.empty(boxes.shape[0], 6, 15, dtype=torch.float32, device=boxes.device)
-    call("sv_get_pyramids", L.ptr(boxes), int(boxes.shape[1]), int(boxes.shape[0]), L.ptr(out), L.stream())
+    call("sv_get_pyramids", L.ptr(boxes), int(boxes.shape[1]), int(boxes.shape[0]), L.ptr(out))
     return out
 
 
@@ -372,8 +369,8 @@ def points_in_pyramids_mask(batch, face_mask=None, member=False):
     counts = torch.zeros(max(N, 1), 6, dtype=torch.int32, device=dev)
     stride = batch.max_scene_boxes if member else 0
     flags = torch.zeros(max(batch.total_points, 1), max(stride, 1), dtype=torch.uint8, device=dev) if member else None
-    call("sv_pyramid_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
-         N, L.ptr(mask), L.ptr(counts), L.ptr(flags), stride, L.stream())
+    call("sv_pyramid_count", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls), N,
+         L.ptr(mask), L.ptr(counts), L.ptr(flags), stride)
     return (counts[:N], flags[:batch.total_points]) if member else counts[:N]
 
 
@@ -387,8 +384,8 @@ def local_pyramid_dropout(batch, faces, u, dropout_prob):
     np.less_equal(u, float(dropout_prob), out=drop, where=~np.isnan(u))
     if drop.any():
         code = _box_ints(batch, np.where(drop, np.nan_to_num(faces), -1))
-        call("sv_pyramid_dropout", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(),
-             L.ptr(batch.box_cls), L.ptr(code), L.stream())
+        call("sv_pyramid_dropout", *batch._pt_args(), L.ptr(batch.keep), batch.batch_size, batch.max_scene_points, *batch._box_args(), L.ptr(batch.box_cls),
+             L.ptr(code))
     return drop
 
 
@@ -444,8 +441,8 @@ def local_pyramid_sparsify(batch, plan):
     table = _plan_rows(batch, plan, "pyr", 4)
     up = torch.from_numpy(np.concatenate([table.reshape(-1), plan["ranks"].reshape(-1), [0]]).astype(np.int32)).to(batch.points.device)
     keep_in = batch.keep.clone()
-    call("sv_pyramid_sparsify", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width,
-         batch.total_boxes, L.ptr(up[:table.size]), len(table), L.ptr(up[table.size:]), plan["K"], L.ptr(_check_tensor(batch)), L.stream())
+    call("sv_pyramid_sparsify", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width, batch.total_boxes,
+         L.ptr(up[:table.size]), len(table), L.ptr(up[table.size:]), plan["K"], L.ptr(_check_tensor(batch)))
 
 
 def plan_pyramid_swap(counts, left, selected, max_num, rngs=None, faces=None, partners=None):
@@ -502,8 +499,8 @@ def local_pyramid_swap(batch, plan):
     table = _plan_rows(batch, plan, "pairs", 7)
     up = torch.from_numpy(table.reshape(-1).astype(np.int32)).to(batch.points.device)
     keep_in = batch.keep.clone()
-    call("sv_pyramid_swap", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width,
-         batch.total_boxes, L.ptr(up), len(table), L.ptr(_check_tensor(batch)), L.stream())
+    call("sv_pyramid_swap", *batch._pt_args(), L.ptr(keep_in), L.ptr(batch.keep), batch.batch_size, L.ptr(batch.boxes), batch.box_width, batch.total_boxes,
+         L.ptr(up), len(table), L.ptr(_check_tensor(batch)))
 
 
 def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
@@ -518,8 +515,7 @@ def launch_compact(batch, point_range=None, box_range=None, min_num_corners=0):
     pr = None if point_range is None else L.host_array(ctypes.c_double, [float(point_range[i]) for i in (0, 1, 3, 4)])
     br = None if not min_num_corners else L.host_array(ctypes.c_double, [float(v) for v in list(box_range)[:6]])
     call("sv_augment_compact", *batch._pt_args(), L.ptr(batch.keep), B, batch.max_scene_points, pr, *batch._box_args(), L.ptr(batch.box_cls), br,
-         int(min_num_corners), L.ptr(scratch), L.ptr(out_points), L.ptr(out_meta[:B + 1]), L.ptr(out_meta[B + 1:]), L.ptr(gt), gt_stride,
-         L.ptr(box_keep), L.stream())
+         int(min_num_corners), L.ptr(scratch), L.ptr(out_points), L.ptr(out_meta[:B + 1]), L.ptr(out_meta[B + 1:]), L.ptr(gt), gt_stride, L.ptr(box_keep))
     return out_points, out_meta, gt, box_keep
 
 

@@ -132,9 +132,9 @@ class DataBaseSampler:
         o = np.cumsum([0, total, total, B + 1, total + 1, total])
         cand_idx, cand_group, cand_start_d, ptoff_d, dest_d, head_d = [up[o[i]:o[i + 1]] if i < 5 else up[o[5]:] for i in range(6)]
         accept = torch.empty(total, dtype=torch.int32, device=dev)
-        A.call("sv_gt_sample_select", L.ptr(batch.boxes), batch.box_width, L.ptr(batch.box_start), L.ptr(batch.box_cnt), L.ptr(batch.box_cap), L.ptr(batch.box_cls), B,
-               L.ptr(db.boxes), L.ptr(db.class_ids), L.ptr(cand_idx), L.ptr(cand_group), L.ptr(cand_start_d), total, L.ptr(accept), L.stream())
-        A.call("sv_gt_sample_paste", *batch._pt_args(), L.ptr(head_d), L.ptr(batch.keep), B, batch.max_scene_points, L.ptr(db.points),
-               L.ptr(db.offsets), L.ptr(db.boxes), batch.box_width, L.ptr(cand_idx), L.ptr(cand_start_d), L.ptr(ptoff_d), L.ptr(dest_d),
-               L.ptr(accept), total, int(ptoff[-1]), *self.extra_width, L.stream())
+        A.call("sv_gt_sample_select", L.ptr(batch.boxes), batch.box_width, L.ptr(batch.box_start), L.ptr(batch.box_cnt), L.ptr(batch.box_cap),
+               L.ptr(batch.box_cls), B, L.ptr(db.boxes), L.ptr(db.class_ids), L.ptr(cand_idx), L.ptr(cand_group), L.ptr(cand_start_d), total, L.ptr(accept))
+        A.call("sv_gt_sample_paste", *batch._pt_args(), L.ptr(head_d), L.ptr(batch.keep), B, batch.max_scene_points, L.ptr(db.points), L.ptr(db.offsets),
+               L.ptr(db.boxes), batch.box_width, L.ptr(cand_idx), L.ptr(cand_start_d), L.ptr(ptoff_d), L.ptr(dest_d), L.ptr(accept), total, int(ptoff[-1]),
+               *self.extra_width)
         return accept

@@ -136,8 +136,6 @@ def match_on_device(overlaps, dt_off, gt_off, ov_off, dt_scores, ignored_dt, ign
     """Pass 1 -> sort -> thresholds -> pass 2 on device tensors (layouts: include/seevcn_hip.h).  Returns the device tensors
     (table (C, 41, 4) fp64, num_thresholds (C) int32); with detail=True also (sorted true-positive scores (C, total_gt), their counts (C),
     thresholds (C, 41)).  Four library calls, no host read."""
-    L.require_cuda(overlaps, dt_off, gt_off, ov_off, dt_scores, ignored_dt, ignored_gt, combo_cd, min_overlaps, num_valid_gt, dt_bbox, dc_boxes, dc_off,
-                   gt_alpha, dt_alpha)
     dev = overlaps.device
     frames, combos = dt_off.numel() - 1, combo_cd.numel()
     total_dt, total_gt = dt_scores.numel(), ignored_gt.shape[1]
@@ -154,23 +152,21 @@ def match_on_device(overlaps, dt_off, gt_off, ov_off, dt_scores, ignored_dt, ign
             dc_boxes = torch.zeros(1, 4, dtype=torch.float32, device=dev)            # never read: every frame's DontCare run is empty
     if compute_aos:
         assert gt_alpha.dtype == dt_alpha.dtype == torch.float64 and gt_alpha.numel() == total_gt and dt_alpha.numel() == total_dt
-    st = L.stream()
     tp_scores = torch.full((combos, total_gt), float("-inf"), dtype=torch.float64, device=dev)
     tp_count = torch.zeros(combos, dtype=torch.int32, device=dev)
     common = (L.ptr(overlaps), L.ptr(dt_off), L.ptr(gt_off), L.ptr(ov_off), frames, L.ptr(dt_scores), L.ptr(ignored_dt), L.ptr(ignored_gt),
               L.ptr(combo_cd), L.ptr(min_overlaps), combos, total_dt, total_gt)
-    R.call("sv_kitti_match_scores", *common, L.ptr(tp_scores), L.ptr(tp_count), st)
+    R.call("sv_kitti_match_scores", *common, L.ptr(tp_scores), L.ptr(tp_count))
     sorted_scores = torch.sort(tp_scores, dim=1, descending=True).values.contiguous()
     thresholds = torch.zeros(combos, N_SAMPLE_PTS, dtype=torch.float64, device=dev)
     num_thresholds = torch.empty(combos, dtype=torch.int32, device=dev)
-    R.call("sv_kitti_thresholds", L.ptr(sorted_scores), total_gt, L.ptr(tp_count), L.ptr(num_valid_gt), combos, L.ptr(thresholds),
-           L.ptr(num_thresholds), st)
+    R.call("sv_kitti_thresholds", L.ptr(sorted_scores), total_gt, L.ptr(tp_count), L.ptr(num_valid_gt), combos, L.ptr(thresholds), L.ptr(num_thresholds))
     counts = torch.zeros(combos, N_SAMPLE_PTS, 3, dtype=torch.int32, device=dev)
     table = torch.empty(combos, N_SAMPLE_PTS, 4, dtype=torch.float64, device=dev)
     sim_part = torch.empty(frames, combos, N_SAMPLE_PTS, dtype=torch.float64, device=dev) if compute_aos else None
     R.call("sv_kitti_match_stats", *common, L.ptr(thresholds), L.ptr(num_thresholds), int(metric), int(bool(compute_aos)),
-           L.ptr(dt_bbox) if metric == 0 else None, L.ptr(dc_boxes) if metric == 0 else None, L.ptr(dc_off),
-           L.ptr(gt_alpha) if compute_aos else None, L.ptr(dt_alpha) if compute_aos else None, L.ptr(counts), L.ptr(sim_part), L.ptr(table), st)
+           L.ptr(dt_bbox) if metric == 0 else None, L.ptr(dc_boxes) if metric == 0 else None, L.ptr(dc_off), L.ptr(gt_alpha) if compute_aos else None,
+           L.ptr(dt_alpha) if compute_aos else None, L.ptr(counts), L.ptr(sim_part), L.ptr(table))
     if detail:
         return table, num_thresholds, sorted_scores, tp_count, thresholds
     return table, num_thresholds
@@ -188,7 +184,7 @@ def get_thresholds(scores, num_gt, num_sample_pts=41):
     thresholds = torch.zeros(1, N_SAMPLE_PTS, dtype=torch.float64, device=dev)
     n = torch.empty(1, dtype=torch.int32, device=dev)
     sizes = torch.tensor([scores.size, int(num_gt)], dtype=torch.int32, device=dev)          # named: it must outlive the launch
-    R.call("sv_kitti_thresholds", L.ptr(s), scores.size, sizes.data_ptr(), sizes.data_ptr() + 4, 1, L.ptr(thresholds), L.ptr(n), L.stream())
+    R.call("sv_kitti_thresholds", L.ptr(s), scores.size, sizes.data_ptr(), sizes.data_ptr() + 4, 1, L.ptr(thresholds), L.ptr(n))
     out = R.read(torch.cat([thresholds.reshape(-1), n.to(torch.float64)]))
     return out[:int(out[-1])].tolist()
 

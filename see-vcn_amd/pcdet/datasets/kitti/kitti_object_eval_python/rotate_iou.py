@@ -32,7 +32,6 @@ def offsets(counts):
 
 def ragged_overlaps_device(row_boxes, col_boxes, row_off, col_off, out_off, total_pairs, metric, criterion):
     """Device tensors in, the flat fp32 overlap buffer out (block s = (rows_s, cols_s) row-major at out_off[s]).  total_pairs >= 1."""
-    L.require_cuda(row_boxes, col_boxes, row_off, col_off, out_off)
     if metric not in BOX_WIDTH:
         raise ValueError("unknown metric")
     if criterion not in (-1, 0, 1) + ((2,) if metric else ()):
@@ -40,8 +39,8 @@ def ragged_overlaps_device(row_boxes, col_boxes, row_off, col_off, out_off, tota
     assert row_boxes.dtype == col_boxes.dtype == torch.float32 and row_boxes.shape[1] == col_boxes.shape[1] == BOX_WIDTH[metric]
     assert row_off.dtype == col_off.dtype == out_off.dtype == torch.int64 and row_off.numel() == col_off.numel() == out_off.numel() >= 2
     out = torch.empty(int(total_pairs), dtype=torch.float32, device=row_boxes.device)
-    call("sv_kitti_overlaps", L.ptr(row_boxes), L.ptr(col_boxes), L.ptr(row_off), L.ptr(col_off), L.ptr(out_off), row_off.numel() - 1,
-         int(total_pairs), int(metric), int(criterion), L.ptr(out), L.stream())
+    call("sv_kitti_overlaps", L.ptr(row_boxes), L.ptr(col_boxes), L.ptr(row_off), L.ptr(col_off), L.ptr(out_off), row_off.numel() - 1, int(total_pairs),
+         int(metric), int(criterion), L.ptr(out))
     return out
 
 

@@ -23,8 +23,6 @@ class _BevInterp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bev, keypoints, x0, y0, vx, vy, stride):
-        lib = _lib.load()
-        _lib.require_cuda(bev, keypoints)
         kp = keypoints.contiguous().float()
         B, C, H, W = bev.shape
         ctx.nhwc = (BEV_INTERP_NHWC and bev.dtype == torch.float32 and bev.is_contiguous(memory_format=torch.channels_last)
@@ -32,13 +30,11 @@ class _BevInterp(torch.autograd.Function):
         VoxelSetAbstraction.last_bev_layout = 'nhwc' if ctx.nhwc else 'nchw'
         out = torch.empty((kp.shape[0], C), dtype=torch.float32, device=bev.device)
         if ctx.nhwc:
-            rc = lib.sv_bev_interpolate_nhwc(_lib.ptr(kp), kp.shape[0], _lib.ptr(bev.permute(0, 2, 3, 1)), B, C, H, W, x0, y0, vx, vy, float(stride),
-                                             _lib.ptr(out), _lib.stream())
-            _lib.check(rc, "sv_bev_interpolate_nhwc")
+            _lib.launch("sv_bev_interpolate_nhwc", _lib.ptr(kp), kp.shape[0], _lib.ptr(bev.permute(0, 2, 3, 1)), B, C, H, W, x0, y0, vx, vy, float(stride),
+                        _lib.ptr(out))
         else:
             bev = bev.contiguous().float()
-            rc = lib.sv_bev_interpolate(_lib.ptr(kp), kp.shape[0], _lib.ptr(bev), B, C, H, W, x0, y0, vx, vy, float(stride), _lib.ptr(out), _lib.stream())
-            _lib.check(rc, "sv_bev_interpolate")
+            _lib.launch("sv_bev_interpolate", _lib.ptr(kp), kp.shape[0], _lib.ptr(bev), B, C, H, W, x0, y0, vx, vy, float(stride), _lib.ptr(out))
         ctx.save_for_backward(kp)
         ctx.meta = (B, C, H, W, x0, y0, vx, vy, float(stride))
         return out
@@ -53,16 +49,13 @@ class _BevInterp(torch.autograd.Function):
         if ctx.nhwc or ordered.ordered_gradients():           # the channel-last entry sums in a fixed order; the NCHW entry adds with float atomics
             gbev = torch.empty((B, H, W, C), dtype=torch.float32, device=g.device)
             scratch = _lib.workspace.scratch("bev_interp_grad_nhwc", lib.sv_bev_interpolate_grad_nhwc_scratch_bytes(kp.shape[0], B, H, W), g.device)
-            rc = lib.sv_bev_interpolate_grad_nhwc(_lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch),
-                                                  _lib.ptr(gbev), _lib.stream())
-            _lib.check(rc, "sv_bev_interpolate_grad_nhwc")
+            _lib.launch("sv_bev_interpolate_grad_nhwc", _lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch),
+                        _lib.ptr(gbev))
             gbev = gbev.permute(0, 3, 1, 2)                                          # (B, C, H, W) with channels_last strides
             return (gbev if ctx.nhwc else gbev.contiguous()), None, None, None, None, None, None
         gbev = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device)
         scratch = _lib.workspace.scratch("bev_interp_grad", lib.sv_bev_interpolate_grad_scratch_bytes(B, C, H, W), g.device)
-        rc = lib.sv_bev_interpolate_grad(_lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch), _lib.ptr(gbev),
-                                         _lib.stream())
-        _lib.check(rc, "sv_bev_interpolate_grad")
+        _lib.launch("sv_bev_interpolate_grad", _lib.ptr(kp), kp.shape[0], _lib.ptr(g), B, C, H, W, x0, y0, vx, vy, stride, _lib.ptr(scratch), _lib.ptr(gbev))
         return gbev, None, None, None, None, None, None
 
 

@@ -162,7 +162,6 @@ class AnchorHeadTemplate(nn.Module):
         """cls_preds (N,H,W,C1), box_preds (N,H,W,C2), dir_cls_preds (N,H,W,C3) -- or, from a multihead, (N,A_head,C) per head as lists
         -> (B,num_boxes,num_classes) (the list itself when it is one), (B,num_boxes,7+E) through the fused decode kernel sv_anchor_decode
         (sv_anchor_decode_coded for coded boxes and head-major anchors)."""
-        lib = _lib.load()
         first = box_preds[0] if isinstance(box_preds, list) else box_preds
         _lib.require_cuda(first)
         anchors = self._anchors_on(first.device)
@@ -180,17 +179,15 @@ class AnchorHeadTemplate(nn.Module):
         dir_offset, dir_limit = float(cfg_get(self.model_cfg, 'DIR_OFFSET', 0.0)), float(cfg_get(self.model_cfg, 'DIR_LIMIT_OFFSET', 0.0))
         if not self._coded:
             out = torch.empty_like(enc)
-            rc = lib.sv_anchor_decode(_lib.ptr(anchors), num_anchors, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0), dir_offset, dir_limit,
-                                      _lib.ptr(out), _lib.stream())
-            _lib.check(rc, "sv_anchor_decode")
+            _lib.launch("sv_anchor_decode", _lib.ptr(anchors), num_anchors, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0), dir_offset, dir_limit,
+                        _lib.ptr(out))
             return batch_cls_preds, out
         extra = anchors.shape[-1] - 7
         sincos = self._sincos
         assert enc.shape[-1] == 7 + sincos + extra, "box_preds width does not match the box coder"
         out = torch.empty((batch_size, num_anchors, 7 + extra), dtype=torch.float32, device=enc.device)
-        rc = lib.sv_anchor_decode_coded(_lib.ptr(anchors), num_anchors, extra, sincos, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0),
-                                        dir_offset, dir_limit, _lib.ptr(out), _lib.stream())
-        _lib.check(rc, "sv_anchor_decode_coded")
+        _lib.launch("sv_anchor_decode_coded", _lib.ptr(anchors), num_anchors, extra, sincos, _lib.ptr(enc), _lib.ptr(dirp), batch_size, int(nb or 0),
+                    dir_offset, dir_limit, _lib.ptr(out))
         return batch_cls_preds, out
 
     def forward(self, **kwargs):

@@ -149,8 +149,6 @@ class CenterHead(nn.Module):
 
     def assign_targets(self, gt_boxes, feature_map_size=None, **kwargs):
         """gt_boxes (B,M,8+) -> dict of per-head lists: heatmaps (B,ncls,H,W), target_boxes (B,500,dim), inds, masks."""
-        lib = _lib.load()
-        _lib.require_cuda(gt_boxes)
         H, W = int(feature_map_size[0]), int(feature_map_size[1])
         tcfg = cfg_get(self.model_cfg, 'TARGET_ASSIGNER_CONFIG')
         gt = gt_boxes.contiguous().float()
@@ -162,11 +160,10 @@ class CenterHead(nn.Module):
         tbox = torch.empty((nh, B, nmax, D), dtype=torch.float32, device=dev)
         inds = torch.empty((nh, B, nmax), dtype=torch.int64, device=dev)
         masks = torch.empty((nh, B, nmax), dtype=torch.int64, device=dev)
-        rc = lib.sv_center_assign_targets(_lib.ptr(gt) if G else None, B, G, D, nh, len(self.class_names), _lib.ptr(tab), _lib.ptr(ncls), _lib.ptr(off),
-                                          total, W, H, self.point_cloud_range[0], self.point_cloud_range[1], self.voxel_size[0], self.voxel_size[1],
-                                          float(cfg_get(tcfg, 'FEATURE_MAP_STRIDE')), nmax, float(cfg_get(tcfg, 'GAUSSIAN_OVERLAP')),
-                                          int(cfg_get(tcfg, 'MIN_RADIUS')), _lib.ptr(heat), _lib.ptr(tbox), _lib.ptr(inds), _lib.ptr(masks), _lib.stream())
-        _lib.check(rc, "sv_center_assign_targets")
+        _lib.launch("sv_center_assign_targets", _lib.ptr(gt) if G else None, B, G, D, nh, len(self.class_names), _lib.ptr(tab), _lib.ptr(ncls), _lib.ptr(off),
+                    total, W, H, self.point_cloud_range[0], self.point_cloud_range[1], self.voxel_size[0], self.voxel_size[1],
+                    float(cfg_get(tcfg, 'FEATURE_MAP_STRIDE')), nmax, float(cfg_get(tcfg, 'GAUSSIAN_OVERLAP')), int(cfg_get(tcfg, 'MIN_RADIUS')),
+                    _lib.ptr(heat), _lib.ptr(tbox), _lib.ptr(inds), _lib.ptr(masks))
         offs = off_host + [total]
         return {'heatmaps': [heat[:, offs[h]:offs[h + 1]] for h in range(nh)], 'target_boxes': [tbox[h] for h in range(nh)],
                 'inds': [inds[h] for h in range(nh)], 'masks': [masks[h] for h in range(nh)], 'heatmap_masks': []}

@@ -55,7 +55,6 @@ class AxisAlignedTargetAssigner(object):
 
     def assign_targets(self, all_anchors, gt_boxes_with_classes):
         """all_anchors: [(nz,ny,nx,n_size,n_rot,7+E), ...] per class; gt_boxes (B, M, 8+E) -> dict of (B,A[,code_size]) tensors"""
-        lib = _lib.load()
         _lib.require_cuda(gt_boxes_with_classes, *all_anchors)
         t = self._device_tables(all_anchors)
         gt = gt_boxes_with_classes.contiguous().float()
@@ -69,14 +68,11 @@ class AxisAlignedTargetAssigner(object):
         weights = torch.empty((B, A), dtype=torch.float32, device=dev)
         scratch = torch.empty((max(B * G, 1),), dtype=torch.float32, device=dev)
         if not (self.use_multihead or extra or self.sincos):
-            rc = lib.sv_assign_targets_axis_aligned(_lib.ptr(t['anchors']), A, t['per_loc'], len(all_anchors), _lib.ptr(t['offs']), _lib.ptr(t['cls']),
-                                                    _lib.ptr(t['mthr']), _lib.ptr(t['uthr']), _lib.ptr(gt) if G else None, B, G, _lib.ptr(scratch),
-                                                    _lib.ptr(labels), _lib.ptr(targets), _lib.ptr(weights), _lib.stream())
-            _lib.check(rc, "sv_assign_targets_axis_aligned")
+            _lib.launch("sv_assign_targets_axis_aligned", _lib.ptr(t['anchors']), A, t['per_loc'], len(all_anchors), _lib.ptr(t['offs']), _lib.ptr(t['cls']),
+                        _lib.ptr(t['mthr']), _lib.ptr(t['uthr']), _lib.ptr(gt) if G else None, B, G, _lib.ptr(scratch), _lib.ptr(labels), _lib.ptr(targets),
+                        _lib.ptr(weights))
         else:
-            rc = lib.sv_assign_targets_axis_aligned_coded(_lib.ptr(t['anchors']), A, extra, self.sincos, int(bool(self.use_multihead)), t['per_loc'],
-                                                          len(all_anchors), _lib.ptr(t['offs']), _lib.ptr(t['cls']), _lib.ptr(t['mthr']),
-                                                          _lib.ptr(t['uthr']), _lib.ptr(gt) if G else None, B, G, _lib.ptr(scratch),
-                                                          _lib.ptr(labels), _lib.ptr(targets), _lib.ptr(weights), _lib.stream())
-            _lib.check(rc, "sv_assign_targets_axis_aligned_coded")
+            _lib.launch("sv_assign_targets_axis_aligned_coded", _lib.ptr(t['anchors']), A, extra, self.sincos, int(bool(self.use_multihead)), t['per_loc'],
+                        len(all_anchors), _lib.ptr(t['offs']), _lib.ptr(t['cls']), _lib.ptr(t['mthr']), _lib.ptr(t['uthr']), _lib.ptr(gt) if G else None, B, G,
+                        _lib.ptr(scratch), _lib.ptr(labels), _lib.ptr(targets), _lib.ptr(weights))
         return {'box_cls_labels': labels, 'box_reg_targets': targets, 'reg_weights': weights}

@@ -107,9 +107,8 @@ def multi_classes_nms_batch(batch_cls_preds, batch_box_preds, multihead_label_ma
     num_out = torch.empty((S,), dtype=torch.int32, device=dev)
     scratch = _lib.workspace.scratch("nms_segments", lib.sv_nms_segments_scratch_bytes(S, pre), dev)
     normal = cfg_get(nms_config, 'NMS_TYPE') == 'nms_normal_gpu'
-    rc = lib.sv_nms_segments(_lib.ptr(seg_boxes), _lib.ptr(counts), S, pre, float(cfg_get(nms_config, 'NMS_THRESH')), int(normal), post,
-                             _lib.ptr(scratch), _lib.ptr(keep), _lib.ptr(num_out), _lib.stream())
-    _lib.check(rc, "sv_nms_segments")
+    _lib.launch("sv_nms_segments", _lib.ptr(seg_boxes), _lib.ptr(counts), S, pre, float(cfg_get(nms_config, 'NMS_THRESH')), int(normal), post,
+                _lib.ptr(scratch), _lib.ptr(keep), _lib.ptr(num_out))
     kept = _lib.host_ints([num_out])                                                                # the one device -> host read
     # survivors of segment s: keep[s, :kept[s]]; their flat slots, in the output order, are known on the host
     slots = torch.tensor([s * keep.shape[1] + j for s in range(S) for j in range(kept[s])], dtype=torch.int64).to(dev, non_blocking=True)

@@ -31,8 +31,7 @@ def frustum_grid(lidar_to_cam, cam_to_img, image_shape, grid_size, pc_range, dis
     X, Y, Z, rng, mode, dmin, dmax, nbins = _geometry(grid_size, pc_range, disc_cfg)
     B = l2c.shape[0]
     out = torch.empty((B, X, Y, Z, 3), dtype=torch.float32, device=l2c.device)
-    rc = _lib.load().sv_frustum_grid(_lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), B, X, Y, Z, rng, mode, dmin, dmax, nbins, _lib.ptr(out), _lib.stream())
-    _lib.check(rc, "sv_frustum_grid")
+    _lib.launch("sv_frustum_grid", _lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), B, X, Y, Z, rng, mode, dmin, dmax, nbins, _lib.ptr(out))
     return out
 
 
@@ -50,9 +49,8 @@ class _FrustumToVoxel(torch.autograd.Function):
         B, H, W, C = f.shape
         assert p.shape == (B, H, W, nbins + 1), "depth_probs must be (B, num_bins + 1, H, W) on the feature map's grid"
         store = torch.empty((B, Y, X, C, Z), dtype=torch.float32, device=f.device)
-        rc = _lib.load().sv_frustum_to_voxel(_lib.ptr(f), _lib.ptr(p), _lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), B, C, nbins, H, W, X, Y, Z, rng, mode,
-                                            dmin, dmax, _lib.ptr(store), _lib.stream())
-        _lib.check(rc, "sv_frustum_to_voxel")
+        _lib.launch("sv_frustum_to_voxel", _lib.ptr(f), _lib.ptr(p), _lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), B, C, nbins, H, W, X, Y, Z, rng, mode,
+                    dmin, dmax, _lib.ptr(store))
         ctx.save_for_backward(f, p, l2c, c2i, ishape)
         ctx.geom = geom
         return store.permute(0, 3, 4, 1, 2)                                 # (B, C, Z, Y, X), the reference's shape
@@ -70,9 +68,8 @@ class _FrustumToVoxel(torch.autograd.Function):
         scratch = _lib.workspace.scratch("frustum_to_voxel_grad", nbytes, g.device)
         gf = torch.empty_like(f)
         gp = torch.empty_like(p)
-        rc = lib.sv_frustum_to_voxel_grad(_lib.ptr(f), _lib.ptr(p), _lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), _lib.ptr(g), B, C, nbins, H, W, X, Y, Z,
-                                          rng, mode, dmin, dmax, _lib.ptr(scratch), _lib.ptr(gf), _lib.ptr(gp), _lib.stream())
-        _lib.check(rc, "sv_frustum_to_voxel_grad")
+        _lib.launch("sv_frustum_to_voxel_grad", _lib.ptr(f), _lib.ptr(p), _lib.ptr(l2c), _lib.ptr(c2i), _lib.ptr(ishape), _lib.ptr(g), B, C, nbins, H, W, X, Y,
+                    Z, rng, mode, dmin, dmax, _lib.ptr(scratch), _lib.ptr(gf), _lib.ptr(gp))
         return gf.permute(0, 3, 1, 2), gp.permute(0, 3, 1, 2), None, None, None, None
 
 

@@ -16,22 +16,19 @@ import torch
 from .... import _lib
 
 
-def _check_input(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
+def _check_contiguous(t, name):
     if not t.is_contiguous():
         raise RuntimeError(f"{name} must be contiguous")
 
 
 def _overlap(boxes_a, boxes_b, out, iou):
     for t, n in ((boxes_a, "boxes_a"), (boxes_b, "boxes_b"), (out, "ans")):
-        _check_input(t, n)
+        _check_contiguous(t, n)
     assert boxes_a.dtype == boxes_b.dtype == out.dtype == torch.float32 and boxes_a.shape[1] == boxes_b.shape[1] == 7
     na, nb = boxes_a.shape[0], boxes_b.shape[0]
     assert tuple(out.shape) == (na, nb)
-    lib = _lib.load()
-    _lib.check(lib.sv_boxes_overlap_bev(_lib.ptr(boxes_a) if na else None, na, _lib.ptr(boxes_b) if nb else None, nb,
-                                        _lib.ptr(out) if out.numel() else None, int(iou), _lib.stream()), "sv_boxes_overlap_bev")
+    _lib.launch("sv_boxes_overlap_bev", _lib.ptr(boxes_a) if na else None, na, _lib.ptr(boxes_b) if nb else None, nb, _lib.ptr(out) if out.numel() else None,
+                int(iou))
     return 1
 
 
@@ -44,9 +41,8 @@ def boxes_iou_bev_gpu(boxes_a, boxes_b, ans_iou):
 
 
 def _nms(boxes, keep, thresh, normal):
-    _check_input(boxes, "boxes")
-    if not keep.is_contiguous():
-        raise RuntimeError("keep must be contiguous")
+    _check_contiguous(boxes, "boxes")
+    _check_contiguous(keep, "keep")
     assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 7
     assert keep.dtype == torch.int64 and keep.numel() >= boxes.shape[0]
     lib = _lib.load()
@@ -54,8 +50,7 @@ def _nms(boxes, keep, thresh, normal):
     keep_dev = keep if keep.is_cuda else torch.empty((max(n, 1),), dtype=torch.int64, device=dev)
     num_out = torch.zeros((1,), dtype=torch.int32, device=dev)
     scratch = _lib.workspace.scratch("nms", lib.sv_nms_scratch_bytes(n), dev)
-    _lib.check(lib.sv_nms(_lib.ptr(boxes) if n else None, n, float(thresh), int(normal), _lib.ptr(scratch), _lib.ptr(keep_dev), _lib.ptr(num_out),
-                          _lib.stream()), "sv_nms")
+    _lib.launch("sv_nms", _lib.ptr(boxes) if n else None, n, float(thresh), int(normal), _lib.ptr(scratch), _lib.ptr(keep_dev), _lib.ptr(num_out))
     k = int(num_out.item())
     if not keep.is_cuda:
         keep[:k] = keep_dev[:k].cpu()

@@ -45,13 +45,10 @@ def boxes_overlap_bev(boxes_a, boxes_b):
 def boxes_iou3d_batch(boxes_a, boxes_b):
     """(B,N,>=7), (B,M,>=7) -> (B,N,M) 3-D IoU of every scene's pairs in one launch (sv_boxes_iou3d_batch; seevcn extension: the reference calls
     boxes_iou3d_gpu scene by scene, ~22 launches each).  Same arithmetic as boxes_iou3d_gpu, operation by operation."""
-    lib = _lib.load()
-    _lib.require_cuda(boxes_a, boxes_b)
     assert boxes_a.dim() == 3 and boxes_b.dim() == 3 and boxes_a.shape[0] == boxes_b.shape[0] and boxes_a.shape[2] >= 7 and boxes_b.shape[2] >= 7
     a, b = boxes_a.contiguous().float(), boxes_b.contiguous().float()
     out = torch.empty((a.shape[0], a.shape[1], b.shape[1]), dtype=torch.float32, device=a.device)
-    _lib.check(lib.sv_boxes_iou3d_batch(_lib.ptr(a), a.shape[1], a.shape[2], _lib.ptr(b), b.shape[1], b.shape[2], a.shape[0], _lib.ptr(out), _lib.stream()),
-               "sv_boxes_iou3d_batch")
+    _lib.launch("sv_boxes_iou3d_batch", _lib.ptr(a), a.shape[1], a.shape[2], _lib.ptr(b), b.shape[1], b.shape[2], a.shape[0], _lib.ptr(out))
     return out
 
 
@@ -76,7 +73,6 @@ def boxes_iou3d_gpu(boxes_a, boxes_b):
 
 def _nms(boxes, scores, thresh, pre_maxsize, normal, max_keep=None, padded=None, presorted=False):
     lib = _lib.load()
-    _lib.require_cuda(boxes, scores)
     assert boxes.shape[1] == 7
     if presorted:                                          # the caller's boxes come out of a sorted top-k: no second sort (8-10 launches)
         order = None
@@ -91,9 +87,8 @@ def _nms(boxes, scores, thresh, pre_maxsize, normal, max_keep=None, padded=None,
     keep = torch.empty((max(n, 1, padded or 0),), dtype=torch.int64, device=dev)
     num_out = torch.zeros((1,), dtype=torch.int32, device=dev)
     scratch = _lib.workspace.scratch("nms", lib.sv_nms_scratch_bytes(n), dev)
-    rc = lib.sv_nms_prefix(_lib.ptr(sorted_boxes) if n else None, n, float(thresh), int(normal), n if max_keep is None else min(n, int(max_keep)),
-                           _lib.ptr(scratch), _lib.ptr(keep), _lib.ptr(num_out), _lib.stream())
-    _lib.check(rc, "sv_nms_prefix")
+    _lib.launch("sv_nms_prefix", _lib.ptr(sorted_boxes) if n else None, n, float(thresh), int(normal), n if max_keep is None else min(n, int(max_keep)),
+                _lib.ptr(scratch), _lib.ptr(keep), _lib.ptr(num_out))
     if padded is not None:
         # no device -> host read: `padded` slots, the survivors first (score order), the rest index 0 with valid = False
         valid = torch.arange(padded, device=dev) < torch.clamp(num_out, max=padded)

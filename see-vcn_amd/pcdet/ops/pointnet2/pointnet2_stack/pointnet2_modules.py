@@ -86,7 +86,6 @@ class StackSAModuleMSG(nn.Module):
         hit = self._fused_weights.get(k) if hasattr(self, '_fused_weights') else None
         if hit is not None:
             return hit
-        lib = _lib.load()
         layers = list(self.mlps[k])
         out = []
         for conv, bn, first in ((layers[0], layers[1], 1), (layers[3], layers[4], 0)):
@@ -94,9 +93,8 @@ class StackSAModuleMSG(nn.Module):
             kp = 16 * ((ci - 3) // 16 + 1) if first else ci
             w = torch.empty((co, kp), dtype=torch.float32, device=device)
             b = torch.empty((co,), dtype=torch.float32, device=device)
-            _lib.check(lib.sv_sa_prepare_weights(_lib.ptr(conv.weight.detach().reshape(co, ci).contiguous()), _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()),
-                                                 _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps), co, ci, first, _lib.ptr(w), _lib.ptr(b),
-                                                 _lib.stream()), "sv_sa_prepare_weights")
+            _lib.launch("sv_sa_prepare_weights", _lib.ptr(conv.weight.detach().reshape(co, ci).contiguous()), _lib.ptr(bn.weight.detach()),
+                        _lib.ptr(bn.bias.detach()), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps), co, ci, first, _lib.ptr(w), _lib.ptr(b))
             out += [w, b]
         if not hasattr(self, '_fused_weights'):
             self._fused_weights = {}
@@ -106,7 +104,6 @@ class StackSAModuleMSG(nn.Module):
     def _fused_scale(self, k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features):
         """ball query (HIP) -> sv_sa_mlp_max: gather + both MLP layers on the matrix core + max over the neighbours in ONE launch; no
         (M, C+3, nsample) tensor (the torch path below materialises it and runs Conv2d / BatchNorm2d / max_pool2d over it)."""
-        lib = _lib.load()
         g = self.groupers[k]
         M, B = new_xyz.shape[0], xyz_batch_cnt.shape[0]
         idx = torch.zeros((M, g.nsample), dtype=torch.int32, device=new_xyz.device)
@@ -115,9 +112,8 @@ class StackSAModuleMSG(nn.Module):
         w1, b1, w2, b2 = self._prepared(k, new_xyz.device)
         c = 0 if features is None else features.shape[1]
         out = torch.empty((M, w2.shape[0]), dtype=torch.float32, device=new_xyz.device)
-        _lib.check(lib.sv_sa_mlp_max(_lib.ptr(xyz), _lib.ptr(features) if c else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, c, g.nsample,
-                                     _lib.ptr(w1), _lib.ptr(b1), w1.shape[0], _lib.ptr(w2), _lib.ptr(b2), w2.shape[0], _lib.ptr(out), _lib.stream()),
-                   "sv_sa_mlp_max")
+        _lib.launch("sv_sa_mlp_max", _lib.ptr(xyz), _lib.ptr(features) if c else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, c, g.nsample,
+                    _lib.ptr(w1), _lib.ptr(b1), w1.shape[0], _lib.ptr(w2), _lib.ptr(b2), w2.shape[0], _lib.ptr(out))
         return out
 
     def _train_ok(self, k, xyz, new_xyz, features):

@@ -38,21 +38,18 @@ BALL_HASH_MIN_POINTS = int(os.environ.get("SEEVCN_BALL_HASH_MIN", "2048"))   # s
 
 def ball_query_wrapper(B, M, radius, nsample, new_xyz, new_xyz_batch_cnt, xyz, xyz_batch_cnt, idx):
     lib = _lib.load()
-    _lib.require_cuda(new_xyz, xyz, idx)
     qs, qc = _starts(new_xyz_batch_cnt)
     ps, pc = _starts(xyz_batch_cnt)
     n = int(xyz.shape[0])
     if n >= BALL_HASH_MIN_POINTS and nsample <= 64 and radius > 0:
         # the same idx, element for element, from a cell hash of the support points (sv_ball_query_stack_hashed) instead of the O(M N) scan
         scratch = _lib.workspace.scratch("ball_hash", lib.sv_ball_query_hash_scratch_bytes(n), xyz.device)
-        rc = lib.sv_ball_query_stack_hashed(int(B), int(M), n, float(radius), int(nsample), _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(xyz),
-                                            _lib.ptr(ps), _lib.ptr(pc), _lib.ptr(scratch), _lib.ptr(idx), _lib.stream())
-        _lib.check(rc, "sv_ball_query_stack_hashed")
+        _lib.launch("sv_ball_query_stack_hashed", int(B), int(M), n, float(radius), int(nsample), _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(xyz),
+                    _lib.ptr(ps), _lib.ptr(pc), _lib.ptr(scratch), _lib.ptr(idx))
         return 1
     max_q = int(M)  # upper bound of queries per scene without a host sync
-    rc = lib.sv_ball_query_stack(int(B), int(M), max_q, float(radius), int(nsample), _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc),
-                                 _lib.ptr(xyz), _lib.ptr(ps), _lib.ptr(pc), _lib.ptr(idx), _lib.stream())
-    _lib.check(rc, "sv_ball_query_stack")
+    _lib.launch("sv_ball_query_stack", int(B), int(M), max_q, float(radius), int(nsample), _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(xyz),
+                _lib.ptr(ps), _lib.ptr(pc), _lib.ptr(idx))
     return 1
 
 
@@ -75,29 +72,22 @@ def _row_start(idx_batch_cnt, features_batch_cnt, M):
 
 
 def group_points_wrapper(B, M, C, nsample, features, features_batch_cnt, idx, idx_batch_cnt, out):
-    lib = _lib.load()
-    _lib.require_cuda(features, idx, out)
     rs = _row_start(idx_batch_cnt, features_batch_cnt, M)
-    rc = lib.sv_group_points_stack(int(M), int(C), int(nsample), _lib.ptr(features), _lib.ptr(idx), _lib.ptr(rs), _lib.ptr(out), _lib.stream())
-    _lib.check(rc, "sv_group_points_stack")
+    _lib.launch("sv_group_points_stack", int(M), int(C), int(nsample), _lib.ptr(features), _lib.ptr(idx), _lib.ptr(rs), _lib.ptr(out))
     return 1
 
 
 def group_points_grad_wrapper(B, M, C, N, nsample, grad_out, idx, idx_batch_cnt, features_batch_cnt, grad_features):
     lib = _lib.load()
-    _lib.require_cuda(grad_out, idx, grad_features)
     rs = _row_start(idx_batch_cnt, features_batch_cnt, M)
     if ordered.ordered_gradients():                       # same terms in ascending (query, slot) order, no float atomics
         nbytes = lib.sv_group_points_grad_stack_ordered_scratch_bytes(int(M), int(N), int(nsample))
         scratch = _lib.workspace.scratch("group_grad_ordered", nbytes, grad_out.device)
-        rc = lib.sv_group_points_grad_stack_ordered(int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs),
-                                                    _lib.ptr(scratch), _lib.ptr(grad_features), _lib.stream())
-        _lib.check(rc, "sv_group_points_grad_stack_ordered")
+        _lib.launch("sv_group_points_grad_stack_ordered", int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs),
+                    _lib.ptr(scratch), _lib.ptr(grad_features))
         ordered.count_call("group_points")
         return 1
-    rc = lib.sv_group_points_grad_stack(int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs),
-                                        _lib.ptr(grad_features), _lib.stream())
-    _lib.check(rc, "sv_group_points_grad_stack")
+    _lib.launch("sv_group_points_grad_stack", int(M), int(C), int(N), int(nsample), _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(rs), _lib.ptr(grad_features))
     return 1
 
 
@@ -115,22 +105,19 @@ def fps_bucketed(points, starts, cnt, batch, fixed_n, max_n, m, idx):
                 raise _lib.SeevcnHipError(f"farthest_point_sampling: a scene has {v} points, the caller's max_n is {max_n}")
         _lib.defer_check(cnt.max(), _check)
     scratch = torch.empty((int(lib.sv_fps_bucket_scratch_bytes(int(batch), int(max_n))),), dtype=torch.uint8, device=points.device)
-    _lib.check(lib.sv_farthest_point_sampling_bucketed(_lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), int(batch), int(fixed_n), int(max_n), int(m),
-                                                       _lib.ptr(scratch), _lib.ptr(idx), _lib.stream()), "sv_farthest_point_sampling_bucketed")
+    _lib.launch("sv_farthest_point_sampling_bucketed", _lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), int(batch), int(fixed_n), int(max_n), int(m),
+                _lib.ptr(scratch), _lib.ptr(idx))
     return True
 
 
 def farthest_point_sampling_wrapper(b, n, m, points, temp, idx):
     """The fixed-layout call, (b, n, 3) -> (b, m), of both pointnet2 wrappers and vcn.utils.misc.fps.  temp None: the (b, n) buffer of the exhaustive
     kernels is allocated here, only when they run."""
-    lib = _lib.load()
-    _lib.require_cuda(points, idx)
     if fps_bucketed(points, None, None, b, n, n, m, idx):
         return 1
     if temp is None:
         temp = torch.empty((int(b), int(n)), dtype=torch.float32, device=points.device)
-    rc = lib.sv_farthest_point_sampling(_lib.ptr(points), int(b), int(n), int(m), _lib.ptr(temp), _lib.ptr(idx), _lib.stream())
-    _lib.check(rc, "sv_farthest_point_sampling")
+    _lib.launch("sv_farthest_point_sampling", _lib.ptr(points), int(b), int(n), int(m), _lib.ptr(temp), _lib.ptr(idx))
     return 1
 
 
@@ -145,7 +132,6 @@ def stack_farthest_point_sampling(points, xyz_batch_cnt, npoint, max_n=None, buc
     """All ragged scenes in one launch -> (batch, npoint) int32 GLOBAL row indices (seevcn extension; replaces the
     per-scene loop of voxel_set_abstraction.py:250-256).  bucketed=False: the exhaustive kernels only (tests, A/B runs)."""
     lib = _lib.load()
-    _lib.require_cuda(points)
     starts, cnt = _starts(xyz_batch_cnt)
     batch = cnt.shape[0]
     if max_n is None:
@@ -154,9 +140,8 @@ def stack_farthest_point_sampling(points, xyz_batch_cnt, npoint, max_n=None, buc
     if bucketed and fps_bucketed(points, starts, cnt, batch, 0, max_n, npoint, idx):
         return idx
     temp, scratch = _exhaustive_scratch(lib, points, batch, max_n)
-    rc = lib.sv_stack_farthest_point_sampling_multi(_lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), batch, int(max_n), int(npoint),
-                                                    _lib.ptr(temp), _lib.ptr(scratch), _lib.ptr(idx), _lib.stream())
-    _lib.check(rc, "sv_stack_farthest_point_sampling_multi")
+    _lib.launch("sv_stack_farthest_point_sampling_multi", _lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), batch, int(max_n), int(npoint), _lib.ptr(temp),
+                _lib.ptr(scratch), _lib.ptr(idx))
     return idx
 
 
@@ -189,7 +174,6 @@ def stack_farthest_point_sampling_async(points, xyz_batch_cnt, npoint, max_n):
     """stack_farthest_point_sampling without the read-back: enqueues on the current stream and returns an FpsHandle (seevcn extension, used to
     sample the keypoints on a side stream while the backbone runs).  max_n (largest scene) must come from the host."""
     lib = _lib.load()
-    _lib.require_cuda(points)
     starts, cnt = _starts(xyz_batch_cnt)
     batch = cnt.shape[0]
     idx = torch.empty((batch, npoint), dtype=torch.int32, device=points.device)
@@ -201,9 +185,8 @@ def stack_farthest_point_sampling_async(points, xyz_batch_cnt, npoint, max_n):
     stream = torch.cuda.current_stream()
 
     def launch(write_through):
-        _lib.check(lib.sv_stack_farthest_point_sampling_multi_async(_lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), batch, int(max_n), int(npoint),
-                                                                    _lib.ptr(temp), _lib.ptr(scratch), _lib.ptr(idx), int(write_through), _lib.stream()),
-                   "sv_stack_farthest_point_sampling_multi_async")
+        _lib.launch("sv_stack_farthest_point_sampling_multi_async", _lib.ptr(points), _lib.ptr(starts), _lib.ptr(cnt), batch, int(max_n), int(npoint),
+                    _lib.ptr(temp), _lib.ptr(scratch), _lib.ptr(idx), int(write_through))
 
     launch(0)
     return FpsHandle(idx, err, stream, lambda: launch(1))
@@ -213,16 +196,13 @@ def spc_select(xyz, xyz_batch_cnt, rois, radius, num_sectors, max_n=None):
     """sample_points_with_roi + the sector expression of sector_fps for every scene in one launch (seevcn extension; voxel_set_abstraction.py:45-75,
     88-90).  xyz (N, 3) stacked, rois (B, M, 7 + C) -> sector (N,) int32: -1 not selected | 0..num_sectors; num_sectors == 0: 0 selected | -1.
     max_n: an upper bound of the largest scene known on the host (None: N)."""
-    lib = _lib.load()
-    _lib.require_cuda(xyz, rois)
     assert xyz.dtype == torch.float32 and xyz.is_contiguous() and rois.dim() == 3
     starts, cnt = _starts(xyz_batch_cnt)
     rois = rois.contiguous().float()
     assert rois.shape[0] == cnt.shape[0], "one set of RoIs per scene"
     sector = torch.empty((xyz.shape[0],), dtype=torch.int32, device=xyz.device)
-    rc = lib.sv_spc_select(_lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), cnt.shape[0], int(xyz.shape[0] if max_n is None else max_n), _lib.ptr(rois),
-                           rois.shape[1], rois.shape[2], float(radius), int(num_sectors), _lib.ptr(sector), _lib.stream())
-    _lib.check(rc, "sv_spc_select")
+    _lib.launch("sv_spc_select", _lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), cnt.shape[0], int(xyz.shape[0] if max_n is None else max_n), _lib.ptr(rois),
+                rois.shape[1], rois.shape[2], float(radius), int(num_sectors), _lib.ptr(sector))
     return sector
 
 
@@ -230,16 +210,13 @@ def spc_partition(sector, xyz, xyz_batch_cnt, num_keypoints, num_sectors):
     """The stable (scene, sector) row lists, quotas and output offsets of sector_fps (voxel_set_abstraction.py:91-113) for every scene in one launch
     -> (order (N,), tables (5, B * max(S, 1)) int32 rows seg_start / seg_cnt / seg_m / seg_out_start / kp_cnt -- kp_cnt fills the first B entries of
     its row).  Nothing is read back."""
-    lib = _lib.load()
-    _lib.require_cuda(sector)
     assert sector.dtype == torch.int32 and sector.is_contiguous()
     starts, cnt = _starts(xyz_batch_cnt)
     B, nseg = cnt.shape[0], cnt.shape[0] * max(int(num_sectors), 1)
     order = torch.empty((sector.shape[0],), dtype=torch.int32, device=sector.device)
     tables = torch.empty((5, nseg), dtype=torch.int32, device=sector.device)      # the kernel writes every entry it defines
-    rc = lib.sv_spc_partition(_lib.ptr(sector), _lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), B, int(num_keypoints), int(num_sectors), _lib.ptr(order),
-                              _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.ptr(tables[2]), _lib.ptr(tables[3]), _lib.ptr(tables[4]), _lib.stream())
-    _lib.check(rc, "sv_spc_partition")
+    _lib.launch("sv_spc_partition", _lib.ptr(sector), _lib.ptr(xyz), _lib.ptr(starts), _lib.ptr(cnt), B, int(num_keypoints), int(num_sectors), _lib.ptr(order),
+                _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.ptr(tables[2]), _lib.ptr(tables[3]), _lib.ptr(tables[4]))
     return order, tables
 
 
@@ -247,43 +224,32 @@ def stack_farthest_point_sampling_ragged(xyz, order, seg_start, seg_cnt, seg_m, 
     """One workgroup per segment of the device tables; GLOBAL rows into idx (int32, caller-allocated) at seg_out_start (stack_farthest_point_sampling_
     wrapper, src/sampling.cpp, with the counts left on the device).  order None: segment g is the rows seg_start[g] ... of xyz.  max_n: an upper bound
     of the largest segment known on the host (None: N)."""
-    lib = _lib.load()
-    _lib.require_cuda(xyz, idx)
     assert xyz.dtype == torch.float32 and xyz.is_contiguous() and idx.dtype == torch.int32
     for t in (order, seg_start, seg_cnt, seg_m, seg_out_start):
         assert t is None or t.dtype == torch.int32
     N = xyz.shape[0]
     max_n = N if max_n is None else min(int(max_n), N)
     temp = torch.empty((N,), dtype=torch.float32, device=xyz.device) if max_n > 24576 else None
-    rc = lib.sv_stack_farthest_point_sampling_ragged(_lib.ptr(xyz), N, _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(seg_cnt), _lib.ptr(seg_m),
-                                                     _lib.ptr(seg_out_start), seg_cnt.shape[0], max_n, _lib.ptr(temp), _lib.ptr(idx), idx.numel(),
-                                                     _lib.stream())
-    _lib.check(rc, "sv_stack_farthest_point_sampling_ragged")
+    _lib.launch("sv_stack_farthest_point_sampling_ragged", _lib.ptr(xyz), N, _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(seg_cnt), _lib.ptr(seg_m),
+                _lib.ptr(seg_out_start), seg_cnt.shape[0], max_n, _lib.ptr(temp), _lib.ptr(idx), idx.numel())
     return idx
 
 
 def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, point_indices, idx):
     """src/voxel_query.cpp: new_coords (M, 4) int32 [b, z, y, x], point_indices (B, R1, R2, R3) int32, idx (M, nsample) int32 zero-filled by the caller."""
-    lib = _lib.load()
-    _lib.require_cuda(new_xyz, xyz, new_coords, point_indices, idx)
     assert new_coords.dtype == torch.int32 and point_indices.dtype == torch.int32 and idx.dtype == torch.int32
     cells = int(R1) * int(R2) * int(R3)
     B = point_indices.numel() // cells if cells else 0
-    rc = lib.sv_voxel_query_stack(int(M), B, int(R1), int(R2), int(R3), int(xyz.shape[0]), int(nsample), float(radius), int(z_range), int(y_range),
-                                  int(x_range), _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(new_coords), _lib.ptr(point_indices), _lib.ptr(idx),
-                                  _lib.stream())
-    _lib.check(rc, "sv_voxel_query_stack")
+    _lib.launch("sv_voxel_query_stack", int(M), B, int(R1), int(R2), int(R3), int(xyz.shape[0]), int(nsample), float(radius), int(z_range), int(y_range),
+                int(x_range), _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(new_coords), _lib.ptr(point_indices), _lib.ptr(idx))
     return 1
 
 
 def three_interpolate_wrapper(features, idx, weight, out):
     """src/interpolate.cpp three_interpolate_wrapper_stack: features (M, C), idx / weight (N, 3) -> out (N, C), every element written."""
-    lib = _lib.load()
-    _lib.require_cuda(features, idx, weight, out)
     assert idx.dtype == torch.int32 and features.dtype == weight.dtype == out.dtype == torch.float32
-    rc = lib.sv_three_interpolate_stack(int(idx.shape[0]), int(features.shape[1]), int(features.shape[0]), _lib.ptr(features), _lib.ptr(idx),
-                                        _lib.ptr(weight), _lib.ptr(out), _lib.stream())
-    _lib.check(rc, "sv_three_interpolate_stack")
+    _lib.launch("sv_three_interpolate_stack", int(idx.shape[0]), int(features.shape[1]), int(features.shape[0]), _lib.ptr(features), _lib.ptr(idx),
+                _lib.ptr(weight), _lib.ptr(out))
     return 1
 
 
@@ -291,20 +257,16 @@ def three_interpolate_grad_wrapper(grad_out, idx, weight, grad_features):
     """src/interpolate.cpp three_interpolate_grad_wrapper_stack: grad_out (N, C) -> grad_features (M, C), every element written (the plain
     route zero-fills and adds with float atomics; the ordered route sums in ascending key 3 r + t)."""
     lib = _lib.load()
-    _lib.require_cuda(grad_out, idx, weight, grad_features)
     assert idx.dtype == torch.int32 and grad_out.dtype == weight.dtype == grad_features.dtype == torch.float32
     rows, C, n = int(idx.shape[0]), int(grad_out.shape[1]), int(grad_features.shape[0])
     if ordered.ordered_gradients():
         nbytes = lib.sv_three_interpolate_grad_stack_ordered_scratch_bytes(rows, n)
         scratch = _lib.workspace.scratch("three_interp_grad_ordered", nbytes, grad_out.device)
-        rc = lib.sv_three_interpolate_grad_stack_ordered(rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(scratch),
-                                                         _lib.ptr(grad_features), _lib.stream())
-        _lib.check(rc, "sv_three_interpolate_grad_stack_ordered")
+        _lib.launch("sv_three_interpolate_grad_stack_ordered", rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(scratch),
+                    _lib.ptr(grad_features))
         ordered.count_call("three_interpolate")
         return 1
-    rc = lib.sv_three_interpolate_grad_stack(rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features),
-                                             _lib.stream())
-    _lib.check(rc, "sv_three_interpolate_grad_stack")
+    _lib.launch("sv_three_interpolate_grad_stack", rows, C, n, _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features))
     return 1
 
 
@@ -313,8 +275,6 @@ def vector_pool_choice(support_xyz, xyz_batch_cnt, support_features, new_xyz, ne
     """`voxel_random_choice` vector pooling in one launch (seevcn entry; the reference's vector_pool_wrapper sizes grouped_idxs on the host
     and is re-run until it fits).  -> choice (M, G) int32 global support row or -1, point_cnt (M, G) int32, new_local_xyz (M, 3 G),
     new_features (M, G * c_each); all final, nothing is read back."""
-    lib = _lib.load()
-    _lib.require_cuda(support_xyz, support_features, new_xyz)
     assert support_xyz.dtype == support_features.dtype == new_xyz.dtype == torch.float32
     qs, qc = _starts(new_xyz_batch_cnt)
     ps, pc = _starts(xyz_batch_cnt)
@@ -326,32 +286,28 @@ def vector_pool_choice(support_xyz, xyz_batch_cnt, support_features, new_xyz, ne
     point_cnt = torch.empty((M, G), dtype=torch.int32, device=dev)
     new_local_xyz = torch.empty((M, 3 * G), dtype=torch.float32, device=dev)
     new_features = torch.empty((M, G * c_each), dtype=torch.float32, device=dev)
-    rc = lib.sv_vector_pool_choice(int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(support_xyz),
-                                   _lib.ptr(support_features), _lib.ptr(ps), _lib.ptr(pc), c_in, c_each, int(num_grid_x), int(num_grid_y),
-                                   int(num_grid_z), float(max_neighbour_distance), int(nsample), int(neighbor_type), _lib.ptr(choice),
-                                   _lib.ptr(point_cnt), _lib.ptr(new_local_xyz), _lib.ptr(new_features), _lib.stream())
-    _lib.check(rc, "sv_vector_pool_choice")
+    _lib.launch("sv_vector_pool_choice", int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(qs), _lib.ptr(qc), _lib.ptr(support_xyz),
+                _lib.ptr(support_features), _lib.ptr(ps), _lib.ptr(pc), c_in, c_each, int(num_grid_x), int(num_grid_y), int(num_grid_z),
+                float(max_neighbour_distance), int(nsample), int(neighbor_type), _lib.ptr(choice), _lib.ptr(point_cnt), _lib.ptr(new_local_xyz),
+                _lib.ptr(new_features))
     return choice, point_cnt, new_local_xyz, new_features
 
 
 def vector_pool_choice_grad(grad_new_features, choice, point_cnt, N, num_c_in):
     """grad_new_features (M, G * c_each) -> grad_support_features (N, c_in), every element written."""
     lib = _lib.load()
-    _lib.require_cuda(grad_new_features, choice, point_cnt)
     M, G = int(choice.shape[0]), int(choice.shape[1])
     c_each = int(grad_new_features.shape[1]) // G
     grad_support = torch.empty((int(N), int(num_c_in)), dtype=torch.float32, device=grad_new_features.device)
     if ordered.ordered_gradients():
         nbytes = lib.sv_vector_pool_choice_grad_ordered_scratch_bytes(M, int(N), G)
         scratch = _lib.workspace.scratch("vector_pool_grad_ordered", nbytes, grad_new_features.device)
-        rc = lib.sv_vector_pool_choice_grad_ordered(M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice),
-                                                    _lib.ptr(point_cnt), _lib.ptr(scratch), _lib.ptr(grad_support), _lib.stream())
-        _lib.check(rc, "sv_vector_pool_choice_grad_ordered")
+        _lib.launch("sv_vector_pool_choice_grad_ordered", M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice),
+                    _lib.ptr(point_cnt), _lib.ptr(scratch), _lib.ptr(grad_support))
         ordered.count_call("vector_pool")
         return grad_support
-    rc = lib.sv_vector_pool_choice_grad(M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice), _lib.ptr(point_cnt),
-                                        _lib.ptr(grad_support), _lib.stream())
-    _lib.check(rc, "sv_vector_pool_choice_grad")
+    _lib.launch("sv_vector_pool_choice_grad", M, int(N), G, int(num_c_in), c_each, _lib.ptr(grad_new_features), _lib.ptr(choice), _lib.ptr(point_cnt),
+                _lib.ptr(grad_support))
     return grad_support
 
 
@@ -359,18 +315,15 @@ def vector_pool_three_nn(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_cente
                          neighbor_type):
     """The local neighbour list and the 3-NN of every grid centre over it in one launch (seevcn entry; the reference's two wrappers pass a
     host-sized stack_neighbor_idxs between them).  -> idx (M, G, 3) int32 global rows or -1, dist2 (M, G, 3) (+inf where idx is -1)."""
-    lib = _lib.load()
-    _lib.require_cuda(support_xyz, new_xyz, new_xyz_grid_centers)
     assert support_xyz.dtype == new_xyz.dtype == new_xyz_grid_centers.dtype == torch.float32
     qs, qc = _starts(new_xyz_batch_cnt)
     ps, pc = _starts(xyz_batch_cnt)
     M, N, G = int(new_xyz.shape[0]), int(support_xyz.shape[0]), int(new_xyz_grid_centers.shape[1])
     idx = torch.empty((M, G, 3), dtype=torch.int32, device=new_xyz.device)
     dist2 = torch.empty((M, G, 3), dtype=torch.float32, device=new_xyz.device)
-    rc = lib.sv_vector_pool_three_nn(int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(new_xyz_grid_centers), _lib.ptr(qs), _lib.ptr(qc),
-                                     _lib.ptr(support_xyz), _lib.ptr(ps), _lib.ptr(pc), G, float(max_neighbour_distance), int(nsample),
-                                     int(neighbor_type), _lib.ptr(idx), _lib.ptr(dist2), _lib.stream())
-    _lib.check(rc, "sv_vector_pool_three_nn")
+    _lib.launch("sv_vector_pool_three_nn", int(qc.shape[0]), M, N, M, _lib.ptr(new_xyz), _lib.ptr(new_xyz_grid_centers), _lib.ptr(qs), _lib.ptr(qc),
+                _lib.ptr(support_xyz), _lib.ptr(ps), _lib.ptr(pc), G, float(max_neighbour_distance), int(nsample), int(neighbor_type), _lib.ptr(idx),
+                _lib.ptr(dist2))
     return idx, dist2
 
 

@@ -86,12 +86,11 @@ class SAScaleTrain(Function):
         sel, aux, out = torch.empty((M, C2), **f32), torch.empty((M, C2), **f32), torch.empty((M, C2), **f32)
         arg, aux_arg = torch.empty((M, C2), dtype=torch.uint8, device=dev), torch.empty((M, C2), dtype=torch.uint8, device=dev)
         scratch = _lib.workspace.scratch("sa_train", lib.sv_sa_train_scratch_bytes(C, C1, C2), dev)
-        _lib.check(lib.sv_sa_train_forward(_lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C, ns,
-                                           _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), _lib.ptr(rm1), _lib.ptr(rv1), _lib.ptr(nbt1), C1,
-                                           _lib.ptr(w2c), _lib.ptr(g2.detach()), _lib.ptr(b2.detach()), _lib.ptr(rm2), _lib.ptr(rv2), _lib.ptr(nbt2), C2,
-                                           float(momentum), float(eps), _lib.ptr(scratch), _lib.ptr(proj), _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1),
-                                           _lib.ptr(sm2), _lib.ptr(si2), _lib.ptr(sel), _lib.ptr(aux), _lib.ptr(arg), _lib.ptr(aux_arg), _lib.ptr(out),
-                                           _lib.stream()), "sv_sa_train_forward")
+        _lib.launch("sv_sa_train_forward", _lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C, ns,
+                    _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), _lib.ptr(rm1), _lib.ptr(rv1), _lib.ptr(nbt1), C1, _lib.ptr(w2c),
+                    _lib.ptr(g2.detach()), _lib.ptr(b2.detach()), _lib.ptr(rm2), _lib.ptr(rv2), _lib.ptr(nbt2), C2, float(momentum), float(eps),
+                    _lib.ptr(scratch), _lib.ptr(proj), _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1), _lib.ptr(sm2), _lib.ptr(si2), _lib.ptr(sel),
+                    _lib.ptr(aux), _lib.ptr(arg), _lib.ptr(aux_arg), _lib.ptr(out))
         ctx.save_for_backward(xyz, features, new_xyz, idx, row_start, w1c, g1, b1, w2c, g2, b2, z1, z2, stats, sel, arg, out)
         ctx.w_shapes = (w1.shape, w2.shape)
         ctx.mark_non_differentiable(idx)
@@ -116,18 +115,18 @@ class SAScaleTrain(Function):
         gbn = torch.empty((2 * C1 + 2 * C2,), **f32)
         dg1, db1, dg2, db2 = gbn[:C1], gbn[C1:2 * C1], gbn[2 * C1:2 * C1 + C2], gbn[2 * C1 + C2:]
         if ordered.ordered_gradients():                   # the scatter summed in ascending (query, slot) order instead of float atomics
-            entry, name = lib.sv_sa_train_backward_ordered, "sv_sa_train_backward_ordered"
+            name = "sv_sa_train_backward_ordered"
             scratch = _lib.workspace.scratch("sa_train_ordered", lib.sv_sa_train_backward_ordered_scratch_bytes(M, N, C, ns, C1, C2), dev)
             ordered.count_call("sa_train")
         else:
-            entry, name = lib.sv_sa_train_backward, "sv_sa_train_backward"
+            name = "sv_sa_train_backward"
             scratch = _lib.workspace.scratch("sa_train", lib.sv_sa_train_scratch_bytes(C, C1, C2), dev)
-        _lib.check(entry(_lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C,
-                         ns, _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), C1, _lib.ptr(w2c), _lib.ptr(g2.detach()),
-                         _lib.ptr(b2.detach()), C2, _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1), _lib.ptr(sm2), _lib.ptr(si2),
-                         _lib.ptr(sel), _lib.ptr(arg), _lib.ptr(out), _lib.ptr(grad_out.contiguous()), _lib.ptr(scratch), _lib.ptr(dy1),
-                         _lib.ptr(aux), _lib.ptr(scatter), _lib.ptr(gf), _lib.ptr(gw1), _lib.ptr(gw2), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dg2),
-                         _lib.ptr(db2), _lib.stream()), name)
+        _lib.launch(name, _lib.ptr(xyz), _lib.ptr(features) if C else None, _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(row_start), M, N, C,
+                    ns, _lib.ptr(w1c), _lib.ptr(g1.detach()), _lib.ptr(b1.detach()), C1, _lib.ptr(w2c), _lib.ptr(g2.detach()),
+                    _lib.ptr(b2.detach()), C2, _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(sm1), _lib.ptr(si1), _lib.ptr(sm2), _lib.ptr(si2),
+                    _lib.ptr(sel), _lib.ptr(arg), _lib.ptr(out), _lib.ptr(grad_out.contiguous()), _lib.ptr(scratch), _lib.ptr(dy1),
+                    _lib.ptr(aux), _lib.ptr(scatter), _lib.ptr(gf), _lib.ptr(gw1), _lib.ptr(gw2), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dg2),
+                    _lib.ptr(db2))
         s1, s2 = ctx.w_shapes
         return (None, gf, None, None, None, gw1.view(s1), dg1, db1, gw2.view(s2), dg2, db2, None, None, None, None, None, None, None, None)
 

@@ -82,7 +82,6 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         return hit[1]
 
     def _fused_scale(self, k, xyz, new_xyz, new_coords, features, voxel2point_indices):
-        lib = _lib.load()
         g = self.groupers[k]
         w_in, b_in, w_pos, b_pos, w_out, b_out = self._folded_weights(k)
         M, N = new_xyz.shape[0], xyz.shape[0]
@@ -92,8 +91,8 @@ class NeighborVoxelSAModuleMSG(nn.Module):
                                                  voxel2point_indices, idx)
         f_in = dense_ops._gemm_nt(features, w_in, b_in, dense_ops.ACT_NONE, 0.0)                       # (N, C1)
         pooled = torch.empty((M, w_in.shape[0]), dtype=torch.float32, device=new_xyz.device)
-        _lib.check(lib.sv_voxel_pool_max(_lib.ptr(f_in), _lib.ptr(xyz), _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(w_pos), _lib.ptr(b_pos), M, N,
-                                         w_in.shape[0], g.nsample, _lib.ptr(pooled), _lib.stream()), "sv_voxel_pool_max")
+        _lib.launch("sv_voxel_pool_max", _lib.ptr(f_in), _lib.ptr(xyz), _lib.ptr(new_xyz), _lib.ptr(idx), _lib.ptr(w_pos), _lib.ptr(b_pos), M, N, w_in.shape[0],
+                    g.nsample, _lib.ptr(pooled))
         return dense_ops._gemm_nt(pooled, w_out, b_out, dense_ops.ACT_RELU, 0.0)                       # (M, C2)
 
     def _tree_scale(self, k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices):

@@ -12,15 +12,12 @@ from .... import _lib
 
 
 def points_in_boxes_gpu(boxes_tensor, pts_tensor, box_idx_of_points_tensor):
-    _lib.require_cuda(boxes_tensor, pts_tensor, box_idx_of_points_tensor)
     assert boxes_tensor.dtype == pts_tensor.dtype == torch.float32 and box_idx_of_points_tensor.dtype == torch.int32
     assert boxes_tensor.is_contiguous() and pts_tensor.is_contiguous() and box_idx_of_points_tensor.is_contiguous()
     batch, nbox, npts = boxes_tensor.shape[0], boxes_tensor.shape[1], pts_tensor.shape[1]
     assert boxes_tensor.shape[2] == 7 and pts_tensor.shape[2] == 3 and tuple(box_idx_of_points_tensor.shape) == (batch, npts)
-    lib = _lib.load()
-    _lib.check(lib.sv_points_in_boxes(_lib.ptr(boxes_tensor) if boxes_tensor.numel() else None, _lib.ptr(pts_tensor) if pts_tensor.numel() else None,
-                                      batch, nbox, npts, _lib.ptr(box_idx_of_points_tensor) if box_idx_of_points_tensor.numel() else None, _lib.stream()),
-               "sv_points_in_boxes")
+    _lib.launch("sv_points_in_boxes", _lib.ptr(boxes_tensor) if boxes_tensor.numel() else None, _lib.ptr(pts_tensor) if pts_tensor.numel() else None, batch,
+                nbox, npts, _lib.ptr(box_idx_of_points_tensor) if box_idx_of_points_tensor.numel() else None)
     return 1
 
 
@@ -29,9 +26,8 @@ def points_in_boxes_cpu(boxes_tensor, pts_tensor, pts_indices_tensor, device="cu
     assert pts_indices_tensor.dtype == torch.int32 and tuple(pts_indices_tensor.shape) == (boxes_tensor.shape[0], pts_tensor.shape[0])
     b, p = boxes_tensor.float().contiguous().to(device), pts_tensor.float().contiguous().to(device)
     out = torch.zeros((b.shape[0], p.shape[0]), dtype=torch.int32, device=p.device)
-    lib = _lib.load()
-    _lib.check(lib.sv_points_in_boxes_matrix(_lib.ptr(b) if b.numel() else None, _lib.ptr(p) if p.numel() else None, b.shape[0], p.shape[0],
-                                             _lib.ptr(out) if out.numel() else None, _lib.stream()), "sv_points_in_boxes_matrix")
+    _lib.launch("sv_points_in_boxes_matrix", _lib.ptr(b) if b.numel() else None, _lib.ptr(p) if p.numel() else None, b.shape[0], p.shape[0],
+                _lib.ptr(out) if out.numel() else None)
     pts_indices_tensor.copy_(out.cpu())
     return 1
 

@@ -49,17 +49,15 @@ def assign_points_to_cells(rois, pts, out_size, max_pts_each_voxel, box_pt_range
     pts inside the box that fall into the cell, ascending.  box_pt_range (N, 2) int32: box b looks at rows [lo, hi) only.  The tensor is not
     zero-filled: slots behind a count hold whatever the allocation held."""
     assert rois.shape[1] == 7 and pts.shape[1] == 3
-    _lib.require_cuda(rois, pts, box_pt_range)
     out_x, out_y, out_z = _out_xyz(out_size)
     rois, pts = rois.contiguous().float(), pts.contiguous().float()
     if box_pt_range is not None:
         assert box_pt_range.dtype == torch.int32 and tuple(box_pt_range.shape) == (rois.shape[0], 2)
         box_pt_range = box_pt_range.contiguous()
     lists = torch.empty((rois.shape[0], out_x, out_y, out_z, max_pts_each_voxel), dtype=torch.int32, device=rois.device)
-    _lib.check(_lib.load().sv_roiaware_assign(_lib.ptr(rois) if rois.numel() else None, rois.shape[0], _lib.ptr(pts) if pts.numel() else None,
-                                              pts.shape[0], _lib.ptr(box_pt_range) if box_pt_range is not None and box_pt_range.numel() else None,
-                                              out_x, out_y, out_z, max_pts_each_voxel, _lib.ptr(lists) if lists.numel() else None, _lib.stream()),
-               "sv_roiaware_assign")
+    _lib.launch("sv_roiaware_assign", _lib.ptr(rois) if rois.numel() else None, rois.shape[0], _lib.ptr(pts) if pts.numel() else None, pts.shape[0],
+                _lib.ptr(box_pt_range) if box_pt_range is not None and box_pt_range.numel() else None, out_x, out_y, out_z, max_pts_each_voxel,
+                _lib.ptr(lists) if lists.numel() else None)
     return lists
 
 
@@ -68,7 +66,6 @@ class RoIAwarePoolFromListsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pts_feature, pts_idx_of_voxels, pool_method):
-        _lib.require_cuda(pts_feature, pts_idx_of_voxels)
         assert pts_feature.dim() == 2 and pts_idx_of_voxels.dtype == torch.int32 and pts_idx_of_voxels.dim() == 5
         method = POOL_METHODS[pool_method]
         feat = pts_feature.contiguous().float()
@@ -77,10 +74,8 @@ class RoIAwarePoolFromListsFunction(torch.autograd.Function):
         c = feat.shape[1]
         pooled = torch.empty((n, ox, oy, oz, c), dtype=torch.float32, device=feat.device)
         argmax = torch.empty((n, ox, oy, oz, c), dtype=torch.int32, device=feat.device) if method == 0 else None
-        _lib.check(_lib.load().sv_roiaware_pool(_lib.ptr(feat) if feat.numel() else None, c, _lib.ptr(lists) if lists.numel() else None, n,
-                                                ox * oy * oz, cap, method, _lib.ptr(pooled) if pooled.numel() else None,
-                                                _lib.ptr(argmax) if argmax is not None and argmax.numel() else None, _lib.stream()),
-                   "sv_roiaware_pool")
+        _lib.launch("sv_roiaware_pool", _lib.ptr(feat) if feat.numel() else None, c, _lib.ptr(lists) if lists.numel() else None, n, ox * oy * oz, cap, method,
+                    _lib.ptr(pooled) if pooled.numel() else None, _lib.ptr(argmax) if argmax is not None and argmax.numel() else None)
         ctx.roiaware_pool3d_for_backward = (lists, argmax, method, feat.shape[0], c)
         return pooled
 
@@ -100,10 +95,10 @@ class RoIAwarePoolFromListsFunction(torch.autograd.Function):
             if nbytes == 0:
                 raise _lib.SeevcnHipError("roiaware pooling: the order-fixed gradient needs fewer than 2^31 keys")
             scratch = _lib.workspace.scratch("roiaware_pool_ordered", nbytes, grad_out.device)
-            _lib.check(lib.sv_roiaware_pool_backward_ordered(*args, _lib.ptr(scratch), gi, _lib.stream()), "sv_roiaware_pool_backward_ordered")
+            _lib.launch("sv_roiaware_pool_backward_ordered", *args, _lib.ptr(scratch), gi)
             ordered.count_call("roiaware_pool")
         else:
-            _lib.check(lib.sv_roiaware_pool_backward(*args, gi, _lib.stream()), "sv_roiaware_pool_backward")
+            _lib.launch("sv_roiaware_pool_backward", *args, gi)
         return grad_in, None, None
 
 

@@ -23,7 +23,6 @@ def voxelize_dynamic(points, pc_range, voxel_size, grid_size, batch_size, num_fe
     int32 count is returned as a 4th value instead of narrowing (no host sync; graph-capturable).
     """
     lib = _lib.load()
-    _lib.require_cuda(points)
     assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] >= 4
     points = points.contiguous()
     P, stride = points.shape
@@ -40,10 +39,8 @@ def voxelize_dynamic(points, pc_range, voxel_size, grid_size, batch_size, num_fe
     p2v = torch.empty((P,), dtype=torch.int32, device=dev) if return_point_to_voxel else None
     nvox = torch.empty((1,), dtype=torch.int32, device=dev)
     r, v, g = _geom(pc_range, voxel_size, grid_size)
-    rc = lib.sv_voxelize_dynamic(_lib.ptr(points), P, stride, C, r, v, g, int(batch_size), _lib.ptr(ws),
-                                 _lib.ptr(scratch), _lib.ptr(coords), _lib.ptr(feats), _lib.ptr(p2v), cap,
-                                 _lib.ptr(nvox), _lib.stream())
-    _lib.check(rc, "sv_voxelize_dynamic")
+    _lib.launch("sv_voxelize_dynamic", _lib.ptr(points), P, stride, C, r, v, g, int(batch_size), _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(coords),
+                _lib.ptr(feats), _lib.ptr(p2v), cap, _lib.ptr(nvox))
     if not sync:
         return feats, coords, p2v, nvox
     n = _lib.host_int(nvox)
@@ -52,14 +49,11 @@ def voxelize_dynamic(points, pc_range, voxel_size, grid_size, batch_size, num_fe
 
 def mean_vfe(voxels, voxel_num_points):
     """MeanVFE arithmetic (mean_vfe.py:25-29) on (V, max_points, C) hard voxels."""
-    lib = _lib.load()
-    _lib.require_cuda(voxels, voxel_num_points)
     voxels = voxels.contiguous().float()
     nump = voxel_num_points.contiguous().to(torch.int32)
     V, mp, C = voxels.shape
     out = torch.empty((V, C), dtype=torch.float32, device=voxels.device)
-    rc = lib.sv_mean_vfe(_lib.ptr(voxels), _lib.ptr(nump), V, mp, C, _lib.ptr(out), _lib.stream())
-    _lib.check(rc, "sv_mean_vfe")
+    _lib.launch("sv_mean_vfe", _lib.ptr(voxels), _lib.ptr(nump), V, mp, C, _lib.ptr(out))
     return out
 
 
@@ -69,7 +63,6 @@ def voxelize_hard(points, xyz_offset, num_features, scene_cnt, pc_range, voxel_s
     points (ΣP, stride) fp32 cuda; scene_cnt: list/1-D tensor of per-scene point counts.
     Returns voxels (B,max_voxels,max_points,C), coords (B,max_voxels,3) [z,y,x], num_points (B,max_voxels), num_voxels (B)."""
     lib = _lib.load()
-    _lib.require_cuda(points)
     points = points.contiguous().float()
     dev = points.device
     cnt = torch.as_tensor(scene_cnt, dtype=torch.int32, device="cpu")
@@ -84,17 +77,14 @@ def voxelize_hard(points, xyz_offset, num_features, scene_cnt, pc_range, voxel_s
     nump = torch.empty((B, max_voxels), dtype=torch.int32, device=dev)
     nvox = torch.empty((B,), dtype=torch.int32, device=dev)
     r, v, g = _geom(pc_range, voxel_size, grid_size)
-    rc = lib.sv_voxelize_hard(_lib.ptr(points) if total else None, points.shape[1], int(xyz_offset), int(num_features), _lib.ptr(start_d),
-                              _lib.ptr(cnt_d), B, total, max_scene, r, v, g, int(max_points), int(max_voxels), _lib.ptr(scratch),
-                              _lib.ptr(voxels), _lib.ptr(coords), _lib.ptr(nump), _lib.ptr(nvox), _lib.stream())
-    _lib.check(rc, "sv_voxelize_hard")
+    _lib.launch("sv_voxelize_hard", _lib.ptr(points) if total else None, points.shape[1], int(xyz_offset), int(num_features), _lib.ptr(start_d),
+                _lib.ptr(cnt_d), B, total, max_scene, r, v, g, int(max_points), int(max_voxels), _lib.ptr(scratch), _lib.ptr(voxels), _lib.ptr(coords),
+                _lib.ptr(nump), _lib.ptr(nvox))
     return voxels, coords, nump, nvox
 
 
 def pillar_decorate(voxels, voxel_num_points, coords, voxel_size, pc_range, use_absolute_xyz=True, with_distance=False):
     """(V,mp,C) pillars -> (V,mp,C+6[+1]) decorated point features (pillar_vfe.py:94-118)."""
-    lib = _lib.load()
-    _lib.require_cuda(voxels, voxel_num_points, coords)
     voxels = voxels.contiguous().float()
     nump = voxel_num_points.contiguous().to(torch.int32)
     coords = coords.contiguous().to(torch.int32)
@@ -104,7 +94,6 @@ def pillar_decorate(voxels, voxel_num_points, coords, voxel_size, pc_range, use_
     # as doubles: the pillar-centre offset voxel/2 + range start is formed in double and rounded to fp32 once (pillar_vfe.py:79-81)
     vs = _lib.host_array(ctypes.c_double, [float(x) for x in voxel_size])
     rg = _lib.host_array(ctypes.c_double, [float(x) for x in pc_range])
-    rc = lib.sv_pillar_decorate(_lib.ptr(voxels) if V else None, _lib.ptr(nump) if V else None, _lib.ptr(coords) if V else None, V, mp, C, vs, rg,
-                                int(use_absolute_xyz), int(with_distance), _lib.ptr(out) if V else None, _lib.stream())
-    _lib.check(rc, "sv_pillar_decorate")
+    _lib.launch("sv_pillar_decorate", _lib.ptr(voxels) if V else None, _lib.ptr(nump) if V else None, _lib.ptr(coords) if V else None, V, mp, C, vs, rg,
+                int(use_absolute_xyz), int(with_distance), _lib.ptr(out) if V else None)
     return out

@@ -50,5 +50,5 @@ def remove_points_in_boxes3d(points, boxes3d):
     start = torch.tensor([0, m], dtype=torch.int32, device=dev)
     z32 = zeros.to(torch.int32)
     A.call("sv_gt_sample_paste", *batch._pt_args(), L.ptr(z32[:1]), L.ptr(batch.keep), 1, n, None, L.ptr(zeros), L.ptr(batch.boxes), 7, L.ptr(idx),
-           L.ptr(start), L.ptr(z32[:m + 1]), L.ptr(z32[:m]), L.ptr(ones), m, 0, 0.0, 0.0, 0.0, L.stream())
+           L.ptr(start), L.ptr(z32[:m + 1]), L.ptr(z32[:m]), L.ptr(ones), m, 0, 0.0, 0.0, 0.0)
     return points[batch.keep[:n].bool()]

@@ -71,13 +71,10 @@ def scatter_voxel_rows(indices, volume, fill=True, clear=False):
     """volume (B, Z, Y, X) int32 <- row r at [b, z, y, x] of row r of indices (N, 4) (sv_voxel2pinds: 64-bit offsets).  fill: -1 everywhere first;
     clear: write -1 where the rows are, which returns a volume that was all -1 before the scatter to all -1."""
     from ... import _lib
-    lib = _lib.load()
-    _lib.require_cuda(indices, volume)
     assert volume.dtype == torch.int32 and volume.dim() == 4
     ind = indices if indices.dtype == torch.int32 else indices.int()
     B, Z, Y, X = volume.shape
-    _lib.check(lib.sv_voxel2pinds(_lib.ptr(ind.contiguous()), int(ind.shape[0]), int(B), int(Z), int(Y), int(X), int(fill), int(clear), _lib.ptr(volume),
-                                  _lib.stream()), "sv_voxel2pinds")
+    _lib.launch("sv_voxel2pinds", _lib.ptr(ind.contiguous()), int(ind.shape[0]), int(B), int(Z), int(Y), int(X), int(fill), int(clear), _lib.ptr(volume))
     return volume
 
 

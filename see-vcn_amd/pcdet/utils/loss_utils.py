@@ -18,26 +18,22 @@ class _FocalFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, target, weights, alpha, gamma):
-        lib = _lib.load()
         x, t = input.contiguous().float(), target.contiguous().float()
         w = None if weights is None else weights.contiguous().float()
         c = x.shape[-1]
         out = torch.empty_like(x)
-        _lib.check(lib.sv_sigmoid_focal_loss(_lib.ptr(x), _lib.ptr(t), _lib.ptr(w), x.numel() // c, c, float(alpha), float(gamma), None, _lib.ptr(out),
-                                             _lib.stream()), "sv_sigmoid_focal_loss")
+        _lib.launch("sv_sigmoid_focal_loss", _lib.ptr(x), _lib.ptr(t), _lib.ptr(w), x.numel() // c, c, float(alpha), float(gamma), None, _lib.ptr(out))
         ctx.save_for_backward(x, t, w)
         ctx.alpha, ctx.gamma = float(alpha), float(gamma)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, t, w = ctx.saved_tensors
         g = grad_out.contiguous().float()
         c = x.shape[-1]
         gin = torch.empty_like(x)
-        _lib.check(lib.sv_sigmoid_focal_loss(_lib.ptr(x), _lib.ptr(t), _lib.ptr(w), x.numel() // c, c, ctx.alpha, ctx.gamma, _lib.ptr(g), _lib.ptr(gin),
-                                             _lib.stream()), "sv_sigmoid_focal_loss (gradient)")
+        _lib.launch("sv_sigmoid_focal_loss", _lib.ptr(x), _lib.ptr(t), _lib.ptr(w), x.numel() // c, c, ctx.alpha, ctx.gamma, _lib.ptr(g), _lib.ptr(gin))
         return gin, None, None, None, None
 
 
@@ -46,26 +42,23 @@ class _SmoothL1Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, target, code_weights, weights, beta):
-        lib = _lib.load()
         x, t = input.contiguous().float(), target.contiguous().float()
         w = None if weights is None else weights.contiguous().float()
         c = x.shape[-1]
         out = torch.empty_like(x)
-        _lib.check(lib.sv_weighted_smooth_l1_loss(_lib.ptr(x), _lib.ptr(t), _lib.ptr(code_weights), _lib.ptr(w), x.numel() // c, c, float(beta), None,
-                                                  _lib.ptr(out), _lib.stream()), "sv_weighted_smooth_l1_loss")
+        _lib.launch("sv_weighted_smooth_l1_loss", _lib.ptr(x), _lib.ptr(t), _lib.ptr(code_weights), _lib.ptr(w), x.numel() // c, c, float(beta), None,
+                    _lib.ptr(out))
         ctx.save_for_backward(x, t, code_weights, w)
         ctx.beta = float(beta)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, t, cw, w = ctx.saved_tensors
         g = grad_out.contiguous().float()
         c = x.shape[-1]
         gin = torch.empty_like(x)
-        _lib.check(lib.sv_weighted_smooth_l1_loss(_lib.ptr(x), _lib.ptr(t), _lib.ptr(cw), _lib.ptr(w), x.numel() // c, c, ctx.beta, _lib.ptr(g), _lib.ptr(gin),
-                                                  _lib.stream()), "sv_weighted_smooth_l1_loss (gradient)")
+        _lib.launch("sv_weighted_smooth_l1_loss", _lib.ptr(x), _lib.ptr(t), _lib.ptr(cw), _lib.ptr(w), x.numel() // c, c, ctx.beta, _lib.ptr(g), _lib.ptr(gin))
         return gin, None, None, None, None
 
 

@@ -17,7 +17,6 @@ def _shape3(shape):
 
 
 def _check_inputs(indices, s):
-    _lib.require_cuda(indices, s)
     assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4, "indices: (n, 4) int32 [b, z, y, x]"
     assert s.dtype == torch.float32 and s.shape == (indices.shape[0], N_IMPORTANCE), "s: (n, 27) fp32 = sigmoid(imps)"
 
@@ -37,8 +36,7 @@ def focal_select(s, indices, batch_size, topk, threshold):
     n = indices.shape[0]
     fore = torch.empty((n,), dtype=torch.uint8, device=s.device)
     scratch = _lib.workspace.scratch("focal_select", lib.sv_focal_select_scratch_bytes(int(batch_size)), s.device) if topk else None
-    _lib.check(lib.sv_focal_select(_lib.ptr(s), _lib.ptr(indices), n, int(batch_size), int(bool(topk)), float(threshold), _lib.ptr(scratch),
-                                   _lib.ptr(fore), _lib.stream()), "sv_focal_select")
+    _lib.launch("sv_focal_select", _lib.ptr(s), _lib.ptr(indices), n, int(batch_size), int(bool(topk)), float(threshold), _lib.ptr(scratch), _lib.ptr(fore))
     return fore
 
 
@@ -48,7 +46,6 @@ def focal_cells(indices, s, fore, batch_size, spatial_shape, threshold, capacity
     a larger set raises and nothing is written past capacity.  out_coords: a caller's buffer of at least capacity rows."""
     lib = _lib.load()
     _check_inputs(indices, s)
-    _lib.require_cuda(fore, out_coords)
     assert fore.dtype == torch.uint8 and fore.shape == (indices.shape[0],)
     s, indices, fore = s.contiguous(), indices.contiguous(), fore.contiguous()
     n, dev = indices.shape[0], indices.device
@@ -62,9 +59,8 @@ def focal_cells(indices, s, fore, batch_size, spatial_shape, threshold, capacity
     scratch = _lib.workspace.scratch("focal_expand", lib.sv_focal_expand_scratch_bytes(ncells), dev)
     row_of_in = torch.empty((n,), dtype=torch.int32, device=dev)
     num_out = torch.empty((1,), dtype=torch.int32, device=dev)
-    _lib.check(lib.sv_focal_expand(_lib.ptr(indices), _lib.ptr(s), _lib.ptr(fore), n, int(batch_size), _shape3(spatial_shape), float(threshold),
-                                   _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(out_coords), _lib.ptr(row_of_in), capacity, _lib.ptr(num_out),
-                                   _lib.stream()), "sv_focal_expand")
+    _lib.launch("sv_focal_expand", _lib.ptr(indices), _lib.ptr(s), _lib.ptr(fore), n, int(batch_size), _shape3(spatial_shape), float(threshold), _lib.ptr(ws),
+                _lib.ptr(scratch), _lib.ptr(out_coords), _lib.ptr(row_of_in), capacity, _lib.ptr(num_out))
     n_out = _lib.host_int(num_out)          # the host allocates the output rows: the one read of a focal layer
     if n_out > capacity:
         raise _lib.SeevcnHipError(f"sv_focal_expand: the expanded set has {n_out} cells, the capacity is {capacity}")
@@ -78,8 +74,6 @@ class FocalExpandFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, s, indices, nbr, batch_size, spatial_shape, topk, threshold, mask_multi, skip_mask_kernel, capacity):
-        lib = _lib.load()
-        _lib.require_cuda(features, s, indices, nbr)
         features, s, indices = features.contiguous().float(), s.contiguous(), indices.contiguous()
         n, C = features.shape
         assert nbr.dtype == torch.int32 and nbr.shape == (N_IMPORTANCE, n) and nbr.is_contiguous(), "nbr: the (27, n) submanifold table of the input set"
@@ -89,9 +83,8 @@ class FocalExpandFunction(torch.autograd.Function):
         out = torch.empty((n_out, C), dtype=torch.float32, device=dev)
         w = torch.empty((n,), dtype=torch.float32, device=dev)
         cnt = torch.empty((n,), dtype=torch.int32, device=dev)
-        _lib.check(lib.sv_focal_place(_lib.ptr(features), _lib.ptr(s), _lib.ptr(indices), _lib.ptr(fore), _lib.ptr(nbr), _lib.ptr(row_of_in), n, C,
-                                      int(bool(mask_multi)), int(bool(skip_mask_kernel)), float(threshold), n_out, _lib.ptr(w), _lib.ptr(cnt),
-                                      _lib.ptr(out), _lib.stream()), "sv_focal_place")
+        _lib.launch("sv_focal_place", _lib.ptr(features), _lib.ptr(s), _lib.ptr(indices), _lib.ptr(fore), _lib.ptr(nbr), _lib.ptr(row_of_in), n, C,
+                    int(bool(mask_multi)), int(bool(skip_mask_kernel)), float(threshold), n_out, _lib.ptr(w), _lib.ptr(cnt), _lib.ptr(out))
         ctx.save_for_backward(features, s, indices, fore, nbr, row_of_in, w, cnt)
         ctx.flags = (int(bool(mask_multi)), int(bool(skip_mask_kernel)), float(threshold))
         ctx.mark_non_differentiable(out_indices, fore, row_of_in)
@@ -99,7 +92,6 @@ class FocalExpandFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, _gi, _gf, _gr):
-        lib = _lib.load()
         features, s, indices, fore, nbr, row_of_in, w, cnt = ctx.saved_tensors
         mask_multi, skip_mask_kernel, threshold = ctx.flags
         n, C = features.shape
@@ -107,9 +99,9 @@ class FocalExpandFunction(torch.autograd.Function):
         grad_f = torch.empty_like(features)
         grad_s = torch.empty_like(s)
         dots = torch.empty((n,), dtype=torch.float32, device=features.device)
-        _lib.check(lib.sv_focal_backward(_lib.ptr(grad_out), _lib.ptr(features), _lib.ptr(s), _lib.ptr(indices), _lib.ptr(fore), _lib.ptr(nbr),
-                                         _lib.ptr(row_of_in), _lib.ptr(w), _lib.ptr(cnt), n, C, mask_multi, skip_mask_kernel, threshold,
-                                         _lib.ptr(dots), _lib.ptr(grad_f), _lib.ptr(grad_s), _lib.stream()), "sv_focal_backward")
+        _lib.launch("sv_focal_backward", _lib.ptr(grad_out), _lib.ptr(features), _lib.ptr(s), _lib.ptr(indices), _lib.ptr(fore), _lib.ptr(nbr),
+                    _lib.ptr(row_of_in), _lib.ptr(w), _lib.ptr(cnt), n, C, mask_multi, skip_mask_kernel, threshold, _lib.ptr(dots), _lib.ptr(grad_f),
+                    _lib.ptr(grad_s))
         return grad_f, grad_s, None, None, None, None, None, None, None, None, None
 
 
@@ -139,8 +131,6 @@ def image_aug_table(batch_dict, batch_size, device):
 def focal_image_pixels(indices, batch_size, voxel_stride, voxel_size, origin, calib_table, aug_table, image_hw):
     """pix (n) int32 = v * W + u of every row's projection into its scene's image, -1 outside (sv_focal_image_pixels).  voxel_size / origin: the
     layer's z-first host values; calib_table (B, 24), aug_table (B, 4) fp32 on the device.  No host read."""
-    lib = _lib.load()
-    _lib.require_cuda(indices, calib_table, aug_table)
     assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4, "indices: (n, 4) int32 [b, z, y, x]"
     assert calib_table.dtype == torch.float32 and calib_table.shape == (batch_size, 24), "calib_table: (B, 24) fp32 = [V2C^T R0^T (4 x 3) | P2 (3 x 4)]"
     assert aug_table.dtype == torch.float32 and aug_table.shape == (batch_size, 4), "aug_table: (B, 4) fp32"
@@ -149,9 +139,8 @@ def focal_image_pixels(indices, batch_size, voxel_stride, voxel_size, origin, ca
     pix = torch.empty((n,), dtype=torch.int32, device=indices.device)
     vs = _lib.host_array(ctypes.c_float, [float(v) for v in voxel_size])
     org = _lib.host_array(ctypes.c_float, [float(v) for v in origin])
-    _lib.check(lib.sv_focal_image_pixels(_lib.ptr(indices), n, int(batch_size), int(voxel_stride), vs, org, _lib.ptr(calib_table.contiguous()),
-                                         _lib.ptr(aug_table.contiguous()), int(image_hw[0]), int(image_hw[1]), _lib.ptr(pix), _lib.stream()),
-               "sv_focal_image_pixels")
+    _lib.launch("sv_focal_image_pixels", _lib.ptr(indices), n, int(batch_size), int(voxel_stride), vs, org, _lib.ptr(calib_table.contiguous()),
+                _lib.ptr(aug_table.contiguous()), int(image_hw[0]), int(image_hw[1]), _lib.ptr(pix))
     return pix
 
 
@@ -162,16 +151,13 @@ class FocalImageSampleFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, f, features, indices, pix, image_hw, fuse_sum):
-        lib = _lib.load()
-        _lib.require_cuda(f, features, indices, pix)
         f, features, indices, pix = f.contiguous().float(), features.contiguous().float(), indices.contiguous(), pix.contiguous()
         (n, Cv), (B, h, w, C) = f.shape, features.shape
         assert indices.dtype == torch.int32 and indices.shape == (n, 4) and pix.dtype == torch.int32 and pix.shape == (n,)
         mode = int(bool(fuse_sum))
         H, W = int(image_hw[0]), int(image_hw[1])
         out = torch.empty((n, Cv if mode else C + Cv), dtype=torch.float32, device=f.device)
-        _lib.check(lib.sv_focal_image_sample(_lib.ptr(features), B, h, w, C, H, W, _lib.ptr(f), Cv, _lib.ptr(indices), _lib.ptr(pix), n, mode,
-                                             _lib.ptr(out), _lib.stream()), "sv_focal_image_sample")
+        _lib.launch("sv_focal_image_sample", _lib.ptr(features), B, h, w, C, H, W, _lib.ptr(f), Cv, _lib.ptr(indices), _lib.ptr(pix), n, mode, _lib.ptr(out))
         ctx.save_for_backward(indices, pix)
         ctx.geom = (B, h, w, C, H, W, Cv, mode)
         return out
@@ -191,8 +177,8 @@ class FocalImageSampleFunction(torch.autograd.Function):
                 raise _lib.SeevcnHipError("sv_focal_image_sample_grad: pixel index or tap key exceeds int32")
             scratch = _lib.workspace.scratch("focal_image_grad", nbytes, g.device)
             grad_features = torch.empty((B, h, w, C), dtype=torch.float32, device=g.device)
-            _lib.check(lib.sv_focal_image_sample_grad(_lib.ptr(g), g.shape[1], _lib.ptr(indices), _lib.ptr(pix), n, B, h, w, C, H, W, _lib.ptr(scratch),
-                                                      _lib.ptr(grad_features), _lib.stream()), "sv_focal_image_sample_grad")
+            _lib.launch("sv_focal_image_sample_grad", _lib.ptr(g), g.shape[1], _lib.ptr(indices), _lib.ptr(pix), n, B, h, w, C, H, W, _lib.ptr(scratch),
+                        _lib.ptr(grad_features))
         return grad_f, grad_features, None, None, None, None
 
 

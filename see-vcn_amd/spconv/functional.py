@@ -64,7 +64,7 @@ class TablePlan(_ArenaViews):
         if rows is None or masks is None:
             rows = torch.empty((max(self.n_rows, 1), 32), dtype=torch.int32, device=dev)
             masks = torch.empty((max(self.n_rows, 1),), dtype=torch.int32, device=dev)
-            _lib.check(lib.sv_conv_table_rows(_lib.ptr(table), self.n_rows, self.K, _lib.ptr(rows), _lib.ptr(masks), _lib.stream()), "sv_conv_table_rows")
+            _lib.launch("sv_conv_table_rows", _lib.ptr(table), self.n_rows, self.K, _lib.ptr(rows), _lib.ptr(masks))
         self.rows, self.masks = rows, masks
         n_perm = lib.sv_conv_plan_perm_bytes(self.n_rows) // 4
         self.perm = torch.empty((n_perm,), dtype=torch.int32, device=dev)
@@ -73,13 +73,11 @@ class TablePlan(_ArenaViews):
         if g is not None and FUSED_PLAN:
             # regrouping + the tile deal for this tiles-per-wave value in one launch (one workgroup per region)
             t = torch.empty((lib.sv_conv_plan_tiles_bytes(self.n_rows, int(g)) // 4,), dtype=torch.int32, device=dev)
-            _lib.check(lib.sv_conv_plan_build_dealt(_lib.ptr(masks), self.n_rows, int(g), _lib.ptr(self.perm), _lib.ptr(self.masks_p), _lib.ptr(t),
-                                                    _lib.stream()), "sv_conv_plan_build_dealt")
+            _lib.launch("sv_conv_plan_build_dealt", _lib.ptr(masks), self.n_rows, int(g), _lib.ptr(self.perm), _lib.ptr(self.masks_p), _lib.ptr(t))
             self._tiles[int(g)] = t
             return
         hist = _lib.workspace.persistent("conv_plan_hist", lib.sv_conv_plan_persistent_bytes(), dev)
-        _lib.check(lib.sv_conv_plan_build(_lib.ptr(masks), self.n_rows, _lib.ptr(hist), _lib.ptr(self.perm), _lib.ptr(self.masks_p), _lib.stream()),
-                   "sv_conv_plan_build")
+        _lib.launch("sv_conv_plan_build", _lib.ptr(masks), self.n_rows, _lib.ptr(hist), _lib.ptr(self.perm), _lib.ptr(self.masks_p))
 
     @classmethod
     def from_parts(cls, table, n_rows, K, rows, masks, perm, masks_p, g, tile_of):
@@ -126,7 +124,7 @@ class TablePlan(_ArenaViews):
         if g not in self._tiles:
             lib = _lib.load()
             t = torch.empty((lib.sv_conv_plan_tiles_bytes(self.n_rows, g) // 4,), dtype=torch.int32, device=self.perm.device)
-            _lib.check(lib.sv_conv_plan_tiles(_lib.ptr(self.masks_p), self.n_rows, g, _lib.ptr(t), _lib.stream()), "sv_conv_plan_tiles")
+            _lib.launch("sv_conv_plan_tiles", _lib.ptr(self.masks_p), self.n_rows, g, _lib.ptr(t))
             self._tiles[g] = t
         return self._tiles[g]
 
@@ -237,17 +235,15 @@ class Rulebook(_ArenaViews):
             if pieces not in plans:
                 nbr = self.nbr_out
                 buf = torch.empty((lib.sv_wgrad_plan_bytes(self.n_out, int(self.K), pieces),), dtype=torch.uint8, device=nbr.device)
-                _lib.check(lib.sv_wgrad_plan_build(_lib.ptr(nbr), self.n_out, int(self.K), pieces, buf.data_ptr(), _lib.stream()), "sv_wgrad_plan_build")
+                _lib.launch("sv_wgrad_plan_build", _lib.ptr(nbr), self.n_out, int(self.K), pieces, buf.data_ptr())
                 plans[pieces] = buf
             out = plans[pieces]
         self._plan_results[key] = (out,)
         return out
 
     def pair_counts(self):
-        lib = _lib.load()
         counts = torch.empty((self.K,), dtype=torch.int32, device=self.nbr_out.device)
-        _lib.check(lib.sv_rulebook_pair_counts(_lib.ptr(self.nbr_out), self.n_out, self.K, _lib.ptr(counts), _lib.stream()),
-                   "sv_rulebook_pair_counts")
+        _lib.launch("sv_rulebook_pair_counts", _lib.ptr(self.nbr_out), self.n_out, self.K, _lib.ptr(counts))
         return counts
 
 
@@ -287,7 +283,6 @@ WGRAD_PLANNED = os.environ.get("SEEVCN_WGRAD_PLANNED", "1") != "0"   # 0: weight
 
 def build_subm_rulebook(indices, batch_size, spatial_shape, ksize, dilation=(1, 1, 1)):
     lib = _lib.load()
-    _lib.require_cuda(indices)
     assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4
     indices = indices.contiguous()
     n = indices.shape[0]
@@ -302,18 +297,16 @@ def build_subm_rulebook(indices, batch_size, spatial_shape, ksize, dilation=(1, 
         with_rows = K <= 27 and n > 0
         rows = torch.empty((n, 32), dtype=torch.int32, device=dev) if with_rows else None
         masks = torch.empty((n,), dtype=torch.int32, device=dev) if with_rows else None
-        rc = lib.sv_rulebook_subm_cellmap(_lib.ptr(indices), n, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(dilation),
-                                          _lib.ptr(cellmap), _lib.ptr(nbr), _lib.ptr(rows), _lib.ptr(masks), _lib.stream())
-        _lib.check(rc, "sv_rulebook_subm_cellmap")
+        _lib.launch("sv_rulebook_subm_cellmap", _lib.ptr(indices), n, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(dilation), _lib.ptr(cellmap),
+                    _lib.ptr(nbr), _lib.ptr(rows), _lib.ptr(masks))
         rb = Rulebook(nbr, None, indices, list(spatial_shape), n, n, True, list(ksize))
         rb.rows_out, rb.masks_out = rows, masks
         rb.dilation = [int(d) for d in dilation]
         return rb
     ws = _lib.workspace.persistent(f"rb_index_{tuple(spatial_shape)}_{batch_size}", lib.sv_index_persistent_bytes(ncells), dev)
     scratch = _lib.workspace.scratch("rb_scratch", lib.sv_rulebook_scratch_bytes(n, ncells), dev)
-    rc = lib.sv_rulebook_subm(_lib.ptr(indices), n, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(dilation),
-                              _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(nbr), _lib.stream())
-    _lib.check(rc, "sv_rulebook_subm")
+    _lib.launch("sv_rulebook_subm", _lib.ptr(indices), n, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(dilation), _lib.ptr(ws), _lib.ptr(scratch),
+                _lib.ptr(nbr))
     rb = Rulebook(nbr, None, indices, list(spatial_shape), n, n, True, list(ksize))
     rb.dilation = [int(d) for d in dilation]          # recorded by this builder only: a table may be shared between keys when kernel and dilation agree
     return rb
@@ -321,7 +314,6 @@ def build_subm_rulebook(indices, batch_size, spatial_shape, ksize, dilation=(1, 
 
 def build_sparse_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, dilation=(1, 1, 1)):
     lib = _lib.load()
-    _lib.require_cuda(indices)
     assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4
     indices = indices.contiguous()
     n_in = indices.shape[0]
@@ -341,21 +333,17 @@ def build_sparse_rulebook(indices, batch_size, spatial_shape, ksize, stride, pad
     num_out = torch.empty((1,), dtype=torch.int32, device=dev)      # zeroed by sv_rulebook_sparse
     with_rows = K <= 27 and n_in > 0
     in_block = torch.empty((33 * n_in,), dtype=torch.int32, device=dev) if with_rows else None     # [rows (n_in, 32) | masks (n_in)]
-    rc = lib.sv_rulebook_sparse(_lib.ptr(indices), n_in, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(stride),
-                                _i3(padding), _i3(dilation), _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(out_coords),
-                                _lib.ptr(nbr_in) if n_in else None, _lib.ptr(in_block), cap, _lib.ptr(num_out), _lib.stream())
-    _lib.check(rc, "sv_rulebook_sparse")
+    _lib.launch("sv_rulebook_sparse", _lib.ptr(indices), n_in, int(batch_size), _i3(spatial_shape), _i3(ksize), _i3(stride), _i3(padding), _i3(dilation),
+                _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(out_coords), _lib.ptr(nbr_in) if n_in else None, _lib.ptr(in_block), cap, _lib.ptr(num_out))
     n_out = _lib.host_int(num_out)  # host needs the size to allocate the output rows (spconv syncs here too)
     out_coords = out_coords[:n_out]
     if not with_rows or n_out == 0:
         nbr_out = torch.empty((K, n_out), dtype=torch.int32, device=dev)
-        rc = lib.sv_rulebook_invert(_lib.ptr(nbr_in) if n_in else None, n_in, K, _lib.ptr(nbr_out) if n_out else None, n_out, _lib.stream())
-        _lib.check(rc, "sv_rulebook_invert")
+        _lib.launch("sv_rulebook_invert", _lib.ptr(nbr_in) if n_in else None, n_in, K, _lib.ptr(nbr_out) if n_out else None, n_out)
         return Rulebook(nbr_out, nbr_in, out_coords, oshape, n_in, n_out, False, list(ksize))
     # one block for the output side: [rows (n_out, 32) | k-major table (K, n_out) | masks (n_out)] -- the row-major twins and masks feed the plans
     out_block = torch.empty(((32 + K + 1) * n_out,), dtype=torch.int32, device=dev)
-    rc = lib.sv_rulebook_invert_rows(_lib.ptr(in_block), n_in, K, _lib.ptr(out_block), n_out, _lib.stream())
-    _lib.check(rc, "sv_rulebook_invert_rows")
+    _lib.launch("sv_rulebook_invert_rows", _lib.ptr(in_block), n_in, K, _lib.ptr(out_block), n_out)
     nbr_out = out_block[32 * n_out:(32 + K) * n_out].view(K, n_out)
     rb = Rulebook(nbr_out, nbr_in, out_coords, oshape, n_in, n_out, False, list(ksize))
     rb.rows_out, rb.masks_out = out_block[:32 * n_out].view(n_out, 32), out_block[(32 + K) * n_out:]
@@ -388,7 +376,6 @@ def build_network_index(coords, batch_size, spatial_shape, specs, n0_dev=None, w
     network does not fit the batch form: a kernel wider than 3, a cell map beyond CELLMAP_MAX_BYTES, more than 8 levels, no rows."""
     import numpy as np
     lib = _lib.load()
-    _lib.require_cuda(coords)
     assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
     coords = coords.contiguous()
     dev, B, cap0 = coords.device, int(batch_size), int(coords.shape[0])
@@ -423,11 +410,9 @@ def build_network_index(coords, batch_size, spatial_shape, specs, n0_dev=None, w
         geoms = []
         for l, sp in enumerate(strided):
             geoms += shapes[l] + sp.ksize + sp.stride + sp.padding + sp.dilation
-        rc = lib.sv_rulebook_chain_count(_lib.ptr(coords), cap0, _lib.ptr(n0_dev), B, L, _lib.host_array(ctypes.c_int32, geoms),
-                                         _lib.host_array(ctypes.c_void_p, [w.data_ptr() for w in works]),
-                                         _lib.host_array(ctypes.c_void_p, [t.data_ptr() for t in sites]), _lib.host_array(ctypes.c_int64, caps),
-                                         _lib.ptr(num_out), _lib.ptr(scratch), _lib.stream())
-        _lib.check(rc, "sv_rulebook_chain_count")
+        _lib.launch("sv_rulebook_chain_count", _lib.ptr(coords), cap0, _lib.ptr(n0_dev), B, L, _lib.host_array(ctypes.c_int32, geoms),
+                    _lib.host_array(ctypes.c_void_p, [w.data_ptr() for w in works]), _lib.host_array(ctypes.c_void_p, [t.data_ptr() for t in sites]),
+                    _lib.host_array(ctypes.c_int64, caps), _lib.ptr(num_out), _lib.ptr(scratch))
     try:
         if L:
             vals = _lib.host_ints(([n0_dev] if n0_dev is not None else []) + [num_out])        # THE read
@@ -515,7 +500,7 @@ def build_network_index(coords, batch_size, spatial_shape, specs, n0_dev=None, w
                 *shapes[l], *shapes[l + 1], *sp.ksize, 1, 1, 1, *sp.padding, *[-d for d in sp.dilation], *sp.stride, B)
     arr = np.array(jobs, dtype=np.int64)
     try:
-        _lib.check(lib.sv_rulebook_batch(arr.ctypes.data, len(jobs), _lib.stream()), "sv_rulebook_batch")
+        _lib.launch("sv_rulebook_batch", arr.ctypes.data, len(jobs))
     except BaseException:
         for w in (works if L else []):                                 # a refused batch leaves phase 1's marks (and maybe map entries) behind:
             w.zero_()                                                  # the persistent workspaces must be all-zero for the next call
@@ -536,7 +521,7 @@ def build_network_index(coords, batch_size, spatial_shape, specs, n0_dev=None, w
             pj.append([masks, pl["n_rows"], pl["g"], addr(pl["perm"]), addr(pl["masks_p"]), addr(pl["tiles"]), 0, 0])
     if pj:
         parr = np.array(pj, dtype=np.int64)
-        _lib.check(lib.sv_conv_plan_build_dealt_batch(parr.ctypes.data, len(pj), _lib.stream()), "sv_conv_plan_build_dealt_batch")
+        _lib.launch("sv_conv_plan_build_dealt_batch", parr.ctypes.data, len(pj))
     # ---- the Rulebook objects: every table a lazy slice of the arena (views are made when something asks for the tensor)
     out = {}
     level_idx = [coords]
@@ -601,7 +586,6 @@ class _FragmentCache:
         """Re-lay the fragments of every (K, C_in, C_out) weight view in `weights` in ONE launch (a backbone calls this at the top of its
         forward); each layer's get() of this forward then takes its pair without a launch of its own.  An entry stays fresh only until it is
         taken once or the next refresh_all."""
-        lib = _lib.load()
         self._fresh.clear()
         weights = [w for w in weights if w.is_cuda and w.dtype == torch.float32 and w.shape[1] % 16 == 0 and w.shape[2] % 16 == 0]
         if not weights:
@@ -621,7 +605,7 @@ class _FragmentCache:
                 self._tables.clear()
             table = torch.tensor(rows, dtype=torch.int64).to(weights[0].device)
             self._tables[sig] = table
-        _lib.check(lib.sv_conv_weight_fragments_batch(_lib.ptr(table), len(rows), unit0, _lib.stream()), "sv_conv_weight_fragments_batch")
+        _lib.launch("sv_conv_weight_fragments_batch", _lib.ptr(table), len(rows), unit0)
         self._fresh.update(keys)
 
     def get(self, weight_kio, refresh=True):
@@ -630,10 +614,8 @@ class _FragmentCache:
         if hit and (not refresh or key in self._fresh):
             self._fresh.discard(key)
             return fwd, bwd
-        lib = _lib.load()
         sk, si, so = weight_kio.stride()
-        _lib.check(lib.sv_conv_weight_fragments(ctypes.c_void_p(weight_kio.data_ptr()), sk, si, so, K, cin, cout, _lib.ptr(fwd), _lib.ptr(bwd), _lib.stream()),
-                   "sv_conv_weight_fragments")
+        _lib.launch("sv_conv_weight_fragments", ctypes.c_void_p(weight_kio.data_ptr()), sk, si, so, K, cin, cout, _lib.ptr(fwd), _lib.ptr(bwd))
         return fwd, bwd
 
     # ---- the half side: fp16 fragment copies for the half-precision eval list (sv_conv_weight_fragments_h16, forward direction only).  Keyed and dropped
@@ -658,7 +640,6 @@ class _FragmentCache:
     def refresh_all_half(self, weights):
         """refresh_all for the fp16 copies: ONE launch (sv_conv_weight_fragments_h16_batch) re-lays every (K, C_in, C_out) view in `weights` that the
         fp16 kernel's layout takes; get_half() of this forward then finds its copy fresh."""
-        lib = _lib.load()
         self._fresh_h.clear()
         weights = [w for w in weights if self.half_layout_applies(w)]
         if not weights:
@@ -678,7 +659,7 @@ class _FragmentCache:
                 self._tables.clear()
             table = torch.tensor(rows, dtype=torch.int64).to(weights[0].device)
             self._tables[sig] = table
-        _lib.check(lib.sv_conv_weight_fragments_h16_batch(_lib.ptr(table), len(rows), unit0, _lib.stream()), "sv_conv_weight_fragments_h16_batch")
+        _lib.launch("sv_conv_weight_fragments_h16_batch", _lib.ptr(table), len(rows), unit0)
         self._fresh_h.update(keys)
 
     def get_half(self, weight_kio):
@@ -688,8 +669,7 @@ class _FragmentCache:
             self._fresh_h.discard(key)
             return frag
         sk, si, so = weight_kio.stride()
-        _lib.check(_lib.load().sv_conv_weight_fragments_h16(ctypes.c_void_p(weight_kio.data_ptr()), sk, si, so, K, cin, cout, _lib.ptr(frag), _lib.stream()),
-                   "sv_conv_weight_fragments_h16")
+        _lib.launch("sv_conv_weight_fragments_h16", ctypes.c_void_p(weight_kio.data_ptr()), sk, si, so, K, cin, cout, _lib.ptr(frag))
         return frag
 
     def clear(self):
@@ -706,16 +686,13 @@ fragment_cache = _FragmentCache()
 def gather_gemm_planned(x, plan, wfrag, n_rows, K, kd, nc, bias=None, scale=None, shift=None, residual=None, relu=False, bn_partial=None):
     """Y (n_rows, nc) = epi(sum_k X[nbr[k]] @ W[k]) on a table plan (Rulebook.plan) with the weights in fragment order.  bn_partial: device address
     (int) of sv_conv_planned_partials() x 2 x nc floats that receive the BatchNorm partial sums of Y (plain epilogue only)."""
-    lib = _lib.load()
     tp, tile_of, g, rev = plan
     assert x.shape[1] == kd and x.dtype == torch.float32
     x = x.contiguous()
     y = torch.empty((n_rows, nc), dtype=torch.float32, device=x.device)
-    rc = lib.sv_sparse_conv_gather_gemm_planned(_lib.ptr(x) if x.numel() else None, x.shape[0], _lib.ptr(tp.rows), _lib.ptr(tp.perm), _lib.ptr(tp.masks_p),
-                                                _lib.ptr(tile_of), int(g), _lib.ptr(wfrag),
-                                                _lib.ptr(y) if n_rows else None, n_rows, int(K), int(kd), int(nc), _lib.ptr(bias), _lib.ptr(scale),
-                                                _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)), int(bool(rev)), bn_partial, _lib.stream())
-    _lib.check(rc, "sv_sparse_conv_gather_gemm_planned")
+    _lib.launch("sv_sparse_conv_gather_gemm_planned", _lib.ptr(x) if x.numel() else None, x.shape[0], _lib.ptr(tp.rows), _lib.ptr(tp.perm),
+                _lib.ptr(tp.masks_p), _lib.ptr(tile_of), int(g), _lib.ptr(wfrag), _lib.ptr(y) if n_rows else None, n_rows, int(K), int(kd), int(nc),
+                _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)), int(bool(rev)), bn_partial)
     return y
 
 
@@ -724,17 +701,15 @@ def gather_gemm_planned_h16(x16, plan, wfrag16, n_rows, K, kd, nc, bias=None, sc
     """Y (n_rows, nc) = store(epi(sum_k X16[nbr[k]] @ W16[k])) on a table plan (Rulebook.plan; its deal is not used) with fp16 rows, fp16 weight fragments
     (fragment_cache.get_half), fp32 accumulation and epilogue; Y is fp16 (round to nearest even) or fp32.  out: a (n_rows, nc) tensor of out_dtype to
     write (it need not be 16-byte aligned)."""
-    lib = _lib.load()
     tp = plan[0]
     assert x16.shape[1] == kd and x16.dtype == torch.float16 and out_dtype in (torch.float16, torch.float32)
     assert residual16 is None or residual16.dtype == torch.float16
     x16 = x16.contiguous()
     y = torch.empty((n_rows, nc), dtype=out_dtype, device=x16.device) if out is None else out
     assert y.dtype == out_dtype and tuple(y.shape) == (n_rows, nc)
-    rc = lib.sv_sparse_conv_gather_gemm_planned_h16(_lib.ptr(x16) if x16.numel() else None, x16.shape[0], _lib.ptr(tp.rows), _lib.ptr(tp.perm), _lib.ptr(tp.masks_p),
-                                                    _lib.ptr(wfrag16), _lib.ptr(y) if n_rows else None, int(out_dtype == torch.float32), n_rows, int(K), int(kd),
-                                                    int(nc), _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual16), int(bool(relu)), _lib.stream())
-    _lib.check(rc, "sv_sparse_conv_gather_gemm_planned_h16")
+    _lib.launch("sv_sparse_conv_gather_gemm_planned_h16", _lib.ptr(x16) if x16.numel() else None, x16.shape[0], _lib.ptr(tp.rows), _lib.ptr(tp.perm),
+                _lib.ptr(tp.masks_p), _lib.ptr(wfrag16), _lib.ptr(y) if n_rows else None, int(out_dtype == torch.float32), n_rows, int(K), int(kd), int(nc),
+                _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual16), int(bool(relu)))
     return y
 
 
@@ -743,23 +718,20 @@ def narrow_h16(x):
     assert x.dtype == torch.float32
     x = x.contiguous()
     y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-    _lib.check(_lib.load().sv_narrow_h16(_lib.ptr(x) if x.numel() else None, x.numel(), _lib.ptr(y) if x.numel() else None, _lib.stream()), "sv_narrow_h16")
+    _lib.launch("sv_narrow_h16", _lib.ptr(x) if x.numel() else None, x.numel(), _lib.ptr(y) if x.numel() else None)
     return y
 
 
 def gather_gemm(x, nbr, wt, n_rows, bias=None, scale=None, shift=None, residual=None, relu=False):
     """Plain kernels: Y (n_rows, Nc) = epi(sum_k X[nbr[k]] @ wt[k].T) with the k-major table and a (K, Nc, Kd) weight (made contiguous here:
     only the 3-channel input layer and odd channel counts come this way)."""
-    lib = _lib.load()
     K, Nc, Kd = wt.shape
     assert x.shape[1] == Kd and nbr.shape[0] == K and wt.dtype == torch.float32
     x = x.contiguous()
     wt = wt.contiguous()
     y = torch.empty((n_rows, Nc), dtype=torch.float32, device=x.device)
-    rc = lib.sv_sparse_conv_gather_gemm(_lib.ptr(x) if x.numel() else None, x.shape[0], _lib.ptr(nbr) if nbr.numel() else None, _lib.ptr(wt),
-                                        _lib.ptr(y) if n_rows else None, n_rows, K, Kd, Nc, _lib.ptr(bias), _lib.ptr(scale),
-                                        _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)), _lib.stream())
-    _lib.check(rc, "sv_sparse_conv_gather_gemm")
+    _lib.launch("sv_sparse_conv_gather_gemm", _lib.ptr(x) if x.numel() else None, x.shape[0], _lib.ptr(nbr) if nbr.numel() else None, _lib.ptr(wt),
+                _lib.ptr(y) if n_rows else None, n_rows, K, Kd, Nc, _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)))
     return y
 
 
@@ -780,17 +752,14 @@ def wgrad(x, nbr, dy, K, cin, cout, like=None, plan=None):
         st = (0, 0, 0)
     if plan is not None:
         partial = _lib.workspace.scratch("wgrad", lib.sv_sparse_conv_wgrad_planned_bytes(K, cin, cout), dy.device)
-        rc = lib.sv_sparse_conv_wgrad_planned(xs, int(x.shape[0]), ns, ds, dw.data_ptr(), n_rows, K, cin, cout, st[0], st[1], st[2], plan.data_ptr(),
-                                              _lib.ptr(partial), _lib.stream())
-        _lib.check(rc, "sv_sparse_conv_wgrad_planned")
+        _lib.launch("sv_sparse_conv_wgrad_planned", xs, int(x.shape[0]), ns, ds, dw.data_ptr(), n_rows, K, cin, cout, st[0], st[1], st[2], plan.data_ptr(),
+                    _lib.ptr(partial))
         return dw
     scratch = _lib.workspace.scratch("wgrad", lib.sv_sparse_conv_wgrad_scratch_bytes(n_rows, K, cin, cout), dy.device)
     if strided:
-        rc = lib.sv_sparse_conv_wgrad_strided(xs, int(x.shape[0]), ns, ds, dw.data_ptr(), n_rows, K, cin, cout, st[0], st[1], st[2], _lib.ptr(scratch), _lib.stream())
-        _lib.check(rc, "sv_sparse_conv_wgrad_strided")
+        _lib.launch("sv_sparse_conv_wgrad_strided", xs, int(x.shape[0]), ns, ds, dw.data_ptr(), n_rows, K, cin, cout, st[0], st[1], st[2], _lib.ptr(scratch))
         return dw
-    rc = lib.sv_sparse_conv_wgrad(xs, int(x.shape[0]), ns, ds, _lib.ptr(dw), n_rows, K, cin, cout, _lib.ptr(scratch), _lib.stream())
-    _lib.check(rc, "sv_sparse_conv_wgrad")
+    _lib.launch("sv_sparse_conv_wgrad", xs, int(x.shape[0]), ns, ds, _lib.ptr(dw), n_rows, K, cin, cout, _lib.ptr(scratch))
     return dw
 
 
@@ -823,7 +792,7 @@ def build_wgrad_plans(items):
         for q, (rb, pieces, off, nbytes) in enumerate(todo):
             jobs[q, :5] = (rb.addr("nbr_out"), rb.n_out, int(rb.K), pieces, buf.data_ptr() + off)
             rb._wgrad_plans[pieces] = buf[off:off + nbytes]
-        _lib.check(lib.sv_wgrad_plan_build_batch(jobs.ctypes.data, len(todo), _lib.stream()), "sv_wgrad_plan_build_batch")
+        _lib.launch("sv_wgrad_plan_build_batch", jobs.ctypes.data, len(todo))
     for rb, cin, cout in items:
         rb.wgrad_plan(cin, cout)          # fills the per-layer cache from the per-table plans
 
@@ -931,7 +900,6 @@ class DenseFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, indices, batch_size, spatial_shape):
         lib = _lib.load()
-        _lib.require_cuda(features, indices)
         features = features.contiguous().float()
         indices = indices.contiguous()
         n, c = features.shape
@@ -939,24 +907,20 @@ class DenseFunction(torch.autograd.Function):
         dev = features.device
         scratch = _lib.workspace.scratch("dense_map", lib.sv_sparse_to_dense_scratch_bytes(batch_size, d, h, w), dev)
         out = torch.empty((batch_size, c, d, h, w), dtype=torch.float32, device=dev)
-        rc = lib.sv_sparse_to_dense(_lib.ptr(features) if n else None, _lib.ptr(indices) if n else None, n, batch_size, c, d, h, w,
-                                    _lib.ptr(scratch), _lib.ptr(out), _lib.stream())
-        _lib.check(rc, "sv_sparse_to_dense")
+        _lib.launch("sv_sparse_to_dense", _lib.ptr(features) if n else None, _lib.ptr(indices) if n else None, n, batch_size, c, d, h, w, _lib.ptr(scratch),
+                    _lib.ptr(out))
         ctx.save_for_backward(indices)
         ctx.dims = (batch_size, c, d, h, w)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         (indices,) = ctx.saved_tensors
         b, c, d, h, w = ctx.dims
         n = indices.shape[0]
         grad = grad.contiguous().float()
         out = torch.empty((n, c), dtype=torch.float32, device=grad.device)
-        rc = lib.sv_dense_to_sparse(_lib.ptr(grad), _lib.ptr(indices) if n else None, n, b, c, d, h, w, _lib.ptr(out) if n else None,
-                                    _lib.stream())
-        _lib.check(rc, "sv_dense_to_sparse")
+        _lib.launch("sv_dense_to_sparse", _lib.ptr(grad), _lib.ptr(indices) if n else None, n, b, c, d, h, w, _lib.ptr(out) if n else None)
         return out, None, None, None
 
 
@@ -971,7 +935,6 @@ class DenseChannelsLastFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, indices, batch_size, spatial_shape):
         lib = _lib.load()
-        _lib.require_cuda(features, indices)
         features = features.contiguous().float()
         indices = indices.contiguous()
         n, c = features.shape
@@ -979,23 +942,20 @@ class DenseChannelsLastFunction(torch.autograd.Function):
         dev = features.device
         scratch = _lib.workspace.scratch("dense_map", lib.sv_sparse_to_dense_scratch_bytes(batch_size, d, h, w), dev)
         out = torch.empty((batch_size, h, w, c * d), dtype=torch.float32, device=dev)
-        rc = lib.sv_sparse_to_dense_nhwc(_lib.ptr(features) if n else None, _lib.ptr(indices) if n else None, n, batch_size, c, d, h, w,
-                                         _lib.ptr(scratch), _lib.ptr(out), _lib.stream())
-        _lib.check(rc, "sv_sparse_to_dense_nhwc")
+        _lib.launch("sv_sparse_to_dense_nhwc", _lib.ptr(features) if n else None, _lib.ptr(indices) if n else None, n, batch_size, c, d, h, w,
+                    _lib.ptr(scratch), _lib.ptr(out))
         ctx.save_for_backward(indices)
         ctx.dims = (batch_size, c, d, h, w)
         return out.permute(0, 3, 1, 2)                                   # (N, C D, H, W), channels_last strides
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         (indices,) = ctx.saved_tensors
         b, c, d, h, w = ctx.dims
         n = indices.shape[0]
         grad = grad.float().permute(0, 2, 3, 1).contiguous()             # a view of a channels_last gradient
         out = torch.empty((n, c), dtype=torch.float32, device=grad.device)
-        rc = lib.sv_dense_to_sparse_nhwc(_lib.ptr(grad), _lib.ptr(indices) if n else None, n, b, c, d, h, w, _lib.ptr(out) if n else None, _lib.stream())
-        _lib.check(rc, "sv_dense_to_sparse_nhwc")
+        _lib.launch("sv_dense_to_sparse_nhwc", _lib.ptr(grad), _lib.ptr(indices) if n else None, n, b, c, d, h, w, _lib.ptr(out) if n else None)
         return out, None, None, None
 
 

@@ -32,7 +32,6 @@ def partial_address(channels, device):
 def bn_forward_raw(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, num_batches_tracked=None, n_partials=0):
     """y, save_mean, save_invstd (the last two None in eval mode) of the fused BatchNorm(+ReLU) forward on a contiguous (N, C) matrix.  n_partials > 0:
     the statistics' first pass is already in the scratch (partial_address), written by the kernel that produced x."""
-    lib = _lib.load()
     n, c = x.shape
     y = torch.empty_like(x)
     if training:
@@ -41,27 +40,24 @@ def bn_forward_raw(x, gamma, beta, running_mean, running_var, momentum, eps, tra
     else:
         mean = invstd = None
     if training and n_partials:
-        _lib.check(lib.sv_batchnorm_relu_forward_partial(_lib.ptr(x), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                                         float(momentum), float(eps), int(relu), _lib.ptr(_scratch(c, x.device)), int(n_partials), _lib.ptr(y),
-                                                         _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(num_batches_tracked), _lib.stream()),
-                   "sv_batchnorm_relu_forward_partial")
+        _lib.launch("sv_batchnorm_relu_forward_partial", _lib.ptr(x), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
+                    float(momentum), float(eps), int(relu), _lib.ptr(_scratch(c, x.device)), int(n_partials), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(invstd),
+                    _lib.ptr(num_batches_tracked))
         return y, mean, invstd
-    _lib.check(lib.sv_batchnorm_relu_forward(_lib.ptr(x), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                             float(momentum), float(eps), int(training), int(relu), _lib.ptr(_scratch(c, x.device)), _lib.ptr(y),
-                                             _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(num_batches_tracked), _lib.stream()), "sv_batchnorm_relu_forward")
+    _lib.launch("sv_batchnorm_relu_forward", _lib.ptr(x), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var), float(momentum),
+                float(eps), int(training), int(relu), _lib.ptr(_scratch(c, x.device)), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(invstd),
+                _lib.ptr(num_batches_tracked))
     return y, mean, invstd
 
 
 def bn_backward_raw(x, dy, gamma, beta, mean, invstd, relu):
     """dx, dgamma, dbeta of the training-mode fused BatchNorm(+ReLU); x is the BatchNorm INPUT (the ReLU mask is recomputed from it)."""
-    lib = _lib.load()
     n, c = x.shape
     dx = torch.empty_like(x)
     dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
-    _lib.check(lib.sv_batchnorm_relu_backward(_lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd),
-                                              int(relu), _lib.ptr(_scratch(c, x.device)), _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                              _lib.stream()), "sv_batchnorm_relu_backward")
+    _lib.launch("sv_batchnorm_relu_backward", _lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd), int(relu),
+                _lib.ptr(_scratch(c, x.device)), _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta))
     return dx, dgamma, dbeta
 
 
@@ -113,43 +109,37 @@ def sync_buffers(bn, channels, device, backward=False):
 def bn_forward_synced(x, bn, relu, n_partials=0):
     """y, save_mean, save_invstd, total_rows of a SYNCED norm on a contiguous (N, C) matrix: this rank's sums (from x, or from the n_partials partials
     its producer left in the scratch), the exchange, the combine over all ranks, the elementwise pass."""
-    lib = _lib.load()
     n, c = x.shape
     dev = x.device
     local, gathered, group = sync_buffers(bn, c, dev)
-    _lib.check(lib.sv_batchnorm_stats_local(None if n_partials else _lib.ptr(x), n, c, _lib.ptr(_scratch(c, dev)), int(n_partials), _lib.ptr(local), _lib.stream()),
-               "sv_batchnorm_stats_local")
+    _lib.launch("sv_batchnorm_stats_local", None if n_partials else _lib.ptr(x), n, c, _lib.ptr(_scratch(c, dev)), int(n_partials), _lib.ptr(local))
     exchange(local, gathered, group)
     stats = torch.empty(4 * c, dtype=torch.float32, device=dev)                      # scale | shift | batch mean | batch invstd
     total = torch.empty(1, dtype=torch.float64, device=dev)
     mean, invstd = stats[2 * c:3 * c], stats[3 * c:]
     rs = bn.track_running_stats
-    _lib.check(lib.sv_batchnorm_finalize_global(_lib.ptr(gathered), gathered.shape[0], c, _lib.ptr(bn.weight), _lib.ptr(bn.bias),
-                                                _lib.ptr(bn.running_mean if rs else None), _lib.ptr(bn.running_var if rs else None), float(bn.momentum), float(bn.eps),
-                                                _lib.ptr(stats), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(bn.num_batches_tracked if rs else None), _lib.ptr(total),
-                                                _lib.stream()), "sv_batchnorm_finalize_global")
+    _lib.launch("sv_batchnorm_finalize_global", _lib.ptr(gathered), gathered.shape[0], c, _lib.ptr(bn.weight), _lib.ptr(bn.bias),
+                _lib.ptr(bn.running_mean if rs else None), _lib.ptr(bn.running_var if rs else None), float(bn.momentum), float(bn.eps), _lib.ptr(stats),
+                _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(bn.num_batches_tracked if rs else None), _lib.ptr(total))
     y = torch.empty_like(x)
-    _lib.check(lib.sv_batchnorm_apply(_lib.ptr(x), n, c, _lib.ptr(stats), int(relu), _lib.ptr(y), _lib.stream()), "sv_batchnorm_apply")
+    _lib.launch("sv_batchnorm_apply", _lib.ptr(x), n, c, _lib.ptr(stats), int(relu), _lib.ptr(y))
     return y, mean, invstd, total
 
 
 def bn_backward_synced(x, dy, bn, gamma, beta, mean, invstd, total, relu):
     """dx, dgamma, dbeta of a SYNCED norm: this rank's two sums, the exchange, the elementwise pass with the sums and the row count of all ranks.
     dgamma / dbeta are this rank's own sums (the data-parallel wrapper averages them like any other parameter gradient)."""
-    lib = _lib.load()
     n, c = x.shape
     dev = x.device
     dx = torch.empty_like(x)
     dgb = torch.empty(2 * c, dtype=torch.float32, device=dev)
     local, gathered, group = sync_buffers(bn, c, dev, backward=True)
     scratch = _scratch(c, dev)
-    _lib.check(lib.sv_batchnorm_backward_sums_local(_lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd), int(relu),
-                                                    _lib.ptr(scratch), 0, _lib.ptr(dgb), dgb.data_ptr() + 4 * c, _lib.ptr(local), _lib.stream()),
-               "sv_batchnorm_backward_sums_local")
+    _lib.launch("sv_batchnorm_backward_sums_local", _lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd),
+                int(relu), _lib.ptr(scratch), 0, _lib.ptr(dgb), dgb.data_ptr() + 4 * c, _lib.ptr(local))
     exchange(local, gathered, group)
-    _lib.check(lib.sv_batchnorm_backward_apply_global(_lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd), int(relu),
-                                                      _lib.ptr(gathered), gathered.shape[0], _lib.ptr(total), _lib.ptr(scratch), _lib.ptr(dx), _lib.stream()),
-               "sv_batchnorm_backward_apply_global")
+    _lib.launch("sv_batchnorm_backward_apply_global", _lib.ptr(x), _lib.ptr(dy), n, c, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd),
+                int(relu), _lib.ptr(gathered), gathered.shape[0], _lib.ptr(total), _lib.ptr(scratch), _lib.ptr(dx))
     return dx, dgb[:c], dgb[c:]
 
 

@@ -187,7 +187,7 @@ def vc_rings(clouds, fixed_bins=0, min_in_pts=0, with_elevation=False):
     ring = torch.empty(clouds.points.shape[0], dtype=torch.int32, device=dev)
     table = torch.empty(B * (1 + MAX_RINGS), dtype=torch.int32, device=dev)
     elev = torch.empty(clouds.points.shape[0], dtype=torch.float64, device=dev) if with_elevation else None
-    call("sv_vc_rings", *clouds.args(), int(fixed_bins), int(min_in_pts), L.ptr(ring), L.ptr(table[:B]), L.ptr(table[B:]), L.ptr(elev), L.stream())
+    call("sv_vc_rings", *clouds.args(), int(fixed_bins), int(min_in_pts), L.ptr(ring), L.ptr(table[:B]), L.ptr(table[B:]), L.ptr(elev))
     return ring, table, elev
 
 
@@ -225,7 +225,7 @@ def vc_select(clouds, plans, lengths, ring=None, keep=None, keep_used=None):
         raise ValueError("an object has no points")
     table = torch.from_numpy(pack_plans(plans, lengths, keep_used)).to(dev)
     out = torch.empty(int(lengths.sum()), 3, dtype=torch.float32, device=dev)
-    call("sv_vc_select", *clouds.args(), L.ptr(ring), L.ptr(keep), L.ptr(table), L.ptr(out), L.stream())
+    call("sv_vc_select", *clouds.args(), L.ptr(ring), L.ptr(keep), L.ptr(table), L.ptr(out))
     return StackedClouds(out, lengths)
 
 
@@ -235,7 +235,7 @@ def vc_resample(clouds, index):
     index = np.ascontiguousarray(index, np.int32)
     B, n_points = index.shape
     out = torch.empty(B, n_points, 3, dtype=torch.float32, device=dev)
-    call("sv_vc_resample", *clouds.args(), L.ptr(torch.from_numpy(index).to(dev)), n_points, L.ptr(out), L.stream())
+    call("sv_vc_resample", *clouds.args(), L.ptr(torch.from_numpy(index).to(dev)), n_points, L.ptr(out))
     return out
 
 
@@ -244,22 +244,21 @@ def vc_pointwise(clouds, noise, mode):
     noise = np.ascontiguousarray(noise, np.float64)
     assert noise.size == clouds.points.shape[0] * (3 if mode == 0 else 1)
     dev_noise = torch.from_numpy(noise).to(clouds.points.device)
-    call("sv_vc_pointwise", L.ptr(clouds.points), int(clouds.points.shape[0]), L.ptr(dev_noise), int(mode), L.stream())
+    call("sv_vc_pointwise", L.ptr(clouds.points), int(clouds.points.shape[0]), L.ptr(dev_noise), int(mode))
 
 
 def vc_world_transform(clouds, op, params):
     """One op of sv_world_transform_points (flip_x, flip_y, rotation, scaling) with one float64 parameter per object, in place."""
     code = P.pack_codes([op], "world")
     p = torch.from_numpy(np.ascontiguousarray(params, np.float64).reshape(clouds.batch_size, 1)).to(clouds.points.device)
-    call("sv_world_transform_points", L.ptr(clouds.points), 3, L.ptr(clouds.start), L.ptr(clouds.cnt), clouds.batch_size, int(clouds.counts.max()),
-         code, 1, L.ptr(p), L.stream())
+    call("sv_world_transform_points", L.ptr(clouds.points), 3, L.ptr(clouds.start), L.ptr(clouds.cnt), clouds.batch_size, int(clouds.counts.max()), code, 1,
+         L.ptr(p))
 
 
 def vc_object_scale(clouds, params):
     """sv_vc_object_scale in place: params (B, 8) host float64 = enable, centre, heading, scale."""
     p = torch.from_numpy(np.ascontiguousarray(params, np.float64).reshape(clouds.batch_size, 8)).to(clouds.points.device)
-    call("sv_vc_object_scale", L.ptr(clouds.points), L.ptr(clouds.start), L.ptr(clouds.cnt), clouds.batch_size, int(clouds.counts.max()), L.ptr(p),
-         L.stream())
+    call("sv_vc_object_scale", L.ptr(clouds.points), L.ptr(clouds.start), L.ptr(clouds.cnt), clouds.batch_size, int(clouds.counts.max()), L.ptr(p))
 
 
 # ---------------------------------------------------------------------------------------------------------------- batch transforms

@@ -13,34 +13,29 @@ from .... import _lib, ordered
 
 
 def forward(xyz1, xyz2):
-    lib = _lib.load()
-    _lib.require_cuda(xyz1, xyz2)
     xyz1, xyz2 = xyz1.contiguous().float(), xyz2.contiguous().float()
     assert xyz1.dim() == 3 and xyz2.dim() == 3 and xyz1.shape[2] == 3 and xyz2.shape[2] == 3 and xyz1.shape[0] == xyz2.shape[0]
     B, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     dev = xyz1.device
     dist1, dist2 = torch.empty((B, n), dtype=torch.float32, device=dev), torch.empty((B, m), dtype=torch.float32, device=dev)
     idx1, idx2 = torch.empty((B, n), dtype=torch.int32, device=dev), torch.empty((B, m), dtype=torch.int32, device=dev)
-    _lib.check(lib.sv_chamfer_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, n, m, _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1), _lib.ptr(idx2),
-                                      _lib.stream()), "sv_chamfer_forward")
+    _lib.launch("sv_chamfer_forward", _lib.ptr(xyz1), _lib.ptr(xyz2), B, n, m, _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1), _lib.ptr(idx2))
     return [dist1, dist2, idx1, idx2]
 
 
 def backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2):
     lib = _lib.load()
-    _lib.require_cuda(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2)
     xyz1, xyz2 = xyz1.contiguous().float(), xyz2.contiguous().float()
     B, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     g1, g2 = torch.empty_like(xyz1), torch.empty_like(xyz2)
     if ordered.ordered_gradients():                           # same terms in a stated order, no float atomics (sv_chamfer_backward_ordered)
         nbytes = lib.sv_chamfer_backward_ordered_scratch_bytes(B, n, m)
         scratch = _lib.workspace.scratch("chamfer_ordered", nbytes, xyz1.device) if nbytes else None
-        _lib.check(lib.sv_chamfer_backward_ordered(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(idx1.contiguous()), _lib.ptr(idx2.contiguous()),
-                                                   _lib.ptr(grad_dist1.contiguous().float()), _lib.ptr(grad_dist2.contiguous().float()), B, n, m,
-                                                   _lib.ptr(scratch), _lib.ptr(g1), _lib.ptr(g2), _lib.stream()), "sv_chamfer_backward_ordered")
+        _lib.launch("sv_chamfer_backward_ordered", _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(idx1.contiguous()), _lib.ptr(idx2.contiguous()),
+                    _lib.ptr(grad_dist1.contiguous().float()), _lib.ptr(grad_dist2.contiguous().float()), B, n, m, _lib.ptr(scratch), _lib.ptr(g1),
+                    _lib.ptr(g2))
         ordered.count_call("chamfer")
         return [g1, g2]
-    _lib.check(lib.sv_chamfer_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(idx1.contiguous()), _lib.ptr(idx2.contiguous()),
-                                       _lib.ptr(grad_dist1.contiguous().float()), _lib.ptr(grad_dist2.contiguous().float()), B, n, m,
-                                       _lib.ptr(g1), _lib.ptr(g2), _lib.stream()), "sv_chamfer_backward")
+    _lib.launch("sv_chamfer_backward", _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(idx1.contiguous()), _lib.ptr(idx2.contiguous()),
+                _lib.ptr(grad_dist1.contiguous().float()), _lib.ptr(grad_dist2.contiguous().float()), B, n, m, _lib.ptr(g1), _lib.ptr(g2))
     return [g1, g2]

@@ -60,7 +60,6 @@ class Calibration(object):
 
     def project_device(self, pc_velo, img_w, img_h, min_dist=1.0, device='cuda', want_rect=True):
         """(N,>=3) points -> uv (N,2) int32 (floor; -1 outside), fov (N) bool, rect (N,3) float32 CUDA tensors."""
-        lib = _lib.load()
         pts = _dev_points(pc_velo, device)
         n = pts.shape[0]
         uv = torch.empty((n, 2), dtype=torch.int32, device=pts.device)
@@ -69,10 +68,8 @@ class Calibration(object):
         v2c = np.ascontiguousarray(self.V2C, dtype=np.float64)
         r0 = np.ascontiguousarray(self.R0, dtype=np.float64)
         p = np.ascontiguousarray(self.P, dtype=np.float64)
-        _lib.check(lib.sv_project_lidar_to_image_kitti(_lib.ptr(pts), n, pts.stride(0), v2c.ctypes.data, r0.ctypes.data, p.ctypes.data,
-                                                       int(img_w), int(img_h), float(min_dist), _lib.ptr(uv), _lib.ptr(fov),
-                                                       _lib.ptr(rect) if rect is not None else None, _lib.stream()),
-                   "sv_project_lidar_to_image_kitti")
+        _lib.launch("sv_project_lidar_to_image_kitti", _lib.ptr(pts), n, pts.stride(0), v2c.ctypes.data, r0.ctypes.data, p.ctypes.data, int(img_w), int(img_h),
+                    float(min_dist), _lib.ptr(uv), _lib.ptr(fov), _lib.ptr(rect) if rect is not None else None)
         return pts, uv, fov.bool(), rect
 
 
@@ -93,7 +90,6 @@ def map_pointcloud_to_image_custom(points, calib, img_shape, camera_model="pinho
     reference's (rounded half-to-even / float64)."""
     if camera_model not in ("pinhole", "equidistant"):
         raise NotImplementedError
-    lib = _lib.load()
     img_h, img_w = int(img_shape[0]), int(img_shape[1])
     pts = _dev_points(points, device)
     n = pts.shape[0]
@@ -105,9 +101,8 @@ def map_pointcloud_to_image_custom(points, calib, img_shape, camera_model="pinho
     d = np.zeros(5, np.float64)
     dc = np.asarray(calib['distcoeff'], dtype=np.float64).reshape(-1)
     d[:min(5, len(dc))] = dc[:5]
-    _lib.check(lib.sv_project_lidar_to_image_camera(_lib.ptr(pts), n, pts.stride(0), e.ctypes.data, k.ctypes.data, d.ctypes.data,
-                                                    1 if camera_model == "equidistant" else 0, img_w, img_h, _lib.ptr(uvd_int), _lib.ptr(uvd),
-                                                    _lib.ptr(fov), _lib.stream()), "sv_project_lidar_to_image_camera")
+    _lib.launch("sv_project_lidar_to_image_camera", _lib.ptr(pts), n, pts.stride(0), e.ctypes.data, k.ctypes.data, d.ctypes.data,
+                1 if camera_model == "equidistant" else 0, img_w, img_h, _lib.ptr(uvd_int), _lib.ptr(uvd), _lib.ptr(fov))
     fovb = fov.bool()
     fov_np = fovb.cpu().numpy()
     src = points if isinstance(points, np.ndarray) else points.cpu().numpy()
@@ -167,7 +162,6 @@ def map_pointcloud_to_image_nuscenes(points, cs_lidar, pose_lidar, pose_cam, cs_
     of the camera sample_data, each a dict with 'rotation' (w,x,y,z) and 'translation' (3,), the last one also 'camera_intrinsic' -- are
     passed in directly (no devkit needed).  Same return dict as the reference: pc_lidar, pc_cam (float32 camera frame), pts_img
     (floor(u,v) int), fov_inds, img_shape."""
-    lib = _lib.load()
     img_h, img_w = int(img_shape[0]), int(img_shape[1])
     pts = _dev_points(points, device)
     n = pts.shape[0]
@@ -179,9 +173,8 @@ def map_pointcloud_to_image_nuscenes(points, cs_lidar, pose_lidar, pose_cam, cs_
     pc_cam = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
     uv = torch.empty((n, 2), dtype=torch.int32, device=pts.device)
     fov = torch.empty((n,), dtype=torch.uint8, device=pts.device)
-    _lib.check(lib.sv_project_lidar_to_image_nuscenes(_lib.ptr(pts), n, pts.stride(0), rot.ctypes.data, tr.ctypes.data, k.ctypes.data, img_w, img_h,
-                                                      float(min_dist), _lib.ptr(pc_cam), _lib.ptr(uv), _lib.ptr(fov), _lib.stream()),
-               "sv_project_lidar_to_image_nuscenes")
+    _lib.launch("sv_project_lidar_to_image_nuscenes", _lib.ptr(pts), n, pts.stride(0), rot.ctypes.data, tr.ctypes.data, k.ctypes.data, img_w, img_h,
+                float(min_dist), _lib.ptr(pc_cam), _lib.ptr(uv), _lib.ptr(fov))
     fovb = fov.bool()
     fov_np = fovb.cpu().numpy()
     src = points if isinstance(points, np.ndarray) else points.cpu().numpy()
@@ -192,8 +185,6 @@ def map_pointcloud_to_image_nuscenes(points, cs_lidar, pose_lidar, pose_cam, cs_
 def points_in_masks_device(uv, fov, masks=None, rects=None, cap=None):
     """uv (N,2) int32, fov (N) bool/uint8, masks (I,H,W) uint8 or rects (I,4) int32 -> index (I,cap) int32 ascending point
     indices, count (I) int32 (CUDA tensors)."""
-    lib = _lib.load()
-    _lib.require_cuda(uv, fov)
     n = uv.shape[0]
     inst = masks if masks is not None else rects
     n_inst = inst.shape[0]
@@ -205,9 +196,8 @@ def points_in_masks_device(uv, fov, masks=None, rects=None, cap=None):
     else:
         img_h = img_w = 1 << 30
     fov8 = fov.to(torch.uint8).contiguous()
-    _lib.check(lib.sv_points_in_masks(_lib.ptr(uv.contiguous()), _lib.ptr(fov8), n, _lib.ptr(masks) if masks is not None else None,
-                                      _lib.ptr(rects) if rects is not None else None, n_inst, img_w, img_h, cap, _lib.ptr(index),
-                                      _lib.ptr(count), _lib.stream()), "sv_points_in_masks")
+    _lib.launch("sv_points_in_masks", _lib.ptr(uv.contiguous()), _lib.ptr(fov8), n, _lib.ptr(masks) if masks is not None else None,
+                _lib.ptr(rects) if rects is not None else None, n_inst, img_w, img_h, cap, _lib.ptr(index), _lib.ptr(count))
     return index, count
 
 
@@ -290,8 +280,7 @@ def instance_masks_device(instances, img_h, img_w, device='cuda', shrink_percent
     else:
         xy_t = off_t = inst_t = scratch = None
         max_v = 0
-    _lib.check(lib.sv_polygons_to_masks(_lib.ptr(xy_t), _lib.ptr(off_t), _lib.ptr(inst_t), n_poly, max_v, n, img_h, img_w, _lib.ptr(scratch),
-                                        _lib.ptr(masks), _lib.stream()), "sv_polygons_to_masks")
+    _lib.launch("sv_polygons_to_masks", _lib.ptr(xy_t), _lib.ptr(off_t), _lib.ptr(inst_t), n_poly, max_v, n, img_h, img_w, _lib.ptr(scratch), _lib.ptr(masks))
     for i, m in host.items():
         assert m.shape == (img_h, img_w), f"instance {i}: mask {m.shape} on a {(img_h, img_w)} image"
         masks[i].copy_(torch.from_numpy(np.ascontiguousarray(m)))
@@ -328,8 +317,8 @@ def instance_masks_within_distance(instances, img_h, img_w, device='cuda', shrin
     scratch = torch.empty((lib.sv_polygon_masks_scratch_bytes(n_poly, img_h, img_w),), dtype=torch.uint8, device=dev)
     dist_t = torch.tensor(dist, dtype=torch.float64, device=dev)
     kept = torch.empty((n_poly,), dtype=torch.int32, device=dev)
-    _lib.check(lib.sv_polygons_to_masks_shrunk(_lib.ptr(xy_t), _lib.ptr(off_t), _lib.ptr(inst_t), _lib.ptr(dist_t), n_poly, max_v, n, img_h, img_w,
-                                               _lib.ptr(scratch), _lib.ptr(masks), _lib.ptr(kept), _lib.stream()), "sv_polygons_to_masks_shrunk")
+    _lib.launch("sv_polygons_to_masks_shrunk", _lib.ptr(xy_t), _lib.ptr(off_t), _lib.ptr(inst_t), _lib.ptr(dist_t), n_poly, max_v, n, img_h, img_w,
+                _lib.ptr(scratch), _lib.ptr(masks), _lib.ptr(kept))
     empty = sorted({inst_of[p] for p in np.nonzero(kept.cpu().numpy() == 0)[0]})
     if empty:
         redo = instance_masks_device([{'segmentation': instances[i]['segmentation']} for i in empty], img_h, img_w, dev, 0)
@@ -401,7 +390,6 @@ def largest_clusters_device(points, starts, counts, max_points, point_index=None
     """One launch for all instances.  points (ΣN,>=3) float32 CUDA; starts (I) int64, counts (I) int32.  Returns out_local
     (same slots as the input lists) int32, out_count (I) int32, eps (I) float64."""
     lib = _lib.load()
-    _lib.require_cuda(points, starts, counts)
     n_inst = counts.shape[0]
     slots = point_index.shape[0] if point_index is not None else points.shape[0]
     out_local = torch.empty((max(slots, 1),), dtype=torch.int32, device=points.device)
@@ -410,12 +398,10 @@ def largest_clusters_device(points, starts, counts, max_points, point_index=None
     nbytes = lib.sv_isolate_cluster_scratch_bytes(n_inst, int(max_points))
     scratch = _lib.workspace.scratch("isolate_cluster", nbytes, points.device) if nbytes else None
     tan_vres = float(np.tan(vres * np.pi / 180)) if vres is not None else 0.0
-    _lib.check(lib.sv_isolate_largest_cluster(_lib.ptr(points), points.stride(0), _lib.ptr(point_index) if point_index is not None else None,
-                                              _lib.ptr(starts), _lib.ptr(counts), n_inst, int(max_points), tan_vres, float(eps_scaling),
-                                              float(min_eps), float(max_eps), -1.0 if fixed_eps is None else float(fixed_eps),
-                                              int(min_points), int(min_cluster), _lib.ptr(scratch) if scratch is not None else None,
-                                              _lib.ptr(out_local), _lib.ptr(out_count), _lib.ptr(out_eps), _lib.stream()),
-               "sv_isolate_largest_cluster")
+    _lib.launch("sv_isolate_largest_cluster", _lib.ptr(points), points.stride(0), _lib.ptr(point_index) if point_index is not None else None, _lib.ptr(starts),
+                _lib.ptr(counts), n_inst, int(max_points), tan_vres, float(eps_scaling), float(min_eps), float(max_eps),
+                -1.0 if fixed_eps is None else float(fixed_eps), int(min_points), int(min_cluster), _lib.ptr(scratch) if scratch is not None else None,
+                _lib.ptr(out_local), _lib.ptr(out_count), _lib.ptr(out_eps))
     return out_local, out_count, out_eps
 
 
@@ -522,15 +508,12 @@ def populate_gtboxes(sample_infos, dataset_name, classes, add_ground_lift=False,
 
 def crop_boxes_device(points, boxes, cap=None):
     """points (N,>=3) float32 CUDA, boxes list of OrientedBox -> index (G,cap) int32, count (G) int32."""
-    lib = _lib.load()
-    _lib.require_cuda(points)
     n, G = points.shape[0], len(boxes)
     cap = int(n if cap is None else cap)
     rows = torch.from_numpy(np.ascontiguousarray(np.stack([b.row() for b in boxes]), dtype=np.float64)).to(points.device)
     index = torch.empty((G, max(cap, 1)), dtype=torch.int32, device=points.device)
     count = torch.zeros((G,), dtype=torch.int32, device=points.device)
-    _lib.check(lib.sv_crop_points_in_boxes(_lib.ptr(points), n, points.stride(0), _lib.ptr(rows), G, cap, _lib.ptr(index),
-                                           _lib.ptr(count), _lib.stream()), "sv_crop_points_in_boxes")
+    _lib.launch("sv_crop_points_in_boxes", _lib.ptr(points), n, points.stride(0), _lib.ptr(rows), G, cap, _lib.ptr(index), _lib.ptr(count))
     return index, count
 
 
@@ -556,7 +539,6 @@ def isolate_gt_pts(pcd_gtboxes, min_lidar_pts, use_seev1=False, device='cuda'):
 def merge_multi_camera_detections(isolated_inst, min_overlap=3, min_dist_to_check=3, device='cuda'):
     """SEE_VCN.py:183-209.  The overlap count (points of j within 0.1 m of some point of i, inclusive) runs on
     sv_points_near_set with the threshold moved to the next float64 (strict < next(0.1) == inclusive <= 0.1 on the distance)."""
-    lib = _lib.load()
     isolated_inst = list(isolated_inst)
     joined = []
     inst_d = [np.linalg.norm(inst.mean(axis=0)) for inst in isolated_inst]
@@ -570,8 +552,7 @@ def merge_multi_camera_detections(isolated_inst, min_overlap=3, min_dist_to_chec
                     if dev[t] is None:
                         dev[t] = _dev_points(np.asarray(isolated_inst[t]), device)
                 near = torch.empty((dev[j].shape[0],), dtype=torch.uint8, device=dev[j].device)
-                _lib.check(lib.sv_points_near_set(_lib.ptr(dev[j]), dev[j].shape[0], _lib.ptr(dev[i]), dev[i].shape[0], 3, thresh,
-                                                  _lib.ptr(near), _lib.stream()), "sv_points_near_set")
+                _lib.launch("sv_points_near_set", _lib.ptr(dev[j]), dev[j].shape[0], _lib.ptr(dev[i]), dev[i].shape[0], 3, thresh, _lib.ptr(near))
                 if int(near.sum().item()) > min_overlap:
                     isolated_inst.append(np.vstack([isolated_inst[i], isolated_inst[j]]))
                     joined.extend([i, j])

@@ -76,17 +76,14 @@ class VCN_CN(nn.Module):
             return self._forward_eval(in_dict)
 
     def _forward_eval(self, in_dict):
-        lib = _lib.load()
         x, boxes = in_dict['input'], in_dict['gt_boxes']
-        _lib.require_cuda(x, boxes)
         x = x.float().contiguous()
         boxes = boxes.float()[:, :7].contiguous()
         assert boxes.shape[1] == 7, f'gt_label wrong shape, should be (B 7) but given shape is {boxes.shape}'
         bs, n, _ = x.shape
         p = self._prepared.get()
-        st = _lib.stream()
         pc = torch.empty_like(x)
-        _lib.check(lib.sv_vcn_cn_transform(_lib.ptr(x), bs, n, _lib.ptr(boxes), 0, _lib.ptr(pc), st), "sv_vcn_cn_transform")
+        _lib.launch("sv_vcn_cn_transform", _lib.ptr(x), bs, n, _lib.ptr(boxes), 0, _lib.ptr(pc))
         pts, rg, sel, u_dev = pc.view(bs * n, 3), None, None, None
         if self.dedup_points and n > 1:
             sel, rg, u_dev = L.distinct_rows(x, sync=False)       # the number of distinct rows stays on the device (see VCN_VC._forward_eval)
@@ -94,5 +91,5 @@ class VCN_CN(nn.Module):
         coarse_cn = L.run_fc(p["shape_fc"], feat, L.ACT_RELU)
         nc = self.number_coarse
         coarse = torch.empty((bs, nc, 3), dtype=torch.float32, device=x.device)
-        _lib.check(lib.sv_vcn_cn_transform(_lib.ptr(coarse_cn), bs, nc, _lib.ptr(boxes), 1, _lib.ptr(coarse), st), "sv_vcn_cn_transform")
+        _lib.launch("sv_vcn_cn_transform", _lib.ptr(coarse_cn), bs, nc, _lib.ptr(boxes), 1, _lib.ptr(coarse))
         return {'coarse': coarse}

@@ -168,18 +168,15 @@ class VCN_VC(nn.Module):
             return self._forward_eval(in_dict)
 
     def _forward_eval(self, in_dict):
-        lib = _lib.load()
         x = in_dict['input']
-        _lib.require_cuda(x)
         x = x.float().contiguous()
         bs, n, _ = x.shape
         dev = x.device
         p = self._prepared.get()
-        st = _lib.stream()
         fview = torch.empty_like(x)
         centred = torch.empty_like(x)
         state = torch.zeros((bs, 32), dtype=torch.float32, device=dev)
-        _lib.check(lib.sv_vcn_vc_prep(_lib.ptr(x), bs, n, _lib.ptr(fview), _lib.ptr(centred), _lib.ptr(state), st), "sv_vcn_vc_prep")
+        _lib.launch("sv_vcn_vc_prep", _lib.ptr(x), bs, n, _lib.ptr(fview), _lib.ptr(centred), _lib.ptr(state))
         # pose encoder: 3->64 LReLU, 64->128 LReLU, 128->1024, max over n   (VCN_VC.py:116-123,193)
         (w0, b0), (w1, b1), (w2, b2) = p["pose"]
         sel = rg = u_dev = None
@@ -195,7 +192,7 @@ class VCN_VC(nn.Module):
         L.gemm(h, w2, b2, L.ACT_NONE, rows_per_group=n, store=False, group_max=pose_feat, row_group=rg, m_dev=u_dev)
         rel_pose = L.run_fc(p["pose_fc"], pose_feat, L.ACT_LRELU)                     # (B, 9)   :194
         pc_cn = torch.empty_like(x)
-        _lib.check(lib.sv_vcn_vc_pose(_lib.ptr(fview), bs, n, _lib.ptr(rel_pose), _lib.ptr(state), _lib.ptr(pc_cn), st), "sv_vcn_vc_pose")
+        _lib.launch("sv_vcn_vc_pose", _lib.ptr(fview), bs, n, _lib.ptr(rel_pose), _lib.ptr(state), _lib.ptr(pc_cn))
         pts = pc_cn.view(bs * n, 3)
         feat = L.encode(p["enc"], pts, bs, n, row_group=rg, sel=sel, m_dev=u_dev, pool=pool)      # (B, 1024) :203
         coarse_cn = L.run_fc(p["shape_fc"], feat, L.ACT_RELU)                         # (B, 3072) :204
@@ -203,6 +200,5 @@ class VCN_VC(nn.Module):
         coarse = torch.empty((bs, nc, 3), dtype=torch.float32, device=dev)
         reg_rot = torch.empty((bs, 3, 3), dtype=torch.float32, device=dev)
         reg_centre = torch.empty((bs, 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.sv_vcn_vc_finish(_lib.ptr(coarse_cn), bs, nc, _lib.ptr(state), _lib.ptr(coarse), _lib.ptr(reg_rot),
-                                        _lib.ptr(reg_centre), st), "sv_vcn_vc_finish")
+        _lib.launch("sv_vcn_vc_finish", _lib.ptr(coarse_cn), bs, nc, _lib.ptr(state), _lib.ptr(coarse), _lib.ptr(reg_rot), _lib.ptr(reg_centre))
         return {'coarse': coarse, 'reg_rot': reg_rot, 'reg_centre': reg_centre}

@@ -75,7 +75,6 @@ def gemm(a, w, bias=None, act=ACT_NONE, group_bias=None, rows_per_group=1, store
     (int32 tensor); a.shape[0] is then the capacity, the output keeps capacity rows and only the first *m_dev are computed.
 
     Returns the (M,N) output (or None when store=False); `group_max` (groups, N) must be pre-filled with -inf."""
-    lib = _lib.load()
     M, K = a.shape
     N = w.shape[0]
     assert w.shape[1] == K and a.is_contiguous() and w.is_contiguous()
@@ -87,17 +86,16 @@ def gemm(a, w, bias=None, act=ACT_NONE, group_bias=None, rows_per_group=1, store
         out = torch.empty((M, N), dtype=torch.float32, device=a.device) if store else None
     if row_group is None:
         assert m_dev is None
-        rc = lib.sv_gemm_bias_act(_lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group),
-                                  _lib.ptr(out), N, _lib.ptr(group_max), M, N, K, int(act), float(slope), _lib.stream())
+        _lib.launch("sv_gemm_bias_act", _lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), int(rows_per_group), _lib.ptr(out), N,
+                    _lib.ptr(group_max), M, N, K, int(act), float(slope))
     elif m_dev is None:
         assert row_group.dtype == torch.int32 and row_group.shape[0] == M
-        rc = lib.sv_gemm_bias_act_ragged(_lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), _lib.ptr(row_group),
-                                         _lib.ptr(out), N, _lib.ptr(group_max), M, N, K, int(act), float(slope), _lib.stream())
+        _lib.launch("sv_gemm_bias_act_ragged", _lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), _lib.ptr(row_group), _lib.ptr(out), N,
+                    _lib.ptr(group_max), M, N, K, int(act), float(slope))
     else:
         assert row_group.dtype == torch.int32 and row_group.shape[0] == M and m_dev.dtype == torch.int32
-        rc = lib.sv_gemm_bias_act_ragged_dev(_lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), _lib.ptr(row_group),
-                                             _lib.ptr(out), N, _lib.ptr(group_max), M, _lib.ptr(m_dev), N, K, int(act), float(slope), _lib.stream())
-    _lib.check(rc, "sv_gemm_bias_act")
+        _lib.launch("sv_gemm_bias_act_ragged_dev", _lib.ptr(a), K, _lib.ptr(w), K, _lib.ptr(bias), _lib.ptr(group_bias), _lib.ptr(row_group), _lib.ptr(out), N,
+                    _lib.ptr(group_max), M, _lib.ptr(m_dev), N, K, int(act), float(slope))
     return out
 
 
@@ -108,16 +106,14 @@ def distinct_rows(x, sync=True):
     Ni distinct rows; the per-point layers (Conv1d k=1, eval-mode BatchNorm folded) and the max-pools over points give
     bit-identical results on the distinct rows alone.  sync=True: one host sync (the number of kept rows).  sync=False: no read --
     (sel, row_group) keep their B*n capacity rows and the third value is U as a device int32 tensor for the *_dev / *_gather layer entries."""
-    lib = _lib.load()
     B, n, _ = x.shape
     idx = torch.empty((B, n), dtype=torch.int32, device=x.device)
     cnt = torch.empty((B,), dtype=torch.int32, device=x.device)
-    _lib.check(lib.sv_unique_rows(_lib.ptr(x), B, n, _lib.ptr(idx), _lib.ptr(cnt), _lib.stream()), "sv_unique_rows")
+    _lib.launch("sv_unique_rows", _lib.ptr(x), B, n, _lib.ptr(idx), _lib.ptr(cnt))
     sel = torch.empty((B * n,), dtype=torch.int64, device=x.device)
     row_group = torch.empty((B * n,), dtype=torch.int32, device=x.device)
     total = torch.empty((1,), dtype=torch.int32, device=x.device)
-    _lib.check(lib.sv_unique_rows_compact(_lib.ptr(idx), _lib.ptr(cnt), B, n, _lib.ptr(sel), _lib.ptr(row_group), _lib.ptr(total), _lib.stream()),
-               "sv_unique_rows_compact")
+    _lib.launch("sv_unique_rows_compact", _lib.ptr(idx), _lib.ptr(cnt), B, n, _lib.ptr(sel), _lib.ptr(row_group), _lib.ptr(total))
     if not sync:
         return sel, row_group, total
     u = _lib.host_int(total)                                                                                     # sync: U rows
@@ -128,29 +124,25 @@ def distinct_rows(x, sync=True):
 def pointwise3(xyz, w, b, act, slope=LRELU_SLOPE, sel=None, m_dev=None, tag=None):
     """K = 3 first layer on the rows of xyz (M, 3) -- or, with sel (capacity,) int64 and m_dev, on xyz[sel[m]] for m < *m_dev (the output keeps
     the capacity's rows; gather and count stay on the device)."""
-    lib = _lib.load()
     C = w.shape[0]
     if sel is not None and m_dev is not None:
         M = sel.shape[0]
         out = (_lib.workspace.scratch(f"vcn_{tag}", M * C * 4, xyz.device)[:M * C * 4].view(torch.float32).view(M, C) if tag is not None
                else torch.empty((M, C), dtype=torch.float32, device=xyz.device))
-        rc = lib.sv_pointwise_conv3_gather(_lib.ptr(xyz), _lib.ptr(sel), M, _lib.ptr(m_dev), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), C, int(act), float(slope),
-                                           _lib.stream())
-        _lib.check(rc, "sv_pointwise_conv3_gather")
+        _lib.launch("sv_pointwise_conv3_gather", _lib.ptr(xyz), _lib.ptr(sel), M, _lib.ptr(m_dev), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), C, int(act),
+                    float(slope))
         return out
     if sel is not None:
         xyz = xyz[sel]
     M = xyz.shape[0]
     out = torch.empty((M, C), dtype=torch.float32, device=xyz.device)
-    rc = lib.sv_pointwise_conv3(_lib.ptr(xyz), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), M, C, int(act), float(slope), _lib.stream())
-    _lib.check(rc, "sv_pointwise_conv3")
+    _lib.launch("sv_pointwise_conv3", _lib.ptr(xyz), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), M, C, int(act), float(slope))
     return out
 
 
 def neg_inf(shape, device):
-    lib = _lib.load()
     t = torch.empty(shape, dtype=torch.float32, device=device)
-    _lib.check(lib.sv_fill_f32(_lib.ptr(t), t.numel(), float("-inf"), _lib.stream()), "sv_fill_f32")
+    _lib.launch("sv_fill_f32", _lib.ptr(t), t.numel(), float("-inf"))
     return t
 
 

@@ -16,13 +16,12 @@ def points_near_set(query, ref, thresh):
     """bool (Nq,) : query point closer than `thresh` to any ref point (float64 distances).  Rows are [x,y,z] or, for a batch of
     scenes in one launch, [b,x,y,z] (only rows of the same scene are compared)."""
     lib = _lib.load()
-    _lib.require_cuda(query, ref)
     q, r = query.detach().float().contiguous(), ref.detach().float().contiguous()
     assert q.dim() == 2 and q.shape[1] == r.shape[1] and q.shape[1] in (3, 4)
     near = torch.empty((q.shape[0],), dtype=torch.uint8, device=q.device)
     scratch = _lib.workspace.scratch("near_set_boxes", lib.sv_points_near_set_scratch_bytes(r.shape[0]), q.device)
-    _lib.check(lib.sv_points_near_set_boxed(_lib.ptr(q) if q.numel() else None, q.shape[0], _lib.ptr(r) if r.numel() else None, r.shape[0], q.shape[1],
-                                            float(thresh), _lib.ptr(scratch), _lib.ptr(near) if q.numel() else None, _lib.stream()), "sv_points_near_set_boxed")
+    _lib.launch("sv_points_near_set_boxed", _lib.ptr(q) if q.numel() else None, q.shape[0], _lib.ptr(r) if r.numel() else None, r.shape[0], q.shape[1],
+                float(thresh), _lib.ptr(scratch), _lib.ptr(near) if q.numel() else None)
     return near.bool()
 
 
@@ -63,7 +62,7 @@ def complete_scene_batch_device(points, clustered, object_scene, point_dist_thre
     rows = rows.float().contiguous()
     n = rows.shape[0]
     scratch = _lib.workspace.scratch("dedup_rows", lib.sv_dedup_rows_scratch_bytes(n), rows.device)
-    _lib.check(lib.sv_dedup_rows(_lib.ptr(rows) if n else None, n, _lib.ptr(scratch), _lib.stream()), "sv_dedup_rows")
+    _lib.launch("sv_dedup_rows", _lib.ptr(rows) if n else None, n, _lib.ptr(scratch))
     near = points_near_set(points, rows, point_dist_thresh)
     out = torch.cat([rows, points], dim=0)
     out[n:, 0].masked_fill_(near, -1.0)

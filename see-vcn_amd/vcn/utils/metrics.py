@@ -26,7 +26,7 @@ COL_SUMS, COL_STRIPPED, COL_NZ1, COL_NZ2, COL_BOX, COL_IOU, COL_NUM_OOB, COL_NUM
 def objects_table(coarse, complete, gt_boxes, reg_rot=None, reg_centre=None):
     """The per-object table (B, COLUMNS) fp32 of sv_vc_metrics_objects (integer columns: view(torch.int32)); one library call, no read.
     complete None: the Chamfer columns are skipped."""
-    L.require_cuda(coarse, complete, gt_boxes, reg_rot, reg_centre)
+    L.require_cuda(gt_boxes)                                   # it is moved to coarse's device below: ptr() would not see where it came from
     as32 = lambda t: None if t is None else t.detach().float().contiguous()
     coarse, complete, gt_boxes, reg_rot, reg_centre = as32(coarse), as32(complete), as32(gt_boxes), as32(reg_rot), as32(reg_centre)
     B, n = coarse.shape[0], coarse.shape[1]
@@ -36,8 +36,7 @@ def objects_table(coarse, complete, gt_boxes, reg_rot=None, reg_centre=None):
     assert reg_centre is None or reg_centre.shape == (B, 3), "reg_centre (B,3)"
     m = 0 if complete is None else complete.shape[1]
     table = torch.empty((B, COLUMNS), dtype=torch.float32, device=coarse.device)
-    call("sv_vc_metrics_objects", L.ptr(coarse), L.ptr(complete), L.ptr(gt_boxes.to(coarse.device)), L.ptr(reg_rot), L.ptr(reg_centre), B, n, m,
-         L.ptr(table), L.stream())
+    call("sv_vc_metrics_objects", L.ptr(coarse), L.ptr(complete), L.ptr(gt_boxes.to(coarse.device)), L.ptr(reg_rot), L.ptr(reg_centre), B, n, m, L.ptr(table))
     return table
 
 
@@ -112,7 +111,7 @@ class Metrics(object):
         num_pts = _num_pts_device(gt['num_pts'], coarse.device)
         assert num_pts.numel() == B, "num_pts: one count an object"
         out = torch.empty(30, dtype=torch.float32, device=coarse.device)
-        call("sv_vc_metrics_levels", L.ptr(table), L.ptr(num_pts), B, L.ptr(out), L.stream())
+        call("sv_vc_metrics_levels", L.ptr(table), L.ptr(num_pts), B, L.ptr(out))
         if len(enabled) != len(cls.BUILT):
             out = out.view(6, 5)[[cls.BUILT.index(name) for name in enabled]].reshape(-1)
         return out if eval_by_num_pts else out.view(-1, 5)[:, 0].contiguous()
@@ -198,5 +197,5 @@ def _diagonal_iou3d(boxes_a, boxes_b):
     """(B,7), (B,7) -> (B,) 3-D IoU of pair i with pair i: B box sets of one box each through sv_boxes_iou3d_batch (no B x B matrix)."""
     a, b = boxes_a.detach().float().contiguous(), boxes_b.detach().float().contiguous()
     out = torch.empty(len(a), dtype=torch.float32, device=a.device)
-    call("sv_boxes_iou3d_batch", L.ptr(a), 1, 7, L.ptr(b), 1, 7, len(a), L.ptr(out), L.stream())
+    call("sv_boxes_iou3d_batch", L.ptr(a), 1, 7, L.ptr(b), 1, 7, len(a), L.ptr(out))
     return out

@@ -18,15 +18,14 @@ def _as_device_f32(x, device=None):
 def get_partial_mesh_batch_device(batch_partial, batch_complete, k=20, surface_pts=1024):
     """(B,n,3), (B,m,3) CUDA tensors -> surface (B,surface_pts,3) float32 tensor, n_selected (B) int32 tensor."""
     lib = _lib.load()
-    _lib.require_cuda(batch_partial, batch_complete)
     p, c = _as_device_f32(batch_partial), _as_device_f32(batch_complete)
     assert p.dim() == 3 and c.dim() == 3 and p.shape[0] == c.shape[0] and p.shape[2] == 3 and c.shape[2] == 3
     B = p.shape[0]
     out = torch.empty((B, surface_pts, 3), dtype=torch.float32, device=p.device)
     nsel = torch.empty((B,), dtype=torch.int32, device=p.device)
     scratch = _lib.workspace.scratch("surface_select", lib.sv_vcn_surface_select_scratch_bytes(B), p.device)
-    _lib.check(lib.sv_vcn_surface_select(_lib.ptr(p), _lib.ptr(c), B, p.shape[1], c.shape[1], int(k), int(surface_pts), _lib.ptr(scratch), _lib.ptr(out),
-                                         _lib.ptr(nsel), _lib.stream()), "sv_vcn_surface_select")
+    _lib.launch("sv_vcn_surface_select", _lib.ptr(p), _lib.ptr(c), B, p.shape[1], c.shape[1], int(k), int(surface_pts), _lib.ptr(scratch), _lib.ptr(out),
+                _lib.ptr(nsel))
     return out, nsel
 
 
@@ -53,8 +52,6 @@ def get_largest_cluster_batch_device(pc, eps=0.4, min_points=1, total_pts=1024, 
     read on this stream (_lib.defer_check: the pipeline's voxel count follows within the same step).  period (B) int32 CUDA tensor, optional:
     object b's cloud repeats its first period[b] rows (get_partial_mesh_batch_device's second return value) -- a hint that is verified on the
     device and only shortens the pair tests (same output)."""
-    lib = _lib.load()
-    _lib.require_cuda(pc)
     x = _as_device_f32(pc)
     assert x.dim() == 3 and x.shape[2] == 3
     B = x.shape[0]
@@ -62,11 +59,10 @@ def get_largest_cluster_batch_device(pc, eps=0.4, min_points=1, total_pts=1024, 
     cnt = torch.empty((B,), dtype=torch.int32, device=x.device)
     if period is not None:
         assert period.dtype == torch.int32 and period.shape == (B,) and period.is_cuda
-        _lib.check(lib.sv_vcn_largest_cluster_periodic(_lib.ptr(x), B, x.shape[1], _lib.ptr(period.contiguous()), float(eps), int(min_points), int(total_pts),
-                                                       _lib.ptr(out), _lib.ptr(cnt), _lib.stream()), "sv_vcn_largest_cluster_periodic")
+        _lib.launch("sv_vcn_largest_cluster_periodic", _lib.ptr(x), B, x.shape[1], _lib.ptr(period.contiguous()), float(eps), int(min_points), int(total_pts),
+                    _lib.ptr(out), _lib.ptr(cnt))
     else:
-        _lib.check(lib.sv_vcn_largest_cluster(_lib.ptr(x), B, x.shape[1], float(eps), int(min_points), int(total_pts), _lib.ptr(out), _lib.ptr(cnt),
-                                              _lib.stream()), "sv_vcn_largest_cluster")
+        _lib.launch("sv_vcn_largest_cluster", _lib.ptr(x), B, x.shape[1], float(eps), int(min_points), int(total_pts), _lib.ptr(out), _lib.ptr(cnt))
     if B:
         if defer_check:
             _lib.defer_check(cnt.min(), _no_cluster)

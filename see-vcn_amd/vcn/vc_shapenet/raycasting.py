@@ -38,10 +38,9 @@ def cameras_to_device(cams, device):
 
 def rays_pinhole(cams, width_px, height_px):
     """cams (C, 12) float64 on the device -> (C, H, W, 6) float32."""
-    L.require_cuda(cams)
     C = cams.shape[0]
     out = torch.empty((C, height_px, width_px, 6), dtype=torch.float32, device=cams.device)
-    call("sv_rays_pinhole", L.ptr(cams), C, int(width_px), int(height_px), L.ptr(out), L.stream())
+    call("sv_rays_pinhole", L.ptr(cams), C, int(width_px), int(height_px), L.ptr(out))
     return out
 
 
@@ -49,7 +48,6 @@ def hit_points(t_hit, segments, width_px, height_px, rays=None, cams=None, boxes
     """rays[hit][:, :3] + rays[hit][:, 3:] * t_hit[hit] for `segments` runs of width_px * height_px rays each, in ray order, segment after segment,
     with the in-box crop: (points (N, 3), flags (N,), obj_points (N, 3), counts (2, segments)) on the device, N = all rays; the rows in use are
     the first counts[0].sum() (points, flags) and counts[1].sum() (obj_points).  No host read."""
-    L.require_cuda(t_hit, rays, cams, boxes)
     dev = t_hit.device
     n = segments * width_px * height_px
     assert t_hit.numel() == n and (rays is None) != (cams is None)
@@ -61,8 +59,8 @@ def hit_points(t_hit, segments, width_px, height_px, rays=None, cams=None, boxes
     if nbytes == 0:
         raise L.SeevcnHipError(f"hit_points: {segments} segments of {width_px} x {height_px} rays exceed the index width (2^31 rays, 65535 segments)")
     scratch = L.workspace.scratch("ray_hit_points", nbytes, dev)
-    call("sv_ray_hit_points", L.ptr(rays), L.ptr(cams), segments, int(width_px), int(height_px), L.ptr(t_hit), L.ptr(boxes), L.ptr(scratch),
-         L.ptr(points), L.ptr(flags), L.ptr(obj_points), L.ptr(counts), L.stream())
+    call("sv_ray_hit_points", L.ptr(rays), L.ptr(cams), segments, int(width_px), int(height_px), L.ptr(t_hit), L.ptr(boxes), L.ptr(scratch), L.ptr(points),
+         L.ptr(flags), L.ptr(obj_points), L.ptr(counts))
     return points, flags, obj_points, counts
 
 
@@ -115,9 +113,9 @@ class RaycastingScene:
             prim = torch.arange(T, dtype=torch.int32, device=dev) - starts
             keys = torch.empty(T, dtype=torch.int64, device=dev)
             scratch = L.workspace.scratch("bvh", int(L.load().sv_bvh_scratch_bytes(T)), dev)
-            call("sv_bvh_keys", L.ptr(tris), T, L.ptr(keys), L.ptr(status), L.ptr(scratch), L.stream())
+            call("sv_bvh_keys", L.ptr(tris), T, L.ptr(keys), L.ptr(status), L.ptr(scratch))
             keys = torch.sort(keys).values
-            call("sv_bvh_build", L.ptr(tris), L.ptr(geom), L.ptr(prim), T, L.ptr(keys), L.ptr(nodes), L.ptr(leaves), L.ptr(scratch), L.stream())
+            call("sv_bvh_build", L.ptr(tris), L.ptr(geom), L.ptr(prim), T, L.ptr(keys), L.ptr(nodes), L.ptr(leaves), L.ptr(scratch))
 
             def refuse(v):
                 if v & 1:
@@ -137,14 +135,14 @@ class RaycastingScene:
 
     def cast_rays(self, rays):
         """rays (..., 6) float32 [origin, direction] -> dict with open3d's keys (no normals), shaped like rays.shape[:-1]."""
-        L.require_cuda(rays)
+        L.require_cuda(rays)                                   # before the scene is built for them
         assert rays.shape[-1] == 6
         nodes, leaves, T, status = self._build()
         flat = rays.detach().to(torch.float32).reshape(-1, 6).contiguous()
         n = flat.shape[0]
         ans = self._answer(n, flat.device)
         call("sv_cast_rays", L.ptr(nodes), L.ptr(leaves), T, L.ptr(flat), n, L.ptr(ans["t_hit"]), L.ptr(ans["geometry_ids"]), L.ptr(ans["primitive_ids"]),
-             L.ptr(ans["primitive_uvs"]), L.ptr(status), L.stream())
+             L.ptr(ans["primitive_uvs"]), L.ptr(status))
         L.flush_checks()                                        # a read only after a rebuild: the refusal of a scene that is not finite
         shape = tuple(rays.shape[:-1])
         return {k: v.reshape(shape + tuple(v.shape[1:])) for k, v in ans.items()}
@@ -156,8 +154,8 @@ class RaycastingScene:
         nodes, leaves, T, status = self._build()
         C = cams.shape[0]
         ans = self._answer(C * width_px * height_px, cams.device)
-        call("sv_cast_pinhole", L.ptr(nodes), L.ptr(leaves), T, L.ptr(cams), C, int(width_px), int(height_px), L.ptr(ans["t_hit"]),
-             L.ptr(ans["geometry_ids"]), L.ptr(ans["primitive_ids"]), L.ptr(ans["primitive_uvs"]), L.ptr(status), L.stream())
+        call("sv_cast_pinhole", L.ptr(nodes), L.ptr(leaves), T, L.ptr(cams), C, int(width_px), int(height_px), L.ptr(ans["t_hit"]), L.ptr(ans["geometry_ids"]),
+             L.ptr(ans["primitive_ids"]), L.ptr(ans["primitive_uvs"]), L.ptr(status))
         return ans
 
     @property

@@ -4,7 +4,6 @@ Forward: bit-identical to the NCHW entry on the permuted map.  Gradient: bit-exa
 float-atomic sum cannot meet, and within (n + 1) * 2^-24 * sum |grad_out * w| of the float64 sum -- a bound the NCHW entry's atomic order meets too."""
 import ctypes
 import functools
-import re
 
 import numpy as np
 import pytest
@@ -28,13 +27,13 @@ B = 2
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
 def test_header_and_binding_declare_the_new_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
+    with open(L.HEADER_PATH) as f:
+        protos = L.parse_declarations(f.read())
     ctype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
     for name, (ret, params) in NEW_ENTRIES.items():
-        m = re.search(r"\b(size_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", src, flags=re.S)
-        assert m, f"{name} is not declared in seevcn_hip.h"
-        declared = [" ".join(p.split()).rsplit(" ", 1)[0] for p in m.group(2).split(",")]        # drop the parameter names
-        assert m.group(1) == ret and declared == params, (name, m.group(1), declared)
+        assert name in protos, f"{name} is not declared in seevcn_hip.h"
+        declared = [p.rsplit(" ", 1)[0] for p in protos[name][1]]                                # drop the parameter names
+        assert protos[name][0] == ret and declared == params, (name, protos[name][0], declared)
         assert name in L.SIGNATURES, f"{name} has no prototype in _lib.py"
         restype, argtypes = L.SIGNATURES[name]
         assert restype == ctype[ret]

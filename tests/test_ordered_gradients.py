@@ -277,11 +277,9 @@ NEW_ENTRIES = ["sv_chamfer_backward_ordered", "sv_group_points_grad_stack_ordere
 def test_ordered_entries_are_declared_bound_and_exported(hip_lib):
     """The three entries and their scratch functions: declared in the header, exported by the library, bound in _lib.py with the header's types."""
     import ctypes
-    import re
     import seevcn_amd._lib as L
-    src = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    protos = {name: (ret, [" ".join(p.split()) for p in params.split(",")])
-              for ret, name, params in re.findall(r"\b(size_t|int)\s+(sv_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S)}
+    with open(L.HEADER_PATH) as f:
+        protos = L.parse_declarations(f.read())
     kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
     for name in NEW_ENTRIES + [n + "_scratch_bytes" for n in NEW_ENTRIES]:
         assert name in protos, f"{name} is not declared in seevcn_hip.h"

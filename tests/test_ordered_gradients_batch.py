@@ -28,11 +28,9 @@ def test_batch_ordered_entries_are_declared_bound_and_exported(hip_lib):
     """The six names: declared in the header, exported, bound with the header's types; an ordered prototype = the plain one + `void* scratch`
     in front of the output pointer; the scratch functions return exactly 16 + 4 * (2 * rows + 2 * keys)."""
     import ctypes
-    import re
     import seevcn_amd._lib as L
-    src = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    protos = {name: (ret, [" ".join(p.split()) for p in params.split(",")])
-              for ret, name, params in re.findall(r"\b(size_t|int)\s+(sv_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S)}
+    with open(L.HEADER_PATH) as f:
+        protos = L.parse_declarations(f.read())
     kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
     for name in ENTRIES + [n + "_scratch_bytes" for n in ENTRIES]:
         assert name in protos, f"{name} is not declared in seevcn_hip.h"

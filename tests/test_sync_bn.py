@@ -28,8 +28,9 @@ def _free_port():
 def test_sync_batchnorm_symbols_in_header_bindings_and_library(hip_lib):
     import seevcn_amd._lib as L
     header = open(L.HEADER_PATH).read()
+    protos = L.parse_declarations(header)
     for name in SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", header), f"{name} not declared in seevcn_hip.h"
+        assert name in protos and protos[name][0] == "int", f"{name} not declared in seevcn_hip.h"
         assert name in L.SIGNATURES, f"{name} has no prototype in _lib.py"
         assert hasattr(hip_lib, name), f"{name} not exported by the library"
     for code, name in ((11, "SV_OP_BN_STATS_LOCAL"), (12, "SV_OP_BN_FINALIZE_GLOBAL"), (13, "SV_OP_BN_BWD_SUMS_LOCAL"), (14, "SV_OP_BN_BWD_APPLY_GLOBAL")):
